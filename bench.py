@@ -172,6 +172,33 @@ def cpu_baseline(preset, B=8, reps=5):
             'config0_forward_b2_s': round(fwd2, 4)}
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: all arrays together stay below this
+
+
+def dump_arrays(path, groups):
+    """--dump-outputs: `groups` = [(bytes for the group, [(name, value), ...]), ...].  Every tensor value goes to
+    path/<name>.npy, floating ones as float32, integer / bool ones as float64 (exact); one that holds more than its even
+    share of the group's bytes is written as that many elements at fixed positions (drawn by a generator seeded with
+    the name, so two runs or two builds sample the same ones).  Returns the bytes written."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for budget, items in groups:
+        items = [(k, v) for k, v in items if torch.is_tensor(v)]
+        for name, t in items:
+            dt = torch.float32 if t.is_floating_point() else torch.float64
+            t = t.detach()
+            n = budget // len(items) // dt.itemsize
+            if t.numel() > n:
+                idx = np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), n, replace=False)
+                t = t.reshape(-1)[torch.from_numpy(np.sort(idx)).to(t.device)]
+            a = t.to(dt).cpu().numpy()
+            np.save(os.path.join(path, name + '.npy'), a)
+            total += a.nbytes
+    return total
+
+
 def _latest_profile(suffix):
     """Newest profiles/rNN*<suffix> by round number (the PMC passes of this same command are committed per round)."""
     import glob
@@ -216,6 +243,9 @@ def main():
                     help='multi-rank REHEARSAL on fewer GPUs than ranks: gloo collectives, ranks share the visible GPUs '
                          '(exercises the world>1 code paths; the numbers mean nothing)')
     ap.add_argument('--zero2', action='store_true', help='reduce-scatter gradients (ZeRO-2 style partition, ds_stage/l2.yaml)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (outputs, loss, parameter gradients; '
+                         'parameters too with --optimizer) as DIR/<name>.npy, rank 0 only, at most 64 MB in all')
     args = ap.parse_args()
 
     t_start = time.perf_counter()
@@ -294,15 +324,20 @@ def main():
         else:
             opt = optim.create_optimizer(ocfg, model)
 
-    def step():
+    last = {}        # --dump-outputs: what the last timed step returned
+
+    def step(keep=False):
         for p in model.parameters():
             p.grad = None
         if args.objective == 'full':
             ret = model(dict(dbatch))
             loss = sum(v for k, v in ret.items() if 'task_loss' in k)
         else:
-            x, _ = model.forward_features(img=img, txt=ids, img_attn_masks=imask, txt_attn_masks=tmask)
+            x, co_masks = model.forward_features(img=img, txt=ids, img_attn_masks=imask, txt_attn_masks=tmask)
             loss = (x * R).sum()
+            ret = {'features': x, 'co_attn_masks': co_masks}
+        if keep:
+            last.update(ret, loss=loss)
         if reducer is not None:
             reducer.prepare(loss)
         loss.backward()
@@ -331,8 +366,8 @@ def main():
     log('warm-up done')
     hip.profile_start()                   # HIP-event pairs around every GEMM launch of the timed region (in-library)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
     t_issue = time.perf_counter() - t0    # host time to ENQUEUE the steps (launch-bound if close to dt)
     barrier()
     dt = time.perf_counter() - t0
@@ -342,6 +377,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     assert torch.isfinite(loss).item(), 'non-finite loss'
+    if args.dump_outputs and rank == 0:
+        # before the steps below overwrite the gradients: half of the bytes for the outputs, a quarter for the
+        # gradients (an eighth each for gradients and updated parameters when the optimizer ran)
+        named = list(model.named_parameters())
+        groups = [(DUMP_BYTES // 2, sorted(last.items())),
+                  (DUMP_BYTES // (8 if opt is not None else 4), [('grad.' + n, p.grad) for n, p in named])]
+        if opt is not None:
+            groups.append((DUMP_BYTES // 8, [('param.' + n, p) for n, p in named]))
+        nbytes = dump_arrays(args.dump_outputs, groups)
+        log(f'last timed step written to {args.dump_outputs} ({nbytes / 2 ** 20:.1f} MB)')
+    last.clear()
     # host cost of enqueueing one step, measured with an EMPTY device queue (in the timed loop above the host runs
     # ahead until the launch queue is full and then waits for the GPU: t_issue there is back-pressure, not host work)
     hs = []
