@@ -1,14 +1,19 @@
 // Fused multi-head softmax attention for VLMo on gfx950 (head_dim 64).
 // Reference: Attention.forward, vlmo.py:79-95:
 //   attn = softmax((q k^T) * dh^-0.5 + keymask(-inf)) ; dropout ; ctx = attn v
-// VLMo sequences are short (64 / 197 / 261 tokens), so a whole head's K and V
-// sit in LDS (<= 36 KB each) and the scores of a 32-query tile never leave
-// registers: no N x N tensor in HBM (the reference materialises [B,h,N,N]
+// At 224 px VLMo sequences are short (64 / 197 / 261 tokens), so a whole head's
+// K and V sit in LDS (<= 36 KB each) and the scores of a 32-query tile never
+// leave registers: no N x N tensor in HBM (the reference materialises [B,h,N,N]
 // several times).  Forward: attn_fwd1_kernel (one wave per query tile, key
 // tiles one at a time with a lazily rescaled running maximum; sequences of up
 // to 288 tokens) and attn_fwd_kernel (128-key chunks with an exact running
-// maximum; longer sequences).  Backward: attn_bwd1_kernel (single pass, up to
-// 256 tokens) and attn_bwd_kernel (two phases, up to 288).
+// maximum; up to 512).  Backward: attn_bwd1_kernel (single pass, up to 256
+// tokens) and attn_bwd_kernel (two phases, up to 288).
+// Higher resolutions (384 / 480 px: 577 / 901 image tokens, up to 965 fused)
+// take the streaming kernels: attn_fwd_long_kernel for launches of 513 - 1024
+// tokens, attn_dkdv_long_kernel + attn_dq_long_kernel for 289 - 1024; K / V
+// (or Q / dO) pass through a two-slot LDS ring instead of staying resident.
+// The launch's max_len picks the kernels; nothing else does.
 //
 // Orientation: scores are computed TRANSPOSED, S^T[key][query] = K . Q^T, so a
 // lane owns one query column (softmax reductions are in-register + one
@@ -71,8 +76,9 @@ __device__ __forceinline__ void stage_image(const bf16* base, int ld, int col0, 
 }
 
 // ---- attention dropout (vlmo.py:93): counter-based, regenerated in the backward -------------------------------
-// keep(seq*heads + head, q, key) <=> top 16 bits of att_mix(c * G + att_key) >= thresh, c = q * 512 + key (sequences
-// are < 512 tokens).  The soft-max arithmetic of these kernels is bound by VALU ISSUE (one wave alone on a SIMD issues
+// keep(seq*heads + head, q, key) <=> top 16 bits of att_mix(c * G + att_key) >= thresh, c = q * 512 + key for a
+// sequence of <= 512 tokens (every sequence these resident kernels take; the streaming kernels use q * 1024 + key
+// above 512 tokens, see att_stride).  The soft-max arithmetic of these kernels is bound by VALU ISSUE (one wave alone on a SIMD issues
 // a vector instruction every 4 cycles; the single-pass backward spends ~2/3 of a step in it), so the hash is as short
 // as its use allows: the counter is affine in q and in key (either orientation advances it with ONE add of a
 // compile-time constant), one xor-shift + one multiply mix it, and only the TOP half of the product is used -- the
@@ -1078,6 +1084,504 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
     if (a.warm) warm_retire(warm_word);
 }
 
+// ------------------------------------------------------------------ streaming kernels, 289 .. 1024 tokens
+// The kernels above keep a whole head's operand images resident in LDS (256 B per token forward, ~512 B backward), which
+// caps them at 576 / 288 tokens.  The three kernels below stream the swept operand through a two-slot LDS ring instead:
+// a chunk = ATT_LCH tiles of 32 tokens x two images (K | V, or Q | dO) = 32 KiB, chunk j + 1 in flight (LDS-DMA) while
+// chunk j is consumed, one barrier per chunk.  One workgroup per (sequence, head) of ATT_LW waves; wave w owns tile
+// w + ATT_LW r in round r, so the number of rounds follows the sequence's OWN length (the short text sequences of a
+// mixed launch take one round of one chunk).  The per-tile arithmetic is that of attn_fwd_kernel / attn_bwd_kernel
+// (scores transposed, key on the lane where the next MFMA wants it).
+//   forward   attn_fwd_long_kernel   waves own query tiles, K / V chunks streamed; exact running maximum per chunk
+//   backward  attn_dkdv_long_kernel  waves own key tiles, Q / dO chunks streamed: dK, dV, dv column sums
+//             attn_dq_long_kernel    waves own query tiles, K / V chunks streamed: dQ, dq column sums
+// The two backward kernels write disjoint columns of dqkv and recompute P from lse and delta = rowsum(dO . O) on their
+// own: no workspace, no global atomics, and every output element is summed in a fixed order (bitwise reproducible).
+// The column sums are folded per wave in registers -> one LDS slot per wave -> summed over the waves in wave order.
+#define ATT_LW 8
+#define ATT_LCH 4
+#define ATT_LBUF (ATT_LCH * 4096)               // one image of one chunk
+#define ATT_LMAX 1024                           // longest sequence of the streaming kernels
+#define ATT_LDS_FWD (4 * ATT_LBUF + ATT_LMAX * 4)
+#define ATT_LDS_BWD (4 * ATT_LBUF + 3 * ATT_LMAX * 4 + ATT_LW * 64 * 4)
+
+// dropout counter stride of a sequence of N tokens: c = q * stride + key.  512 up to 512 tokens (the counter of the
+// kernels above, bit for bit), 1024 beyond: collision-free up to 1024 tokens.  Chosen from the sequence's own length,
+// not the launch's max_len, so that a backward launch over a subset of a forward launch's sequences regenerates its mask.
+__device__ __forceinline__ uint32_t att_stride(int N) { return N > 512 ? 1024u : 512u; }
+
+struct SeqRows {
+    int rowA, lenA, rowB, N;
+    __device__ __forceinline__ SeqRows(const int32_t* seg, int sidx)
+        : rowA(seg[4 * sidx + 0]), lenA(seg[4 * sidx + 1]), rowB(seg[4 * sidx + 2]), N(seg[4 * sidx + 1] + seg[4 * sidx + 3]) {}
+    __device__ __forceinline__ int row(int tok) const {        // padded tokens read the last real row
+        tok = min(tok, N - 1);
+        return tok < lenA ? rowA + tok : rowB + (tok - lenA);
+    }
+};
+
+// LDS-DMA of tiles [t0, t0 + nt) of two 64-column operands into dual-use images ia / ib (tile-local rows: the swizzle of
+// att_off depends on the row modulo 32 only)
+__device__ __forceinline__ void stage_chunk(const bf16* pa, int lda, const bf16* pb, int ldb, const SeqRows& sr, int t0,
+                                            int nt, char* ia, char* ib, int w, int lane) {
+    const int chhi = lane >> 5, rowlo = (lane >> 2) & 7, pc = lane & 3;
+    for (int ii = w; ii < nt * 4; ii += ATT_LW) {
+        const int row = t0 * 32 + ii * 8 + rowlo;
+        const int ch = chhi * 4 + (pc ^ ((row >> 2) & 3));
+        const size_t r = (size_t)sr.row(row);
+        glds16(pa + r * lda + ch * 8, ia + ii * 1024);
+        glds16(pb + r * ldb + ch * 8, ib + ii * 1024);
+    }
+}
+
+// per-wave column sums of 32 tokens x 64 features (t[dt][r] as in colsum_tiles, weight w per lane) added into this wave's
+// LDS slot part[64]: one writer per slot, a fixed order of additions
+__device__ __forceinline__ void colsum_wave(const f32x16* t, float wt, float* part, int lane) {
+    const int h = lane >> 5;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float v = half_wave_total(t[dt][r] * wt);
+            if ((lane & 31) == 31) part[dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] += v;
+        }
+}
+
+// delta (x keep_prob) and the log2-domain LSE of every query of the sequence (+inf / 0 on padded queries), key bias
+__device__ __forceinline__ void bwd_row_constants(const AttnArgs& a, const SeqRows& sr, int bh, int hd, int npad,
+                                                  float* lseq, float* delta, float* kbias) {
+    const float keep_prob = 1.f / a.inv_keep;
+    for (int i = threadIdx.x; i < npad; i += blockDim.x) {
+        float dl = 0.f, lq = INFINITY;
+        const int row = sr.row(i);
+        if (i < sr.N) {
+            const size_t o = (size_t)row * a.d + hd * 64;
+            bf16x8 x[8], y[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                x[c] = *(const bf16x8*)(a.ctx + o + 8 * c);
+                y[c] = *(const bf16x8*)(a.dctx + o + 8 * c);
+            }
+            lq = a.lse[(size_t)bh * a.lse_stride + i] * LOG2E;
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) dl += (float)x[c][j] * (float)y[c][j];
+        }
+        delta[i] = dl * keep_prob;
+        lseq[i] = lq;
+        if (kbias) kbias[i] = (i < sr.N && (!a.keymask || a.keymask[row] != 0)) ? 0.f : -INFINITY;
+    }
+}
+
+__global__ __launch_bounds__(512) void attn_fwd_long_kernel(const AttnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* ring = smem;                                  // [2][K | V]
+    float* kbias = (float*)(smem + 4 * ATT_LBUF);
+
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bh = blockIdx.x, sidx = bh / a.heads, hd = bh % a.heads;
+    const int ld = 3 * a.d;
+    const SeqRows sr(a.seg, sidx);
+    const int N = sr.N;
+    if (N <= 0) return;
+    const int nq = (N + 31) >> 5, nch = (nq + ATT_LCH - 1) / ATT_LCH, nrounds = (nq + ATT_LW - 1) / ATT_LW;
+    const bf16* kb0 = a.qkv + a.d + hd * 64;
+    const bf16* vb0 = a.qkv + 2 * a.d + hd * 64;
+    stage_chunk(kb0, ld, vb0, ld, sr, 0, min(ATT_LCH, nq), ring, ring + ATT_LBUF, w, lane);
+    for (int i = threadIdx.x; i < nq * 32; i += blockDim.x)
+        kbias[i] = (i < N && (!a.keymask || a.keymask[sr.row(i)] != 0)) ? 0.f : -INFINITY;
+
+    const int l31 = lane & 31, h = lane >> 5;
+    const uint32_t akey = att_key(a.seed, bh + a.bh0);
+    const uint32_t stride = att_stride(N);
+    int qi = 0, qrow = 0;
+    uint32_t rq = 0;
+    bf16x8 qf[4];
+    float m_run = -INFINITY, l_run = 0.f;
+    f32x16 O[2] = {zero16(), zero16()};
+    const int nsteps = nrounds * nch;
+    for (int j = 0; j < nsteps; ++j) {
+        const int rd = j / nch, c = j - rd * nch;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                // chunk j landed; everybody is done with chunk j - 1's slot
+        if (j + 1 < nsteps) {
+            const int t0 = ((j + 1) % nch) * ATT_LCH;
+            char* nb = ring + ((j + 1) & 1) * 2 * ATT_LBUF;
+            stage_chunk(kb0, ld, vb0, ld, sr, t0, min(ATT_LCH, nq - t0), nb, nb + ATT_LBUF, w, lane);
+        }
+        const char* Kc = ring + (j & 1) * 2 * ATT_LBUF;
+        const char* Vc = Kc + ATT_LBUF;
+        const int qt = rd * ATT_LW + w;
+        if (qt >= nq) continue;                         // wave-uniform: no query tile for this wave in this round
+        if (c == 0) {
+            qi = qt * 32 + l31;
+            qrow = sr.row(qi);
+            rq = ((uint32_t)qi * stride + 4u * h) * ATT_G + akey;
+            const bf16* qp = a.qkv + (size_t)qrow * ld + hd * 64 + 8 * h;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qp + 16 * s);
+            m_run = -INFINITY, l_run = 0.f;
+            O[0] = zero16(), O[1] = zero16();
+        }
+        const int c0 = c * ATT_LCH;
+        f32x16 S[ATT_LCH];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int cc = 0; cc < ATT_LCH; ++cc) {
+            S[cc] = zero16();
+            const int kt = c0 + cc;
+            if (kt < nq) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) S[cc] = Elem<bf16>::mfma(row_frag(Kc, cc * 32, s, lane), qf[s], S[cc]);
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const f32x4 kb = *(const f32x4*)(kbias + kt * 32 + 8 * g4 + 4 * h);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float t = S[cc][4 * g4 + e] * a.scale_log2e + kb[e];
+                        S[cc][4 * g4 + e] = t;
+                        mx = fmaxf(mx, t);
+                    }
+                }
+            }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx);
+        const bool dead = (m_new == -INFINITY);
+        const float alpha = dead ? 1.f : __builtin_amdgcn_exp2f(m_run - m_new);
+        float lsum = 0.f;
+#pragma unroll
+        for (int cc = 0; cc < ATT_LCH; ++cc) {
+            if (c0 + cc < nq) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float p = dead ? 0.f : __builtin_amdgcn_exp2f(S[cc][i] - m_new);
+                    S[cc][i] = p;
+                    lsum += p;
+                }
+            }
+        }
+        lsum += __shfl_xor(lsum, 32, 64);
+        l_run = l_run * alpha + lsum;
+        m_run = m_new;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) O[dt][i] *= alpha;
+#pragma unroll
+        for (int cc = 0; cc < ATT_LCH; ++cc) {
+            const int kt = c0 + cc;
+            if (kt < nq) {
+                if (a.drop_thresh) {
+                    const uint32_t rk = rq + (uint32_t)(kt * 32) * ATT_G;
+#pragma unroll
+                    for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (att_mix(rk + (uint32_t)(8 * g4 + e) * ATT_G) < a.drop_cmp) S[cc][4 * g4 + e] = 0.f;
+                }
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    bf16x8 pf;
+#pragma unroll
+                    for (int jj = 0; jj < 8; ++jj) pf[jj] = (bf16)S[cc][8 * s2 + jj];
+#pragma unroll
+                    for (int dt = 0; dt < 2; ++dt)
+                        O[dt] = Elem<bf16>::mfma(tr_frag(Vc, cc * 32 + 16 * s2, dt * 32, lane), pf, O[dt]);
+                }
+            }
+        }
+        if (c == nch - 1 && qi < N) {
+            const float inv = a.inv_keep / l_run;
+            bf16* op = a.out + (size_t)qrow * a.d + hd * 64 + 4 * h;
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    bf16x4 o = {(bf16)(O[dt][4 * g4 + 0] * inv), (bf16)(O[dt][4 * g4 + 1] * inv),
+                                (bf16)(O[dt][4 * g4 + 2] * inv), (bf16)(O[dt][4 * g4 + 3] * inv)};
+                    *(bf16x4*)(op + dt * 32 + 8 * g4) = o;
+                }
+            if (h == 0 && a.lse) a.lse[(size_t)bh * a.lse_stride + qi] = (m_run + log2f(l_run)) * LN2;
+        }
+    }
+}
+
+// dQ^T[d][q] = sum_k K^T[d][k] dS^T[k][q]: waves own query tiles, K / V chunks streamed (the dQ item of attn_bwd_kernel)
+__global__ __launch_bounds__(512) void attn_dq_long_kernel(const AttnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* ring = smem;                                  // [2][K | V]
+    float* kbias = (float*)(smem + 4 * ATT_LBUF);
+    float* lseq = kbias + ATT_LMAX;
+    float* delta = lseq + ATT_LMAX;
+    float* part = delta + ATT_LMAX;                     // [ATT_LW][64] column sums of dq
+
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bh = blockIdx.x, sidx = bh / a.heads, hd = bh % a.heads;
+    const int ld = 3 * a.d;
+    const SeqRows sr(a.seg, sidx);
+    const int N = sr.N;
+    if (N <= 0) {
+        if (a.qvsum && threadIdx.x < 64) a.qvsum[(size_t)sidx * 2 * a.d + hd * 64 + threadIdx.x] = 0.f;
+        return;
+    }
+    const int nq = (N + 31) >> 5, nch = (nq + ATT_LCH - 1) / ATT_LCH, nrounds = (nq + ATT_LW - 1) / ATT_LW;
+    const bf16* kb0 = a.qkv + a.d + hd * 64;
+    const bf16* vb0 = a.qkv + 2 * a.d + hd * 64;
+    stage_chunk(kb0, ld, vb0, ld, sr, 0, min(ATT_LCH, nq), ring, ring + ATT_LBUF, w, lane);
+    bwd_row_constants(a, sr, bh, hd, nq * 32, lseq, delta, kbias);
+    for (int i = threadIdx.x; i < ATT_LW * 64; i += blockDim.x) part[i] = 0.f;
+
+    const int l31 = lane & 31, h = lane >> 5;
+    const uint32_t akey = att_key(a.seed, bh + a.bh0);
+    const uint32_t stride = att_stride(N);
+    const float out_scale = a.scale * a.inv_keep;
+    int qi = 0;
+    uint32_t rq = 0;
+    float lq = 0.f, dl = 0.f;
+    bf16x8 qf[4], df[4];
+    f32x16 dQ[2] = {zero16(), zero16()};
+    const int nsteps = nrounds * nch;
+    for (int j = 0; j < nsteps; ++j) {
+        const int rd = j / nch, c = j - rd * nch;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (j + 1 < nsteps) {
+            const int t0 = ((j + 1) % nch) * ATT_LCH;
+            char* nb = ring + ((j + 1) & 1) * 2 * ATT_LBUF;
+            stage_chunk(kb0, ld, vb0, ld, sr, t0, min(ATT_LCH, nq - t0), nb, nb + ATT_LBUF, w, lane);
+        }
+        const char* Kc = ring + (j & 1) * 2 * ATT_LBUF;
+        const char* Vc = Kc + ATT_LBUF;
+        const int qt = rd * ATT_LW + w;
+        if (qt >= nq) continue;
+        if (c == 0) {
+            qi = qt * 32 + l31;
+            const size_t qrow = (size_t)sr.row(qi);
+            const bf16* qp = a.qkv + qrow * ld + hd * 64 + 8 * h;
+            const bf16* dp = a.dctx + qrow * a.d + hd * 64 + 8 * h;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                qf[s] = *(const bf16x8*)(qp + 16 * s);
+                df[s] = *(const bf16x8*)(dp + 16 * s);
+            }
+            lq = lseq[qi], dl = delta[qi];
+            rq = ((uint32_t)qi * stride + 4u * h) * ATT_G + akey;
+            dQ[0] = zero16(), dQ[1] = zero16();
+        }
+        const int c0 = c * ATT_LCH;
+#pragma unroll
+        for (int cc = 0; cc < ATT_LCH; ++cc) {
+            const int kt = c0 + cc;
+            if (kt >= nq) break;
+            f32x16 S = zero16(), dP = zero16();
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                S = Elem<bf16>::mfma(row_frag(Kc, cc * 32, s, lane), qf[s], S);
+                dP = Elem<bf16>::mfma(row_frag(Vc, cc * 32, s, lane), df[s], dP);
+            }
+            const uint32_t rk = rq + (uint32_t)(kt * 32) * ATT_G;
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const f32x4 kb = *(const f32x4*)(kbias + kt * 32 + 8 * g4 + 4 * h);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int i = 4 * g4 + e;
+                    const float p = __builtin_amdgcn_exp2f(S[i] * a.scale_log2e + (kb[e] - lq));
+                    bool keep = true;
+                    if (a.drop_thresh) keep = att_mix(rk + (uint32_t)(8 * g4 + e) * ATT_G) >= a.drop_cmp;
+                    S[i] = p * ((keep ? dP[i] : 0.f) - dl);
+                }
+            }
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                bf16x8 sf;
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) sf[jj] = (bf16)S[8 * s2 + jj];
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt)
+                    dQ[dt] = Elem<bf16>::mfma(tr_frag(Kc, cc * 32 + 16 * s2, dt * 32, lane), sf, dQ[dt]);
+            }
+        }
+        if (c == nch - 1) {
+            if (a.qvsum) colsum_wave(dQ, qi < N ? 1.f : 0.f, part + 64 * w, lane);
+            if (qi < N) {
+                bf16* op = a.out + (size_t)sr.row(qi) * ld + hd * 64 + 4 * h;
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                    for (int g4 = 0; g4 < 4; ++g4) {
+                        bf16x4 o = {(bf16)(dQ[dt][4 * g4 + 0] * out_scale), (bf16)(dQ[dt][4 * g4 + 1] * out_scale),
+                                    (bf16)(dQ[dt][4 * g4 + 2] * out_scale), (bf16)(dQ[dt][4 * g4 + 3] * out_scale)};
+                        *(bf16x4*)(op + dt * 32 + 8 * g4) = o;
+                    }
+            }
+        }
+    }
+    if (a.qvsum) {
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            float s = 0.f;
+            for (int ww = 0; ww < ATT_LW; ++ww) s += part[64 * ww + threadIdx.x];
+            a.qvsum[(size_t)sidx * 2 * a.d + hd * 64 + threadIdx.x] = s * out_scale;
+        }
+    }
+}
+
+// dV^T[d][k] = sum_q dO^T[d][q] Pd[q][k], dK^T[d][k] = sum_q Q^T[d][q] dS[q][k]: waves own key tiles, Q / dO chunks
+// streamed (the dK/dV item of attn_bwd_kernel)
+__global__ __launch_bounds__(512) void attn_dkdv_long_kernel(const AttnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* ring = smem;                                  // [2][Q | dO]
+    float* lseq = (float*)(smem + 4 * ATT_LBUF);
+    float* delta = lseq + ATT_LMAX;
+    float* part = delta + 2 * ATT_LMAX;                 // [ATT_LW][64] column sums of dv (same layout as the dQ kernel)
+
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bh = blockIdx.x, sidx = bh / a.heads, hd = bh % a.heads;
+    const int ld = 3 * a.d;
+    const SeqRows sr(a.seg, sidx);
+    const int N = sr.N;
+    if (N <= 0) {
+        if (a.qvsum && threadIdx.x < 64) a.qvsum[(size_t)sidx * 2 * a.d + a.d + hd * 64 + threadIdx.x] = 0.f;
+        return;
+    }
+    const int nq = (N + 31) >> 5, nch = (nq + ATT_LCH - 1) / ATT_LCH, nrounds = (nq + ATT_LW - 1) / ATT_LW;
+    const bf16* qb0 = a.qkv + hd * 64;
+    const bf16* db0 = a.dctx + hd * 64;
+    stage_chunk(qb0, ld, db0, a.d, sr, 0, min(ATT_LCH, nq), ring, ring + ATT_LBUF, w, lane);
+    bwd_row_constants(a, sr, bh, hd, nq * 32, lseq, delta, nullptr);
+    for (int i = threadIdx.x; i < ATT_LW * 64; i += blockDim.x) part[i] = 0.f;
+
+    const int l31 = lane & 31, h = lane >> 5;
+    const uint32_t akey = att_key(a.seed, bh + a.bh0);
+    const uint32_t gs = att_stride(N) * ATT_G;          // counter advance of one query
+    const float out_scale = a.scale * a.inv_keep;
+    int ki = 0;
+    uint32_t rl = 0;
+    float kb = 0.f;
+    bf16x8 kf[4], vf[4];
+    f32x16 dK[2] = {zero16(), zero16()}, dV[2] = {zero16(), zero16()};
+    const int nsteps = nrounds * nch;
+    for (int j = 0; j < nsteps; ++j) {
+        const int rd = j / nch, c = j - rd * nch;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (j + 1 < nsteps) {
+            const int t0 = ((j + 1) % nch) * ATT_LCH;
+            char* nb = ring + ((j + 1) & 1) * 2 * ATT_LBUF;
+            stage_chunk(qb0, ld, db0, a.d, sr, t0, min(ATT_LCH, nq - t0), nb, nb + ATT_LBUF, w, lane);
+        }
+        const char* Qc = ring + (j & 1) * 2 * ATT_LBUF;
+        const char* Dc = Qc + ATT_LBUF;
+        const int kt = rd * ATT_LW + w;
+        if (kt >= nq) continue;
+        if (c == 0) {
+            ki = kt * 32 + l31;
+            const int krow = sr.row(ki);
+            const bf16* kp = a.qkv + (size_t)krow * ld + a.d + hd * 64 + 8 * h;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                kf[s] = *(const bf16x8*)(kp + 16 * s);
+                vf[s] = *(const bf16x8*)(kp + a.d + 16 * s);
+            }
+            kb = (ki < N && (!a.keymask || a.keymask[krow] != 0)) ? 0.f : -INFINITY;
+            rl = (uint32_t)ki * ATT_G + akey + (uint32_t)(4 * h) * gs;
+            dK[0] = zero16(), dK[1] = zero16(), dV[0] = zero16(), dV[1] = zero16();
+        }
+        const int c0 = c * ATT_LCH;
+#pragma unroll
+        for (int cc = 0; cc < ATT_LCH; ++cc) {
+            const int qt = c0 + cc;
+            if (qt >= nq) break;
+            f32x16 S = zero16(), dP = zero16();
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                S = Elem<bf16>::mfma(row_frag(Qc, cc * 32, s, lane), kf[s], S);
+                dP = Elem<bf16>::mfma(row_frag(Dc, cc * 32, s, lane), vf[s], dP);
+            }
+            f32x16 Pd;
+            const uint32_t rqt = rl + (uint32_t)(qt * 32) * gs;
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const int q0 = qt * 32 + 8 * g4 + 4 * h;
+                const f32x4 lq = *(const f32x4*)(lseq + q0);
+                const f32x4 dl = *(const f32x4*)(delta + q0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int i = 4 * g4 + e;
+                    const float p = __builtin_amdgcn_exp2f(S[i] * a.scale_log2e + (kb - lq[e]));
+                    bool keep = true;
+                    if (a.drop_thresh) keep = att_mix(rqt + (uint32_t)(8 * g4 + e) * gs) >= a.drop_cmp;
+                    Pd[i] = keep ? p : 0.f;
+                    S[i] = p * ((keep ? dP[i] : 0.f) - dl[e]);
+                }
+            }
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                bf16x8 pf, sf;
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) {
+                    pf[jj] = (bf16)Pd[8 * s2 + jj];
+                    sf[jj] = (bf16)S[8 * s2 + jj];
+                }
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt) {
+                    dV[dt] = Elem<bf16>::mfma(tr_frag(Dc, cc * 32 + 16 * s2, dt * 32, lane), pf, dV[dt]);
+                    dK[dt] = Elem<bf16>::mfma(tr_frag(Qc, cc * 32 + 16 * s2, dt * 32, lane), sf, dK[dt]);
+                }
+            }
+        }
+        if (c == nch - 1) {
+            if (a.qvsum) colsum_wave(dV, ki < N ? 1.f : 0.f, part + 64 * w, lane);
+            if (ki < N) {
+                bf16* op = a.out + (size_t)sr.row(ki) * ld + hd * 64 + 4 * h;
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                    for (int g4 = 0; g4 < 4; ++g4) {
+                        bf16x4 ok = {(bf16)(dK[dt][4 * g4 + 0] * out_scale), (bf16)(dK[dt][4 * g4 + 1] * out_scale),
+                                     (bf16)(dK[dt][4 * g4 + 2] * out_scale), (bf16)(dK[dt][4 * g4 + 3] * out_scale)};
+                        bf16x4 ov = {(bf16)(dV[dt][4 * g4 + 0] * a.inv_keep), (bf16)(dV[dt][4 * g4 + 1] * a.inv_keep),
+                                     (bf16)(dV[dt][4 * g4 + 2] * a.inv_keep), (bf16)(dV[dt][4 * g4 + 3] * a.inv_keep)};
+                        *(bf16x4*)(op + a.d + dt * 32 + 8 * g4) = ok;
+                        *(bf16x4*)(op + 2 * a.d + dt * 32 + 8 * g4) = ov;
+                    }
+            }
+        }
+    }
+    if (a.qvsum) {
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            float s = 0.f;
+            for (int ww = 0; ww < ATT_LW; ++ww) s += part[64 * ww + threadIdx.x];
+            a.qvsum[(size_t)sidx * 2 * a.d + a.d + hd * 64 + threadIdx.x] = s * a.inv_keep;
+        }
+    }
+}
+
+int launch_fwd_long(const AttnArgs& a, int nblocks, hipStream_t st) {
+    static DeviceOnce once;
+    if (once.first())
+        (void)hipFuncSetAttribute((const void*)attn_fwd_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_FWD);
+    hipLaunchKernelGGL(attn_fwd_long_kernel, dim3(nblocks), dim3(64 * ATT_LW), ATT_LDS_FWD, st, a);
+    return 0;
+}
+int launch_bwd_long(const AttnArgs& a, int nblocks, hipStream_t st) {
+    static DeviceOnce once;
+    if (once.first()) {
+        (void)hipFuncSetAttribute((const void*)attn_dkdv_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_BWD);
+        (void)hipFuncSetAttribute((const void*)attn_dq_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_BWD);
+    }
+    hipLaunchKernelGGL(attn_dkdv_long_kernel, dim3(nblocks), dim3(64 * ATT_LW), ATT_LDS_BWD, st, a);
+    hipLaunchKernelGGL(attn_dq_long_kernel, dim3(nblocks), dim3(64 * ATT_LW), ATT_LDS_BWD, st, a);
+    return 0;
+}
+
 // dynamic-LDS limit already raised for a kernel on a device (a process may drive several GPUs)
 int& lds_limit_set(int which) {
     static int lim[4][64];
@@ -1148,7 +1652,7 @@ int check_common(const char* fn, const void* qkv, const int32_t* seg, int num_se
 extern "C" int vlmo_attn_fwd(const void* qkv, const int32_t* seg, int num_seq, const int32_t* keymask, void* ctx,
                              float* lse, int lse_stride, int heads, int d, int max_len, float scale,
                              uint32_t drop_thresh, float inv_keep, uint64_t seed, int mask_seq0, hipStream_t stream) {
-    if (int rc = check_common("vlmo_attn_fwd", qkv, seg, num_seq, heads, d, max_len, 576)) return rc;
+    if (int rc = check_common("vlmo_attn_fwd", qkv, seg, num_seq, heads, d, max_len, 1024)) return rc;
     VLMO_CHECK_ARG(ctx, "vlmo_attn_fwd: null ctx");
     VLMO_CHECK_ARG(!lse || lse_stride >= max_len, "vlmo_attn_fwd: lse_stride too small");
     AttnArgs a{};
@@ -1168,6 +1672,11 @@ extern "C" int vlmo_attn_fwd(const void* qkv, const int32_t* seg, int num_seq, c
     a.seed = seed;
     a.bh0 = mask_seq0 * heads;
     const int nt = (max_len + 31) / 32, nb = num_seq * heads;
+    if (max_len > 512) {        // 513 .. 1024 tokens: K / V streamed (the resident kernels' 512-token dropout counter ends here)
+        launch_fwd_long(a, nb, stream);
+        VLMO_CHECK_LAUNCH("vlmo_attn_fwd(long)");
+        return 0;
+    }
     static const bool chunked = [] {
         const char* e = getenv("VLMO_ATTN_FWD");
         return e && !strcmp(e, "chunked");
@@ -1182,7 +1691,7 @@ extern "C" int vlmo_attn_bwd(const void* qkv, const void* ctx, const void* dctx,
                              const int32_t* seg, int num_seq, const int32_t* keymask, void* dqkv, float* qv_colsum,
                              int heads, int d, int max_len, float scale, uint32_t drop_thresh, float inv_keep,
                              uint64_t seed, int mask_seq0, hipStream_t stream) {
-    if (int rc = check_common("vlmo_attn_bwd", qkv, seg, num_seq, heads, d, max_len, 288)) return rc;
+    if (int rc = check_common("vlmo_attn_bwd", qkv, seg, num_seq, heads, d, max_len, 1024)) return rc;
     VLMO_CHECK_ARG(ctx && dctx && lse && dqkv, "vlmo_attn_bwd: null pointer");
     VLMO_CHECK_ARG(lse_stride >= max_len, "vlmo_attn_bwd: lse_stride too small");
     AttnArgs a{};
@@ -1207,6 +1716,11 @@ extern "C" int vlmo_attn_bwd(const void* qkv, const void* ctx, const void* dctx,
     static const int warm = getenv("VLMO_ATTN_WARM") ? atoi(getenv("VLMO_ATTN_WARM")) : 0;      // measurement aid
     a.warm = warm;
     const int nt = (max_len + 31) / 32, nb = num_seq * heads;
+    if (max_len > 288) {        // 289 .. 1024 tokens: the dK/dV and the dQ streaming kernels, back to back
+        launch_bwd_long(a, nb, stream);
+        VLMO_CHECK_LAUNCH("vlmo_attn_bwd(long)");
+        return 0;
+    }
     static const bool two_phase = getenv("VLMO_ATTN_BWD") && !strcmp(getenv("VLMO_ATTN_BWD"), "two_phase");   // measurement aid
     static const bool split = getenv("VLMO_ATTN_BWD_SPLIT") && atoi(getenv("VLMO_ATTN_BWD_SPLIT")) != 0;       // measurement aid, off
     if (!two_phase && split && nt == 9) {

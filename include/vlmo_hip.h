@@ -163,15 +163,21 @@ int vlmo_ln_resid_bwd(const void* dy, const float* x, const float* w, const floa
 /* Fused softmax attention over packed rows (vlmo.py:79-95).
  * qkv [M, 3*d] (q | k | v, head-major inside each third), ctx [M, d].
  * seg[s] = {rowA, lenA, rowB, lenB}: sequence s = rows [rowA,rowA+lenA) ++ [rowB,rowB+lenB).
- * keymask [M] int32 (0 = padded key, vlmo.py:89-91) or NULL.  lse [S, heads, NPAD] fp32.
- * Attention dropout (vlmo.py:93) is a counter hash of (seed, mask_seq0 + s, head, query, key): a backward launch over
- * the sequences [s0, s0 + n) of a forward launch passes mask_seq0 = s0 and the forward's seed to regenerate its mask. */
+ * keymask [M] int32 (0 = padded key, vlmo.py:89-91) or NULL.  lse [S, heads, NPAD] fp32 (natural log, row stride
+ * lse_stride >= max_len).  max_len (the longest sequence of the launch) may be up to 1024; it picks the kernels:
+ * <= 512 resident K / V, 513 - 1024 streamed.  Longer launches are refused.
+ * Attention dropout (vlmo.py:93) is a counter hash of (seed, mask_seq0 + s, head, query, key) with the counter
+ * query * S + key, S = 512 for a sequence of <= 512 tokens and 1024 above -- chosen by the sequence's own length, not
+ * by max_len: a backward launch over the sequences [s0, s0 + n) of a forward launch passes mask_seq0 = s0 and the
+ * forward's seed to regenerate its mask, whatever its own max_len. */
 int vlmo_attn_fwd(const void* qkv, const int32_t* seg, int num_seq, const int32_t* keymask,
                   void* ctx, float* lse, int lse_stride, int heads, int d, int max_len,
                   float scale, uint32_t drop_thresh, float inv_keep, uint64_t seed, int mask_seq0,
                   hipStream_t stream);
 /* qv_colsum (optional, [num_seq][2 d] fp32, written): per sequence the column sums of its tokens' dq | dv rows -- the
- * q_bias / v_bias gradient (vlmo.py:71-75) is their sum over the sequences, so nobody re-reads dqkv for it. */
+ * q_bias / v_bias gradient (vlmo.py:71-75) is their sum over the sequences, so nobody re-reads dqkv for it.
+ * max_len up to 1024: <= 288 the resident kernels, 289 - 1024 a dK/dV and a dQ streaming kernel back to back (no
+ * workspace, no global atomics: dqkv is bitwise reproducible). */
 int vlmo_attn_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse,
                   int lse_stride, const int32_t* seg, int num_seq, const int32_t* keymask,
                   void* dqkv, float* qv_colsum, int heads, int d, int max_len, float scale,

@@ -1,0 +1,151 @@
+"""The backbone and the pretraining module at 384 and 480 px (577 / 901 image tokens; 593 - 941 in the fused layers):
+reference fixtures (tests/golden/backbone_mini_{384,480}.npz, made by tools/gen_hires_golden.py through
+oracle.gen_golden.run_backbone_case), the live CPU oracle at VLMo-Base width, dropout-on schedule equivalences, and a
+VlmoModule loaded from a 224 px checkpoint through interpolate_pos_embedding.  Tolerances are those of
+tests/test_backbone_gpu.py."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import synth
+from oracle.gen_golden import grad_probe, out_weights
+from tests.test_backbone_gpu import _vl_step, build, modes
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+LOSSES = ['mlm', 'mim', 'itc', 'itm']
+
+
+@pytest.mark.parametrize('name,over', [('backbone_mini_384', dict(img_size=384)),
+                                       ('backbone_mini_480', dict(img_size=480, max_text_len=40))])
+def test_hires_forward_backward_matches_reference(golden_dir, name, over):
+    g = np.load(os.path.join(golden_dir, name + '.npz'))
+    B = int(g['meta.B'])
+    model, mc = build('mini', over)
+    model.eval()
+    batch = synth.synth_batch(mc, B, seed=1234)
+    for mode, kw in modes(mc, batch, B).items():
+        model.zero_grad(set_to_none=True)
+        x, m = model.forward_features(**kw)
+        got = x.detach().float().cpu()[:, ::17]          # the fixtures keep every 17th token row (CLS included)
+        ref = torch.from_numpy(g[f'{mode}.out_rows'])
+        err = (got - ref).abs()
+        assert (err <= 2e-2 + 2e-2 * ref.abs()).all(), f'{name}/{mode}: max err {err.max().item():.4f}'
+        assert err.mean().item() <= 4e-3, f'{name}/{mode}: mean err {err.mean().item():.5f}'
+        np.testing.assert_array_equal(m.cpu().numpy(), g[f'{mode}.mask'])
+        pooled = model.pooler(x.detach()).detach().float().cpu().numpy()
+        np.testing.assert_allclose(pooled, g[f'{mode}.pooled'], atol=2e-2, rtol=2e-2)
+        R = out_weights(mode, x.shape).to(DEV)
+        (x * R).sum().backward()
+        for k, p in model.named_parameters():
+            key = f'{mode}.grad_norm.{k}'
+            if key not in g:
+                assert p.grad is None or float(p.grad.abs().max()) == 0.0, f'{k}: grad where reference has none'
+                continue
+            gn = float(g[key])
+            assert p.grad is not None, f'{k}: missing grad'
+            gr = p.grad.detach().float().cpu()
+            if f'{mode}.grad.{k}' in g:
+                rel = (gr - torch.from_numpy(g[f'{mode}.grad.{k}'])).norm().item() / (gn + 1e-12)
+            else:
+                pr = (gr.double() * grad_probe(k, gr.shape).double()).sum().item()
+                rel = max(abs(gr.norm().item() - gn) / (gn + 1e-12),
+                          abs(pr - float(g[f'{mode}.grad_probe.{k}'])) / (gn + 1e-12))
+            assert rel <= 5e-2, f'{name}/{mode}: grad of {k} off by {rel:.3f} of its norm'
+
+
+def test_base_width_480px_vs_oracle():
+    """VLMo-Base width (768, 12 heads), two layers with the fusion layer at 1, 480 px (901 image tokens, 965 fused with
+    64 text tokens), batch 1: forward and every parameter gradient against the fp32 CPU oracle, as
+    test_edge_shapes_and_fusion_layer_override_vs_oracle does at 224 px."""
+    from oracle import vlmo_oracle
+    model, mc = build('base', dict(depth=2, fusion_layer=1, img_size=480))
+    model.eval()
+    B, T = 1, mc.max_text_len
+    g = torch.Generator().manual_seed(480)
+    img = torch.randn(B, 3, mc.img_size, mc.img_size, generator=g)
+    ids = torch.randint(1000, mc.vocab_size, (B, T), generator=g)
+    ids[:, 0] = 101
+    tmask = torch.ones(B, T, dtype=torch.int64)
+    tmask[:, T - 7:] = 0
+    ids[:, T - 7:] = 0
+    im = torch.ones(B, synth.num_img_tokens(mc), dtype=torch.int64)
+    x, m = model.forward_features(img=img.to(DEV), txt=ids.to(DEV), img_attn_masks=im.to(DEV), txt_attn_masks=tmask.to(DEV))
+    R = torch.randn(x.shape, generator=g)
+    (x * R.to(DEV)).sum().backward()
+    sd = {k: v.detach().cpu().clone().requires_grad_(v.is_floating_point()) for k, v in model.state_dict().items()}
+    ref, mref = vlmo_oracle.forward_features(sd, mc, img=img, txt=ids, img_attn_masks=im, txt_attn_masks=tmask)
+    (ref * R).sum().backward()
+    assert x.shape == ref.shape == (B, T + 901, 768)
+    assert torch.equal(m.cpu(), mref)
+    assert (x.detach().cpu() - ref.detach()).abs().max().item() <= 3e-2
+    worst = (0.0, '')
+    for k, p in model.named_parameters():
+        gr = sd[k].grad
+        if gr is None or gr.abs().max() == 0:
+            assert p.grad is None or p.grad.abs().max().item() <= 1e-6, k
+            continue
+        assert p.grad is not None, k
+        rel = (p.grad.detach().cpu() - gr).norm().item() / (gr.norm().item() + 1e-12)
+        worst = max(worst, (rel, k))
+    assert worst[0] <= 6e-2, worst
+
+
+def test_384px_dropout_paths_and_schedules_agree():
+    """Training mode at 384 px with attention dropout, dropout and drop-path on: the native stack path equals the
+    per-block path (outputs bit-identical), the one-stream schedule equals the side-stream schedule, and the split
+    backward attention switch changes nothing (the backward regenerates the forward's mask)."""
+    from exploremultimodal_amd import engine
+    model, mc = build('mini', dict(img_size=384), drop=0.1, drop_path=0.1)
+    model.train()
+    B = 2
+    batch = synth.synth_batch(mc, B, seed=77)
+    kw = modes(mc, batch, B)['vl']
+    R = torch.randn(B, mc.max_text_len + synth.num_img_tokens(mc), mc.embed_dim, device=DEV)
+    old = engine.USE_STACK, engine.OVERLAP_WGRAD, engine.SPLIT_BWD_ATTENTION
+    runs = {}
+    try:
+        for name, stack, overlap, split in (('stack', True, False, True), ('block', False, False, True),
+                                            ('side', True, True, True), ('nosplit', True, False, False)):
+            engine.USE_STACK, engine.OVERLAP_WGRAD, engine.SPLIT_BWD_ATTENTION = stack, overlap, split
+            runs[name] = _vl_step(model, kw, R, 3)
+    finally:
+        engine.USE_STACK, engine.OVERLAP_WGRAD, engine.SPLIT_BWD_ATTENTION = old
+    xs, gs = runs['stack']
+    assert all(torch.isfinite(v).all() for v in gs.values())
+    for name, (x, gr) in runs.items():
+        assert torch.equal(xs, x), name
+        assert set(gr) == set(gs), name
+        for n in gs:
+            frac = 4e-3 if (name == 'block' and n.endswith(('fc1.bias', 'q_bias', 'v_bias'))) else 1e-3
+            tol = frac * gs[n].abs().max().item() + 1e-9
+            assert (gr[n] - gs[n]).abs().max().item() <= tol, (name, n, (gr[n] - gs[n]).abs().max().item(), tol)
+
+
+def test_module_at_384px_from_a_224px_checkpoint_trains():
+    """A VlmoModule (mini dims, img_size 384, losses mlm / itc / itm / mim) loaded from a 224 px state dict through
+    load_from_ckpt -> interpolate_pos_embedding runs a training step with dropout on: finite losses and gradients."""
+    from exploremultimodal_amd.build import build_model
+    cfg224 = synth.make_config('mini', loss_names=LOSSES, img_size=224)
+    sd = {'transformer.' + k: v for k, v in synth.synth_backbone_state_dict(cfg224.model, 0).items()}
+    sd.update(synth.synth_head_state_dict(cfg224.model, 0, LOSSES))
+    assert sd['transformer.pos_embed'].shape[1] == 197
+    cfg = synth.make_config('mini', loss_names=LOSSES, img_size=384, drop_rate=0.1, attn_drop_rate=0.1)
+    model = build_model(cfg)
+    matching, is_beit = model.load_from_ckpt(sd)
+    assert not is_beit and not matching.unexpected_keys
+    assert model.transformer.pos_embed.shape[1] == 577
+    model.d_vae.encoder.load_state_dict(synth.synth_dvae_state_dict(0, n_hid=256, vocab_size=cfg.model.img_vocab_size))
+    model = model.to(DEV).train()
+    batch = {k: v.to(DEV) for k, v in synth.synth_batch(cfg.model, 4, seed=9).items()}
+    ret = model(batch)
+    losses = {k: v for k, v in ret.items() if 'task_loss' in k}
+    assert set(losses) == {f'{n}_task_loss' for n in LOSSES}, sorted(losses)
+    total = sum(losses.values())
+    assert torch.isfinite(total), {k: float(v) for k, v in losses.items()}
+    total.backward()
+    grads = [p.grad for p in model.parameters() if p.grad is not None]
+    assert grads and all(torch.isfinite(gr).all() for gr in grads)
+    assert model.transformer.pos_embed.grad is not None and model.transformer.pos_embed.grad.abs().max() > 0
