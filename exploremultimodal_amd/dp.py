@@ -162,6 +162,7 @@ class GradReducer:
             with torch.cuda.device(self.device):
                 self.native = hip.comm_init(uid[0], self.rank, self.world)
         self._armed = False
+        self._foreign = {}
         self.sinks = {}
         self.arenas = {}
         self._sink_params = set()
@@ -460,15 +461,33 @@ class GradReducer:
         # train/pretrain/multimodal.py:281-284, an objective that returned python 0.) never runs its backward.
         # The graph says which engine nodes WILL run: count those instead, so that a bucket is reduced after its
         # last real contribution and never left holding local, un-averaged gradients.
-        counts = {}
+        counts, key_of, engine_nodes = {}, {}, set()
         for fn in seen:
             groups = getattr(fn, 'sink_groups', None)
             if groups is None or getattr(fn, 'sink', None) is not self:
                 continue
+            engine_nodes.add(fn)
             flat = groups if (groups and isinstance(groups[0], tuple)) else [g_ for blk in groups for g_ in blk]
             for g_ in flat:
                 k = self._key(g_)
                 counts[k] = counts.get(k, 0) + 1
+                for p in g_:
+                    key_of[id(p)] = k
+        # A sink parameter that ALSO receives a gradient from an op outside the engine (a weight regulariser, a weight
+        # reused by a head): its AccumulateGrad node adds that contribution into p.grad -- the bucket view the engine
+        # set -- in place, once every producer has run, i.e. possibly after the engine released the bucket.  Such a
+        # bucket waits for one more release per such parameter, issued by the parameter's post-accumulate-grad hook
+        # (self._hook), which runs after the add was enqueued on the current stream; the collective is ordered after it.
+        self._foreign = {}
+        for fn in seen:
+            if fn in engine_nodes:
+                continue
+            for nxt, _ in fn.next_functions:
+                v = getattr(nxt, 'variable', None) if nxt is not None else None
+                if isinstance(v, torch.Tensor) and v.requires_grad and id(v) in key_of:
+                    self._foreign[id(v)] = key_of[id(v)]
+        for k in self._foreign.values():
+            counts[k] += 1
         for k, sb in self.sinks.items():
             sb.expected = counts.get(k, 0)
         self._pending_expect = {k: c for k, c in counts.items() if k not in self.sinks}
@@ -633,6 +652,14 @@ class GradReducer:
 
     def _hook(self, p):
         if not self._armed:
+            return
+        k = self._foreign.get(id(p))
+        if k is not None:           # the foreign contribution of a sink parameter is in its bucket now (see prepare)
+            sb = self.sinks[k]
+            sb.expected -= 1
+            if sb.expected <= 0:
+                self._ready_event = None
+                self._launch_sink(sb)
             return
         b, _ = self._of[p]
         b.pending -= 1

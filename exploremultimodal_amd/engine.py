@@ -423,6 +423,12 @@ def _fill_grads(D, flats, d, hid, nexp):
     return [dg1, dg2, dn1w, dn1b, dqkv_w, dqkv_b[:d], dqkv_b[2 * d:], dproj_w, dproj_b, dn2w, dn2b] + dexp
 
 
+def _released(ctx_field):
+    if ctx_field is None:
+        raise RuntimeError('Trying to backward through an engine pass a second time: its saved activations were released '
+                           'by the first backward (retain_graph=True is not supported by engine.StackFn / BlockFn)')
+
+
 class BlockFn(torch.autograd.Function):
     """One VLMo Block (vlmo.py:187-197) = norm1 -> qkv -> attention -> proj(+gamma_1, residual) -> norm2 ->
     expert FFN(+gamma_2, residual), forward and backward each ONE native call (vlmo_block_fwd / vlmo_block_bwd).
@@ -462,6 +468,7 @@ class BlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx2):
         meta, D = ctx.meta, ctx.desc
+        _released(D)
         x, *params = ctx.saved_tensors
         nexp = len(meta.expert_ranges)
         d, hid = meta.d, meta.hidden
@@ -479,10 +486,8 @@ class BlockFn(torch.autograd.Function):
                     [sink.acquire(g_, exp_n, dev, akey, aroom, layout=expert_layout(g_, d, hid))
                      for g_ in ctx.sink_groups[1:]]
         else:                   # ONE zero-filled flat buffer (one memset) carved into all gradients of the block
-            reg = _task_flats()
-            if reg:             # fresh gradients for these groups: later StackFn nodes of this backward must not add into
-                for g_ in [params[:11]] + [params[11 + 4 * e: 15 + 4 * e] for e in range(nexp)]:      # an earlier node's buffer
-                    reg.pop(_group_key(g_), None)
+            # (fresh gradients: to inplace_passes() a BlockFn node is a foreign producer, so no StackFn node of this
+            # backward adds into a buffer of these groups)
             whole = torch.zeros(shared_n + nexp * exp_n, dtype=f32, device=dev)
             flats = [whole[:shared_n]] + [whole[shared_n + i * exp_n: shared_n + (i + 1) * exp_n] for i in range(nexp)]
 
@@ -581,19 +586,28 @@ INPLACE_ACCUM = _os.environ.get('VLMO_INPLACE_ACCUM', '1') != '0'      # kill sw
 # A four-objective step runs the block stack three to seven times; without a reducer every pass hands autograd a fresh
 # gradient per parameter and the engine's input buffers add them: 337 elementwise launches = 1.4 ms of a 61 ms step.
 #
-# (1) WITHIN one backward() / autograd.grad() call (always on): the first StackFn node of the graph task that reaches a
-#     parameter GROUP (a block's shared parameters, or one expert) returns views of a flat buffer and registers the
-#     buffer under the task's id; every later node of the same task accumulates INTO that buffer inside the
-#     weight-gradient kernels and returns None for the group.  The engine still holds the first node's tensors (in the
-#     AccumulateGrad input buffer, or as the captured result of autograd.grad), so what it finally accumulates or
-#     returns is the sum: .grad is never touched by us, which makes this correct under autograd.grad(...) and
-#     backward(inputs=[...]) too.  Every engine node of a task must cooperate: a BlockFn node that returns fresh
-#     gradients for a group drops the group's entry (the input buffer would add out of place and orphan our buffer).
+# (1) WITHIN one backward() / autograd.grad() call, OPT-IN per call: `with engine.inplace_passes(loss): loss.backward()`.
+#     The first StackFn node of the graph task that reaches a parameter GROUP (a block's shared parameters, or one
+#     expert) returns views of a flat buffer and registers the buffer; every later node of the same task accumulates
+#     INTO that buffer inside the weight-gradient kernels and returns None for the group.  That is only right while
+#     autograd's input buffer for each parameter of the group still IS the first node's view when the later nodes have
+#     run, i.e. while StackFn nodes are the parameter's only gradient producers: any other contribution (a weight
+#     regulariser, a weight reused outside the engine, a BlockFn pass) makes the input buffer add out of place -- the
+#     view shares its storage with the flat buffer, so it cannot add in place -- and every later node would add into an
+#     orphaned buffer, silently losing its gradient.  Whether that can happen is a property of the graph, so
+#     inplace_passes() walks it from the roots before the backward (sole_producer_groups) and permits the mechanism only
+#     for groups every trainable parameter of which is fed by StackFn nodes alone, and only to the nodes it walked,
+#     during the first graph task that runs inside it.  Outside inplace_passes(), every pass returns fresh gradients and
+#     autograd sums them.  Within those bounds .grad is never touched by us, which makes it correct under
+#     autograd.grad(...) and backward(inputs=[...]) too.  Tensor hooks on a parameter see the sum: they run on the input
+#     buffer when its AccumulateGrad node executes, after every producer.
 # (2) ACROSS backward() calls (gradient-accumulation micro-steps, zero_grad(set_to_none=False)): a pass accumulates
-#     straight into the views the parameters already hold as .grad.  That is only right in an ordinary accumulating
-#     backward(), so it is OPT-IN: `with engine.accumulate_into_grad():` around loss.backward() -- the package's
-#     NativeScalerWithGradNormCount (the reference loop's backward, utils.py:343-364) and bench.py do that.
-_TASK_FLATS = {'task': None, 'flats': {}}
+#     straight into the views the parameters already hold as .grad.  AccumulateGrad adds any other contribution into
+#     that .grad in place, so foreign producers are harmless here, but it is only right in an ordinary accumulating
+#     backward(), so it is OPT-IN as well: `with engine.accumulate_into_grad():` around loss.backward().  The package's
+#     NativeScalerWithGradNormCount (the reference loop's backward, utils.py:343-364) opts into both; bench.py into
+#     neither.
+_TASK_FLATS = {'task': None, 'flats': {}, 'nodes': None, 'groups': frozenset()}
 _INTO_GRAD = [False]
 
 
@@ -612,12 +626,89 @@ class accumulate_into_grad:
         _INTO_GRAD[0] = self.prev
 
 
-def _task_flats():
-    """{group key: flat gradient buffer} of the running graph task (emptied when another task starts)."""
+def _walk(roots):
+    """Every autograd node reachable from `roots` (tensors or nodes), and {id(parameter): (parameter, [the nodes that
+    hand its AccumulateGrad node a gradient, one entry per edge])}."""
+    stack = [r.grad_fn if isinstance(r, torch.Tensor) else r for r in roots]
+    seen, feeds = set(), {}
+    while stack:
+        fn = stack.pop()
+        if fn is None or fn in seen:
+            continue
+        seen.add(fn)
+        for nxt, _ in fn.next_functions:
+            if nxt is None:
+                continue
+            v = getattr(nxt, 'variable', None)
+            if isinstance(v, torch.Tensor):
+                feeds.setdefault(id(v), (v, []))[1].append(fn)
+            stack.append(nxt)
+    return seen, feeds
+
+
+def sole_producer_groups(roots):
+    """(engine nodes, {group key}): the StackFn nodes reachable from `roots`, and the parameter groups of theirs whose
+    every trainable parameter receives its gradient from StackFn nodes ONLY and belongs to one group only -- the groups
+    for which mechanism (1) is sound in a backward from exactly these roots.  An engine node is any node carrying
+    `grad_groups` ([(group key, parameters)], set by StackFn.forward); BlockFn nodes and every other op count as
+    foreign producers."""
+    seen, feeds = _walk(roots)
+    nodes = [fn for fn in seen if getattr(fn, 'grad_groups', None) is not None]
+    node_set = set(nodes)
+    keys_of = {}                                     # id(parameter) -> group keys it belongs to
+    for fn in nodes:
+        for key, gp in fn.grad_groups:
+            for p_ in gp:
+                keys_of.setdefault(id(p_), set()).add(key)
+    foreign = {pid for pid, (_, prod) in feeds.items() if any(fn not in node_set for fn in prod)}
+    foreign |= {pid for pid, ks in keys_of.items() if len(ks) > 1}
+    ok = set()
+    bad = set()
+    for fn in nodes:
+        for key, gp in fn.grad_groups:
+            if any(p_.requires_grad and id(p_) in foreign for p_ in gp):
+                bad.add(key)
+            else:
+                ok.add(key)
+    return node_set, frozenset(ok - bad)
+
+
+class inplace_passes:
+    """Context manager around ONE backward() / autograd.grad() from `roots` (the loss): lets the StackFn passes of that
+    backward accumulate into one gradient buffer per parameter group (mechanism (1) above) wherever the graph shows
+    that no other op produces a gradient for the group.  enabled=False (or INPLACE_ACCUM off): a no-op."""
+
+    def __init__(self, *roots, enabled=True):
+        self.roots = roots
+        self.enabled = bool(enabled) and INPLACE_ACCUM
+
+    def __enter__(self):
+        self.prev = dict(_TASK_FLATS)       # (nested use restores the outer permit on exit)
+        if self.enabled:
+            nodes, groups = sole_producer_groups(self.roots)
+            _TASK_FLATS.update(task=None, flats={}, nodes=nodes, groups=groups)
+        else:
+            _TASK_FLATS.update(nodes=None, groups=frozenset())
+        return self
+
+    def __exit__(self, *a):
+        # the permit ends here, and the registry lets go of this backward's gradient buffers
+        _TASK_FLATS.update(self.prev)
+
+
+def _task_flats(node):
+    """{group key: flat gradient buffer} of the running graph task, when an inplace_passes() walk permitted `node`;
+    None otherwise.  The permit binds to the first graph task an engine node of it runs in."""
+    if _TASK_FLATS['nodes'] is None or node not in _TASK_FLATS['nodes']:
+        return None
     tid = torch._C._current_graph_task_id()
-    if _TASK_FLATS['task'] != tid:
-        _TASK_FLATS['task'], _TASK_FLATS['flats'] = tid, {}
-    return _TASK_FLATS['flats'] if tid >= 0 else None
+    if tid < 0:
+        return None
+    if _TASK_FLATS['task'] is None:
+        _TASK_FLATS['task'] = tid
+    elif _TASK_FLATS['task'] != tid:
+        return None
+    return _TASK_FLATS['flats']
 
 
 def _group_key(gparams):
@@ -713,7 +804,14 @@ class StackFn(torch.autograd.Function):
             ctx.metas, ctx.descs, ctx.keep, ctx.spans = metas, descs, keep, spans
             ctx.save_for_backward(x, *params)
             ctx.sink = GRAD_SINK
-            if ctx.sink is not None:
+            if ctx.sink is None:
+                # the parameter groups this node produces gradients for, read by inplace_passes()' graph walk
+                ctx.grad_groups = []
+                for (o, n_) in spans:
+                    bp = params[o:o + n_]
+                    ctx.grad_groups += [(_group_key(g_), tuple(g_))
+                                        for g_ in [bp[:11]] + [bp[11 + 4 * e: 15 + 4 * e] for e in range((n_ - 11) // 4)]]
+            else:
                 ctx.sink_groups = []
                 for (o, n_) in spans:
                     bp = params[o:o + n_]
@@ -726,6 +824,7 @@ class StackFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dxo):
         metas, descs, spans = ctx.metas, ctx.descs, ctx.spans
+        _released(descs)
         x, *params = ctx.saved_tensors
         nb = len(metas)
         m0 = metas[0]
@@ -754,7 +853,8 @@ class StackFn(torch.autograd.Function):
             # no memset of the weight-gradient matrices: the deferred launches WRITE them (wgrad_store); only the vector
             # gradients (accumulated with atomics by the column folds) are zeroed, in one multi-tensor fill
             whole = None        # allocated when the first group needs fresh gradient storage
-            reg = _task_flats()
+            reg = _task_flats(ctx) if INPLACE_ACCUM else None
+            permit = _TASK_FLATS['groups']
         grads_all = [None] * len(params)
         goff = 0
         store_ok, acquired = WGRAD_STORE, []      # (flat, fresh, is_expert) of every gradient bucket of the pass
@@ -800,7 +900,8 @@ class StackFn(torch.autograd.Function):
                             whole = torch.empty(tot, dtype=f32, device=dev) if WGRAD_STORE else torch.zeros(tot, dtype=f32, device=dev)
                         flats[gi] = whole[goff:goff + gn_]
                         lo = 0 if gi == 0 else 11 + 4 * (gi - 1)
-                        if reg is not None and INPLACE_ACCUM and all(w or not p_.requires_grad for p_, w in zip(gp_, ni[lo:lo + len(gp_)])):
+                        if (reg is not None and _group_key(gp_) in permit
+                                and all(w or not p_.requires_grad for p_, w in zip(gp_, ni[lo:lo + len(gp_)]))):
                             reg[_group_key(gp_)] = flats[gi]
                     goff += gn_
                     acquired.append((flats[gi], kept[gi] == 0, gi > 0))

@@ -246,8 +246,11 @@ class NativeScalerWithGradNormCount:
         if self.reducer is not None:
             self.reducer.prepare(loss)
         from . import engine
-        # an ordinary accumulating backward(): a micro-step may add straight into the gradient views the parameters hold
-        with engine.accumulate_into_grad(not create_graph):
+        # an ordinary accumulating backward(): a micro-step may add straight into the gradient views the parameters hold,
+        # and the passes of this backward into one buffer per parameter group where the graph walk of inplace_passes()
+        # shows no other gradient producer (under a reducer the gradients go to its buckets instead: no walk needed)
+        with engine.accumulate_into_grad(not create_graph), \
+                engine.inplace_passes(loss, enabled=not create_graph and engine.GRAD_SINK is None):
             loss.backward(create_graph=create_graph)
         if self.reducer is not None:
             self.reducer.finish(accumulate=not update_grad)

@@ -489,13 +489,14 @@ def _three_pass_loss(model, kw):
     return xv.float().square().mean() + 2.0 * xl.float().square().mean() + 3.0 * xvl.float().square().mean()
 
 
-def test_passes_of_one_backward_accumulate_in_place():
+def test_passes_of_one_walked_backward_accumulate_in_place():
     """V -> L -> VL passes of ONE step (the merged four-objective step, objectives.py:40-314) summed into one loss and
-    ONE backward(): the first StackFn node that reaches a parameter group returns its gradient buffer, the later nodes
-    of the same graph task add into it inside the weight-gradient kernels and return nothing (engine._task_flats), so
-    autograd has nothing to add.  Gradients equal those of the unfused path (VLMO_INPLACE_ACCUM off: one fresh tensor
-    per pass, summed by autograd) to summation-order rounding -- under backward() AND under autograd.grad(), which
-    must not touch .grad at all."""
+    ONE backward() inside engine.inplace_passes(loss): the graph walk finds no producer but StackFn nodes for any block
+    parameter group, so the first StackFn node that reaches a group returns its gradient buffer, the later nodes of the
+    same graph task add into it inside the weight-gradient kernels and return nothing (engine._task_flats), and autograd
+    has nothing to add.  Gradients equal those of the unfused path (VLMO_INPLACE_ACCUM off: one fresh tensor per pass,
+    summed by autograd) to summation-order rounding -- under backward() AND under autograd.grad(), which must not touch
+    .grad at all -- and so do those of a plain backward() / autograd.grad() outside the walk (fresh gradients)."""
     from exploremultimodal_amd import engine
     model, mc = build('mini')
     model.eval()
@@ -504,21 +505,27 @@ def test_passes_of_one_backward_accumulate_in_place():
     names = [n for n, p in model.named_parameters() if 'blocks.' in n]
     blk = [p for n, p in model.named_parameters() if 'blocks.' in n]
 
-    def grads(inplace, use_grad_api):
+    def grads(inplace, use_grad_api, walked=True):
         old = engine.INPLACE_ACCUM
         engine.INPLACE_ACCUM = inplace
         try:
             for p in model.parameters():
                 p.grad = None
             loss = _three_pass_loss(model, kw)
-            if use_grad_api:
-                used = [p for p in blk]
-                out = torch.autograd.grad(loss, used, allow_unused=True)
-                assert all(p.grad is None for p in model.parameters())         # autograd.grad leaves .grad alone
-                res = {n: g.clone() for n, g in zip(names, out) if g is not None}
-            else:
-                loss.backward()
-                res = {n: p.grad.clone() for n, p in zip(names, blk) if p.grad is not None}
+            with engine.inplace_passes(loss, enabled=walked):
+                if use_grad_api:
+                    used = [p for p in blk]
+                    out = torch.autograd.grad(loss, used, allow_unused=True)
+                    assert all(p.grad is None for p in model.parameters())         # autograd.grad leaves .grad alone
+                    res = {n: g.clone() for n, g in zip(names, out) if g is not None}
+                else:
+                    loss.backward()
+                    res = {n: p.grad.clone() for n, p in zip(names, blk) if p.grad is not None}
+                if inplace and walked:
+                    # the in-place path really ran: every group the walk permitted (here: all of them) got ONE buffer,
+                    # which the second and third pass found
+                    assert engine._TASK_FLATS['groups'], 'the walk permitted no group of an engine-only loss'
+                    assert set(engine._TASK_FLATS['flats']) == set(engine._TASK_FLATS['groups'])
             torch.cuda.synchronize()
             return res
         finally:
@@ -526,13 +533,12 @@ def test_passes_of_one_backward_accumulate_in_place():
 
     ref = grads(False, False)
     for api in (False, True):
-        got = grads(True, api)
-        assert set(got) == set(ref)
-        for n in ref:
-            tol = 2e-3 * ref[n].abs().max().item() + 1e-9
-            assert (got[n] - ref[n]).abs().max().item() <= tol, (api, n, (got[n] - ref[n]).abs().max().item(), tol)
-    # the in-place path really ran: the second and third pass found the first pass's buffers
-    assert engine._TASK_FLATS['flats'], 'no gradient buffer was registered for the graph task'
+        for walked in (True, False):
+            got = grads(True, api, walked)
+            assert set(got) == set(ref)
+            for n in ref:
+                tol = 2e-3 * ref[n].abs().max().item() + 1e-9
+                assert (got[n] - ref[n]).abs().max().item() <= tol, (api, walked, n, (got[n] - ref[n]).abs().max().item(), tol)
 
 
 def test_backward_after_a_parameter_update_is_refused_like_stock_autograd():

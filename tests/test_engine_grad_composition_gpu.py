@@ -1,0 +1,364 @@
+"""Block-parameter gradients of the HIP engine (engine.StackFn / BlockFn and the reducer sink of dp.GradReducer) under
+losses that are not built from the backbone alone: weight regularisers, block weights reused outside the engine, frozen
+groups, gradients over a subset of a group, tensor hooks, accumulation across backward() calls.  These decide which
+buffer a weight-gradient launch writes or adds into and what autograd is handed.
+
+Reference A (tight): the same loss with engine.INPLACE_ACCUM off -- every pass returns fresh gradients and autograd
+sums them -- at the suite's bound for summation-order differences, 2e-3 * max|ref|.  Regulariser strengths are chosen
+per weight so that |grad R| ~ |grad L|: losing the regulariser, or one backbone pass in three, is off by ~30 % of
+max|ref|, two orders above the bound.  Reference B (independent): the fp32 CPU oracle (oracle.vlmo_oracle) on the same
+weights.  All cases in eval mode (no dropout: the passes are deterministic)."""
+import os
+from contextlib import contextmanager, nullcontext
+
+import pytest
+import torch
+
+from oracle import synth
+from tests.test_backbone_gpu import _three_pass_loss, build, modes
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+TOL = 2e-3
+# a shared-group weight, an expert weight fed by two passes (V and VL), a layer-scale vector and a norm weight
+REG_NAMES = ['blocks.0.attn.qkv.weight', 'blocks.0.mlp.v.fc1.weight', 'blocks.1.gamma_1', 'blocks.0.norm1.weight']
+APIS = ('backward', 'scaler', 'grad')
+
+
+def _setup(preset='mini', B=3, seed=6):
+    model, mc = build(preset)
+    model.eval()
+    batch = synth.synth_batch(mc, B, seed=seed)
+    return model, mc, batch, modes(mc, batch, B)
+
+
+def _block_params(model):
+    return [(n, p) for n, p in model.named_parameters() if n.startswith('blocks.') and p.requires_grad]
+
+
+@contextmanager
+def _knobs(stack, inplace=True):
+    from exploremultimodal_amd import engine
+    old = engine.USE_STACK, engine.INPLACE_ACCUM
+    engine.USE_STACK, engine.INPLACE_ACCUM = stack, inplace
+    try:
+        yield
+    finally:
+        engine.USE_STACK, engine.INPLACE_ACCUM = old
+
+
+def _grads(model, loss_fn, api, params):
+    """Block-parameter gradients of loss_fn() through one entry point: 'backward' (plain loss.backward()), 'scaler'
+    (the package's NativeScalerWithGradNormCount, the reference loop's backward), 'grad' (torch.autograd.grad, which
+    must leave .grad alone) or 'grad_walked' (autograd.grad inside engine.inplace_passes)."""
+    from exploremultimodal_amd import engine
+    from exploremultimodal_amd.optim import NativeScalerWithGradNormCount
+    for p in model.parameters():
+        p.grad = None
+    loss = loss_fn()
+    if api == 'backward':
+        loss.backward()
+    elif api == 'scaler':
+        NativeScalerWithGradNormCount()(loss, None, update_grad=False)
+    else:
+        with engine.inplace_passes(loss) if api == 'grad_walked' else nullcontext():
+            out = torch.autograd.grad(loss, [p for _, p in params], allow_unused=True)
+        assert all(p.grad is None for p in model.parameters()), 'autograd.grad touched .grad'
+        torch.cuda.synchronize()
+        return {n: g.clone() for (n, _), g in zip(params, out) if g is not None}
+    torch.cuda.synchronize()
+    return {n: p.grad.clone() for n, p in params if p.grad is not None}
+
+
+def _assert_close(got, ref, what, tol=TOL):
+    assert set(got) == set(ref), (what, sorted(set(got) ^ set(ref)))
+    for n in ref:
+        err = (got[n] - ref[n]).abs().max().item()
+        bound = tol * ref[n].abs().max().item() + 1e-9
+        assert err <= bound, f'{what}: gradient of {n} off by {err:.4g} (bound {bound:.3g}, max|ref| ' \
+                             f'{ref[n].abs().max().item():.4g})'
+
+
+def _reg_coefs(model, gL, names=REG_NAMES):
+    """c per weight with |grad c*sum(w^2)| = |2 c w| = |grad_L w|."""
+    named = dict(model.named_parameters())
+    return [(n, named[n], gL[n].norm().item() / (2.0 * named[n].detach().norm().item())) for n in names]
+
+
+def _reg(coefs):
+    return sum(c * p.float().square().sum() for _, p, c in coefs)
+
+
+@pytest.mark.parametrize('stack', [True, False])
+@pytest.mark.parametrize('preset', ['mini', 'small'])
+def test_weight_regulariser_over_three_passes(preset, stack):
+    """The ADVICE case: V -> L -> VL passes of one step (_three_pass_loss, the merged four-objective step) plus an L2
+    regulariser c * sum(w^2) on a shared-group weight (qkv), an expert weight two passes feed, gamma_1 and norm1.weight
+    -- L + R and R + L (autograd runs the nodes in a different order), under backward(), the package's loss scaler and
+    autograd.grad.  Reference A: INPLACE_ACCUM off, and the decomposition grad(L + R) = grad(L) + 2 c w (the fp32
+    torch gradient of R), both at 2e-3 * max|ref|.  Reference B (mini): the fp32 CPU oracle with the same R, per-parameter
+    relative norm <= 2e-2 for the regularised weights (R carries half their gradient) and <= 5e-2 (the golden tests'
+    bound for bf16 GEMM operands) for every other block parameter."""
+    model, mc, batch, kw = _setup(preset)
+    params = _block_params(model)
+    with _knobs(stack, False):
+        gL = _grads(model, lambda: _three_pass_loss(model, kw), 'backward', params)
+    coefs = _reg_coefs(model, gL)
+    losses = {'L+R': lambda: _three_pass_loss(model, kw) + _reg(coefs),
+              'R+L': lambda: _reg(coefs) + _three_pass_loss(model, kw)}
+    got_scaler = None
+    for order, fn in losses.items():
+        with _knobs(stack, False):
+            ref = _grads(model, fn, 'backward', params)
+        for api in APIS:
+            with _knobs(stack, True):
+                got = _grads(model, fn, api, params)
+            _assert_close(got, ref, f'{preset}/stack={stack}/{order}/{api}')
+            for n, p, c in coefs:        # decomposition: the engine's L-gradient plus the exact R-gradient
+                _assert_close({n: got[n]}, {n: gL[n] + 2.0 * c * p.detach()}, f'{order}/{api}: grad L + 2cw')
+            if api == 'scaler' and order == 'L+R':
+                got_scaler = got
+    if preset != 'mini':
+        return
+    from oracle import vlmo_oracle
+    B = batch['image'].shape[0]
+    im = torch.ones(B, synth.num_img_tokens(mc), dtype=torch.int64)
+    sd = {k: v.detach().cpu().clone().requires_grad_(v.is_floating_point()) for k, v in model.state_dict().items()}
+    xv, _ = vlmo_oracle.forward_features(sd, mc, img=batch['image'], img_attn_masks=im)
+    xl, _ = vlmo_oracle.forward_features(sd, mc, txt=batch['text_ids'], txt_attn_masks=batch['text_mask'])
+    xvl, _ = vlmo_oracle.forward_features(sd, mc, img=batch['image'], txt=batch['text_ids'], img_attn_masks=im,
+                                          txt_attn_masks=batch['text_mask'])
+    loss = xv.square().mean() + 2.0 * xl.square().mean() + 3.0 * xvl.square().mean() + \
+        sum(c * sd[n].square().sum() for n, _, c in coefs)
+    loss.backward()
+    regd = {n for n, _, _ in coefs}
+    worst = (0.0, '')
+    for n, _ in params:
+        gr = sd[n].grad
+        if gr is None or gr.abs().max() == 0:
+            assert n not in got_scaler or got_scaler[n].abs().max().item() <= 1e-6, n
+            continue
+        rel = (got_scaler[n].cpu() - gr).norm().item() / gr.norm().item()
+        worst = max(worst, (rel, n))
+        assert rel <= (2e-2 if n in regd else 5e-2), (n, rel)
+    print('worst block gradient vs fp32 oracle %.4f (%s)' % worst)
+
+
+@pytest.mark.parametrize('stack', [True, False])
+def test_block_weight_reused_outside_the_engine(stack):
+    """A distillation / auxiliary term that reuses block weights: the VL pass's features projected through block 0's
+    L-expert fc1 and block 1's qkv weight, squared and averaged, added to the three-pass loss in both orders.  The
+    term's weight is set so that its gradient on those weights matches the backbone loss's.  Reference A at 2e-3."""
+    model, mc, batch, kw = _setup()
+    params = _block_params(model)
+    W = [model.blocks[0].mlp['l'].fc1.weight, model.blocks[1].attn.qkv.weight]
+    wn = ['blocks.0.mlp.l.fc1.weight', 'blocks.1.attn.qkv.weight']
+
+    def passes():
+        xv, _ = model.forward_features(**kw['v'])
+        xl, _ = model.forward_features(**kw['l'])
+        xvl, _ = model.forward_features(**kw['vl'])
+        return xv.float().square().mean() + 2.0 * xl.float().square().mean() + 3.0 * xvl.float().square().mean(), xvl
+
+    with _knobs(stack, False):
+        gL = _grads(model, lambda: passes()[0], 'backward', params)
+        feat = passes()[1].detach().float()
+        scale = []
+        for n, w in zip(wn, W):
+            (ga,) = torch.autograd.grad((feat @ w.t()).square().mean(), w)
+            scale.append(gL[n].norm().item() / ga.norm().item())
+
+    def aux(xvl):
+        return sum(a * (xvl.float() @ w.t()).square().mean() for a, w in zip(scale, W))
+
+    def l_plus():
+        L, xvl = passes()
+        return L + aux(xvl)
+
+    def plus_l():
+        L, xvl = passes()
+        return aux(xvl) + L
+
+    for order, fn in (('L+aux', l_plus), ('aux+L', plus_l)):
+        with _knobs(stack, False):
+            ref = _grads(model, fn, 'backward', params)
+        for api in APIS:
+            with _knobs(stack, True):
+                got = _grads(model, fn, api, params)
+            _assert_close(got, ref, f'stack={stack}/{order}/{api}')
+
+
+@pytest.mark.parametrize('stack', [True, False])
+def test_frozen_groups_as_in_stage_two(stack):
+    """VLMo stage 2 (text-only pretraining of the L experts): attention, norms, layer-scales and the V and VL experts
+    frozen with requires_grad=False, only the L experts train.  Three-pass loss plus the regulariser on a trainable L
+    expert weight that two passes feed.  Frozen parameters keep .grad None; the trainable ones match reference A at
+    2e-3 and the decomposition grad L + 2cw."""
+    model, mc, batch, kw = _setup()
+    for n, p in model.named_parameters():
+        if n.startswith('blocks.') and '.mlp.l.' not in n:
+            p.requires_grad_(False)
+    frozen = [p for n, p in model.named_parameters() if n.startswith('blocks.') and not p.requires_grad]
+    params = _block_params(model)
+    assert params and frozen
+    with _knobs(stack, False):
+        gL = _grads(model, lambda: _three_pass_loss(model, kw), 'backward', params)
+    coefs = _reg_coefs(model, gL, ['blocks.0.mlp.l.fc1.weight', 'blocks.1.mlp.l.fc2.weight'])
+    for order, fn in (('L+R', lambda: _three_pass_loss(model, kw) + _reg(coefs)),
+                      ('R+L', lambda: _reg(coefs) + _three_pass_loss(model, kw))):
+        with _knobs(stack, False):
+            ref = _grads(model, fn, 'backward', params)
+        for api in APIS:
+            with _knobs(stack, True):
+                got = _grads(model, fn, api, params)
+            assert all(p.grad is None for p in frozen), 'a frozen parameter got a .grad'
+            _assert_close(got, ref, f'stack={stack}/{order}/{api}')
+            for n, p, c in coefs:
+                _assert_close({n: got[n]}, {n: gL[n] + 2.0 * c * p.detach()}, f'{order}/{api}: grad L + 2cw')
+
+
+@pytest.mark.parametrize('stack', [True, False])
+@pytest.mark.parametrize('with_reg', [False, True])
+def test_gradient_over_a_subset_that_splits_groups(stack, with_reg):
+    """backward(inputs=[...]) and autograd.grad over block 0's qkv weight and its L expert's fc2 only -- each one
+    parameter of a larger group -- for the three-pass loss, alone and with a regulariser on the qkv weight.  Plain,
+    and with the passes accumulating in place (engine.inplace_passes); every other parameter keeps .grad None.
+    Reference A: autograd.grad with INPLACE_ACCUM off, at 2e-3."""
+    from exploremultimodal_amd import engine
+    model, mc, batch, kw = _setup()
+    names = ['blocks.0.attn.qkv.weight', 'blocks.0.mlp.l.fc2.weight']
+    named = dict(model.named_parameters())
+    sub = [(n, named[n]) for n in names]
+    with _knobs(stack, False):
+        gL = _grads(model, lambda: _three_pass_loss(model, kw), 'grad', sub)
+    coefs = _reg_coefs(model, gL, names[:1]) if with_reg else []
+    fn = lambda: _three_pass_loss(model, kw) + (_reg(coefs) if coefs else 0.0)
+    with _knobs(stack, False):
+        ref = _grads(model, fn, 'grad', sub)
+    for api in ('grad', 'grad_walked', 'inputs', 'inputs_walked'):
+        with _knobs(stack, True):
+            if api.startswith('grad'):
+                got = _grads(model, fn, api, sub)
+            else:
+                for p in model.parameters():
+                    p.grad = None
+                loss = fn()
+                with engine.inplace_passes(loss) if api == 'inputs_walked' else nullcontext():
+                    loss.backward(inputs=[p for _, p in sub])
+                torch.cuda.synchronize()
+                assert all(p.grad is None for n, p in model.named_parameters() if n not in names)
+                got = {n: p.grad.clone() for n, p in sub}
+        _assert_close(got, ref, f'stack={stack}/reg={with_reg}/{api}')
+
+
+@pytest.mark.parametrize('stack', [True, False])
+def test_tensor_hook_sees_the_sum_of_the_passes(stack):
+    """p.register_hook(lambda g: 2 * g) on block 0's qkv weight and its V expert's fc1 (both fed by several passes):
+    the hook must see the full sum of the passes, so those gradients are 2x reference A and all others 1x, under
+    backward(), the loss scaler and autograd.grad with the passes accumulating in place.  2e-3 * max|ref|."""
+    model, mc, batch, kw = _setup()
+    params = _block_params(model)
+    named = dict(model.named_parameters())
+    hooked = ['blocks.0.attn.qkv.weight', 'blocks.0.mlp.v.fc1.weight']
+    fn = lambda: _three_pass_loss(model, kw)
+    with _knobs(stack, False):
+        ref = _grads(model, fn, 'backward', params)
+    want = {n: (2.0 * g if n in hooked else g) for n, g in ref.items()}
+    hs = [named[n].register_hook(lambda g: 2 * g) for n in hooked]
+    try:
+        for api in ('backward', 'scaler', 'grad_walked'):
+            with _knobs(stack, True):
+                got = _grads(model, fn, api, params)
+            _assert_close(got, want, f'stack={stack}/{api}')
+    finally:
+        for h in hs:
+            h.remove()
+
+
+@pytest.mark.parametrize('stack', [True, False])
+def test_accumulation_across_backward_calls_with_a_regulariser(stack):
+    """Gradient-accumulation micro-steps (multimodal.py:260,316-323) through the package's loss scaler, which adds
+    into the gradient views the parameters hold (engine.accumulate_into_grad), with the regulariser of the ADVICE case:
+    two backward() calls = 2x reference A; with zero_grad(set_to_none=False) between them = 1x.  2e-3 * max|ref|.
+    A second backward() through a graph kept with retain_graph=True is refused with a clear error (the engine releases
+    its saved activation slabs in the first backward) and leaves the block gradients of the first one as they were."""
+    from exploremultimodal_amd import engine
+    from exploremultimodal_amd.optim import NativeScalerWithGradNormCount
+    model, mc, batch, kw = _setup()
+    params = _block_params(model)
+    with _knobs(stack, False):
+        gL = _grads(model, lambda: _three_pass_loss(model, kw), 'backward', params)
+    coefs = _reg_coefs(model, gL)
+    fn = lambda: _three_pass_loss(model, kw) + _reg(coefs)
+    with _knobs(stack, False):
+        ref = _grads(model, fn, 'backward', params)
+    scaler = NativeScalerWithGradNormCount()
+    collect = lambda: {n: p.grad.clone() for n, p in params if p.grad is not None}
+    with _knobs(stack, True):
+        for zero_between, k in ((False, 2.0), (True, 1.0)):
+            model.zero_grad(set_to_none=True)
+            scaler(fn(), None, update_grad=False)
+            if zero_between:
+                model.zero_grad(set_to_none=False)
+            scaler(fn(), None, update_grad=False)
+            torch.cuda.synchronize()
+            _assert_close(collect(), {n: k * g for n, g in ref.items()}, f'stack={stack}/zero_between={zero_between}')
+        model.zero_grad(set_to_none=True)
+        loss = fn()
+        with engine.accumulate_into_grad(), engine.inplace_passes(loss):
+            loss.backward(retain_graph=True)
+            torch.cuda.synchronize()
+            first = collect()
+            with pytest.raises(RuntimeError, match='backward through an engine pass a second time'):
+                loss.backward()
+        torch.cuda.synchronize()
+        _assert_close(first, ref, f'stack={stack}/retain_graph')
+        assert all(torch.equal(p.grad, first[n]) for n, p in params if n in first)
+
+
+@pytest.mark.parametrize('stack', [True, False])
+@pytest.mark.parametrize('wire', ['bf16', 'fp32'])
+def test_reducer_sink_with_a_regulariser(stack, wire):
+    """Single-rank GradReducer on nccl (RCCL) with the engine's sink buckets: three-pass loss + the regulariser of the
+    ADVICE case, prepare() / backward() / finish().  The regulariser's gradient is added into p.grad -- a view of a sink
+    bucket -- by AccumulateGrad after the engine released the bucket; it must reach the bucket before its collective
+    (at world size W the average has to include it).  One rank cannot observe the average, so the test checks what
+    makes it right: values = reference A, and every block parameter's .grad after finish() IS its bucket view.  Bound:
+    2e-3 * max|ref| with an fp32 wire; a bf16 wire rounds every element once more (2^-9 relative): 4e-3."""
+    import torch.distributed as dist
+    from exploremultimodal_amd import engine
+    from exploremultimodal_amd.dp import GradReducer
+    model, mc, batch, kw = _setup()
+    params = _block_params(model)
+    with _knobs(stack, False):
+        gL = _grads(model, lambda: _three_pass_loss(model, kw), 'backward', params)
+        coefs = _reg_coefs(model, gL)
+        fn = lambda: _three_pass_loss(model, kw) + _reg(coefs)
+        ref = _grads(model, fn, 'backward', params)
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT='29563')
+    dist.init_process_group('nccl', rank=0, world_size=1, device_id=torch.device('cuda', 0))
+    red = None
+    try:
+        red = GradReducer(model, comm_dtype=torch.bfloat16 if wire == 'bf16' else torch.float32)
+        assert engine.GRAD_SINK is red
+        with _knobs(stack, True):
+            for p in model.parameters():
+                p.grad = None
+            loss = fn()
+            red.prepare(loss)
+            loss.backward()
+            red.finish()
+            torch.cuda.synchronize()
+        got = {n: p.grad.clone() for n, p in params if p.grad is not None}
+        _assert_close(got, ref, f'stack={stack}/wire={wire}', tol=4e-3 if wire == 'bf16' else TOL)
+        views = set()
+        for sb in red.sinks.values():
+            for p, off in sb.layout:
+                if p.requires_grad and p.grad is not None:
+                    assert p.grad.data_ptr() == sb.flat.data_ptr() + 4 * off, 'a block .grad is not its bucket view'
+                    views.add(id(p))
+        assert {id(p) for n, p in params if n in got} <= views, 'a block .grad outside the sink buckets'
+    finally:
+        if red is not None:
+            red.close()
+        dist.destroy_process_group()
