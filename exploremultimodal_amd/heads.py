@@ -6,7 +6,11 @@ running (max, sum exp, arg-max, label logit) per 64-column chunk, so the [rows, 
 a backward that recomputes (softmax - onehot) tile-wise into the bf16 operand of the input- and weight-gradient GEMMs
 (VLMO_EPI_CE / VLMO_EPI_CE_BWD, csrc/gemm.hip).  ``forward`` still returns the logits (reference contract:
 `mlm_logits` / `mim_logits` in the output dict); ``config.train.fused_ce`` selects the fused path in the objectives.
-The small heads (ITC projection + normalise, 2-way ITM, pooler) are a few MFLOP and stay torch ops."""
+The small heads (ITC projection + normalise, 2-way ITM, pooler) are a few MFLOP and stay torch ops.
+
+The VQA classifier (Linear(hs, 2hs) -> LayerNorm -> GELU -> Linear(2hs, 3129), vlmo_module.py:85-93) and its
+binary cross-entropy (objectives.py:317-353) run as ``VQAHeadFn``: the two Linears on the HIP GEMMs, the LayerNorm +
+GELU and the per-row loss / arg-max on the row kernels of csrc/vqa_head.hip."""
 import torch
 import torch.nn as nn
 
@@ -82,6 +86,123 @@ class LinearCrossEntropyFn(torch.autograd.Function):
         # be half precision (multimodal.py:276-279 runs the module inside autocast)
         xd, wd, bd = ctx.in_dtypes
         return dx.to(xd), dw[:V].to(wd), (db.to(bd) if db is not None else None), None, None, None
+
+
+def _pad64(n):
+    return (n + 63) // 64 * 64
+
+
+class _VQAShadows:
+    """bf16 copies of the VQA classifier's two weight matrices, zero-padded for the GEMMs (reduction dimensions to a
+    multiple of 64, the 3129 answers to 3136), each with its transpose, and the zero-padded fp32 output bias; rebuilt
+    when a parameter's version counter changes (once per optimizer step)."""
+
+    def __init__(self):
+        self.key, self.val = None, None
+
+    def get(self, w1, w2, b2):
+        key = tuple((t._version, t.data_ptr()) for t in (w1, w2, b2))
+        if self.key != key:
+            h2, hs = w1.shape
+            vs = w2.shape[0]
+            k0, k1, npad = _pad64(hs), _pad64(h2), _pad64(vs)
+            dev = w1.device
+            w1s = torch.zeros((h2, k0), dtype=torch.bfloat16, device=dev)
+            w1s[:, :hs] = w1.detach()
+            w1t = torch.zeros((hs, k1), dtype=torch.bfloat16, device=dev)
+            w1t[:, :h2] = w1.detach().t()
+            w2s = torch.zeros((npad, k1), dtype=torch.bfloat16, device=dev)
+            w2s[:vs, :h2] = w2.detach()
+            w2t = w2s.t().contiguous()
+            b2p = torch.zeros(npad, dtype=torch.float32, device=dev)
+            b2p[:vs] = b2.detach()
+            self.key, self.val = key, (w1s, w1t, w2s, w2t, b2p)
+        return self.val
+
+
+class VQAHeadFn(torch.autograd.Function):
+    """``vqa_classifier(x)`` and, when ``targets`` is given, ``BCE-with-logits(logits, targets) * vs`` with the per-row
+    arg-max and the target value at it (objectives.py:12-21, 346-351) -> (logits, loss, argmax, score_rows).
+
+    Forward: x -> bf16 [B, K0] -> GEMM (+b1, fp32 out) -> LayerNorm + GELU (bf16 [B, K1]) -> GEMM (+b2, fp32 [B, 3136])
+    -> per-row BCE sum / arg-max / score.  The loss is sum(row sums) / B (= the mean over B * vs elements times vs); no
+    value goes to the host.  Backward: (sigmoid(z) - y) * dloss / B (+ the gradient of the logits output, e.g. R-Drop's
+    KL term) as the bf16 operand of dh = dz W2, dW2 = dz^T h, db2 = column sums; the LayerNorm + GELU backward writes
+    the bf16 operand of dx = du W1, dW1 = du^T x and folds d gamma, d beta and db1 in the same pass.  Pad columns are
+    zero in every operand, so they reach neither the loss, the arg-max, the logits nor a gradient.  Every reduction runs
+    in a fixed order: two runs give the same bits.  ``out_dtype``: dtype of the returned logits (the autocast dtype
+    under autocast, as the reference's nn.Linear returns); the loss is fp32 and every gradient has its input's dtype."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, ln_w, ln_b, w2, b2, targets, eps, out_dtype, shadows):
+        ctx.set_materialize_grads(False)
+        B, hs = x.shape
+        h2, vs = w1.shape[0], w2.shape[0]
+        w1s, w1t, w2s, w2t, b2p = shadows.get(w1, w2, b2)
+        k0, k1, npad = w1s.shape[1], w2s.shape[1], w2s.shape[0]
+        dev = x.device
+        xb = torch.zeros((B, k0), dtype=torch.bfloat16, device=dev) if k0 != hs else torch.empty((B, k0), dtype=torch.bfloat16, device=dev)
+        xb[:, :hs] = x.detach()
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        b1f, gf, bf = f32(b1), f32(ln_w), f32(ln_b)
+        u = torch.empty((B, h2), dtype=torch.float32, device=dev)
+        hip.gemm_nt(hip.EPI_F32, xb, w1s, B, h2, k0, u, bias=b1f)
+        h = torch.empty((B, k1), dtype=torch.bfloat16, device=dev)
+        mean = torch.empty(B, dtype=torch.float32, device=dev)
+        rstd = torch.empty(B, dtype=torch.float32, device=dev)
+        hip.ln_gelu_fwd(u, gf, bf, h, mean, rstd, B, h2, eps)
+        z = torch.empty((B, npad), dtype=torch.float32, device=dev)
+        hip.gemm_nt(hip.EPI_F32, h, w2s, B, npad, k1, z, bias=b2p)
+        loss = arg = score = y = None
+        if targets is not None:
+            if tuple(targets.shape) != (B, vs):
+                raise ValueError(f'vqa targets must be [{B}, {vs}], got {tuple(targets.shape)}')
+            y = targets.detach().to(torch.float32).contiguous()
+            rows = torch.empty(B, dtype=torch.float32, device=dev)
+            arg = torch.empty(B, dtype=torch.int32, device=dev)
+            score = torch.empty(B, dtype=torch.float32, device=dev)
+            hip.vqa_bce(z, y, B, vs, row_loss=rows, row_arg=arg, row_score=score)
+            loss = rows.sum() / B
+            ctx.mark_non_differentiable(arg, score)
+        logits = z[:, :vs]
+        if out_dtype != torch.float32:
+            logits = logits.to(out_dtype)
+        ctx.save_for_backward(xb, u, h, mean, rstd, z, y, gf, bf, w1t, w2t)
+        ctx.dims = (B, hs, h2, vs, eps)
+        ctx.in_dtypes = (x.dtype, w1.dtype, b1.dtype, ln_w.dtype, ln_b.dtype, w2.dtype, b2.dtype)
+        return logits, loss, arg, score
+
+    @staticmethod
+    def backward(ctx, dlogits, dloss, _darg, _dscore):
+        xb, u, h, mean, rstd, z, y, gf, bf, w1t, w2t = ctx.saved_tensors
+        B, hs, h2, vs, eps = ctx.dims
+        dev = z.device
+        npad, k0, k1 = z.shape[1], xb.shape[1], h.shape[1]
+        dz = torch.empty((B, npad), dtype=torch.bfloat16, device=dev)
+        dadd = dlogits.to(torch.float32).contiguous() if dlogits is not None else None
+        with_loss = y is not None and dloss is not None
+        dscale = dloss.detach().to(torch.float32).reshape(1).contiguous() if with_loss else None
+        hip.vqa_bce(z, y if with_loss else None, B, vs, dscale=dscale, alpha=1.0 / B, dadd=dadd, dz=dz)
+        dh = torch.empty((B, k1), dtype=torch.float32, device=dev)
+        hip.gemm_nt(hip.EPI_F32, dz, w2t, B, k1, npad, dh)
+        dw2 = torch.zeros((npad, k1), dtype=torch.float32, device=dev)
+        hip.gemm_tn(dz, h, dw2, B, npad, k1)
+        db2 = torch.zeros(npad, dtype=torch.float32, device=dev)
+        for r0 in range(0, B, 1008):      # <= 1008 rows per call: one ordered add per column (reproducible)
+            r1 = min(B, r0 + 1008)
+            hip.colsum(dz[r0:r1], db2, r1 - r0, npad)
+        du = torch.empty((B, k1), dtype=torch.bfloat16, device=dev)
+        dg = torch.empty(h2, dtype=torch.float32, device=dev)
+        dbeta = torch.empty(h2, dtype=torch.float32, device=dev)
+        db1 = torch.empty(h2, dtype=torch.float32, device=dev)
+        hip.ln_gelu_bwd(dh, u, gf, bf, mean, rstd, B, h2, dxb=du, dw=dg, db=dbeta, dbias=db1)
+        dx = torch.empty((B, hs), dtype=torch.float32, device=dev)
+        hip.gemm_nt(hip.EPI_F32, du, w1t, B, hs, k1, dx)
+        dw1 = torch.zeros((k1, k0), dtype=torch.float32, device=dev)
+        hip.gemm_tn(du, xb, dw1, B, k1, k0)
+        xd, w1d, b1d, gd, bd, w2d, b2d = ctx.in_dtypes
+        return (dx.to(xd), dw1[:h2, :hs].to(w1d), db1.to(b1d), dg.to(gd), dbeta.to(bd), dw2[:vs, :h2].to(w2d),
+                db2[:vs].to(b2d), None, None, None, None)
 
 
 class BertPredictionHeadTransform(nn.Module):

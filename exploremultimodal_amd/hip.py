@@ -132,6 +132,10 @@ _SIGS = {
     'vlmo_comm_all_gather': [_vp, _vp, _vp, _i64, _i32, _vp],
     'vlmo_grad_pack': [_vp, _vp, _i64, _f32, _vp],
     'vlmo_grad_unpack': [_vp, _vp, _i64, _vp],
+    'vlmo_ln_gelu_fwd': [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _f32, _vp],
+    'vlmo_ln_gelu_bwd': [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp,
+                         _i64, _vp],
+    'vlmo_vqa_bce': [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _i32, _vp],
 }
 
 _lib = None
@@ -530,6 +534,28 @@ def stack_bwd(sdesc):
 def ce_reduce(partial, nchunk, labels, ignore_index, lse, loss, pred, M):
     _check(lib().vlmo_ce_reduce(_p(partial), nchunk, _p(labels), ignore_index, _p(lse), _p(loss), _p(pred), M, _stream()),
            'vlmo_ce_reduce')
+
+
+def ln_gelu_fwd(x, w, b, h, mean, rstd, M, d, eps=1e-12):
+    """h (bf16 [M, >= d], pad columns zeroed) = GELU(LayerNorm(x[:, :d]) * w + b); x fp32."""
+    _check(lib().vlmo_ln_gelu_fwd(_p(x), x.stride(0), _p(w), _p(b), _p(h), h.stride(0), _p(mean), _p(rstd), M, d, eps,
+                                  _stream()), 'vlmo_ln_gelu_fwd')
+
+
+def ln_gelu_bwd(dh, x, w, b, mean, rstd, M, d, *, dx=None, dxb=None, dw=None, db=None, dbias=None):
+    """Backward of ln_gelu_fwd: dx fp32 and / or dxb bf16 (pad columns zeroed); dw, db, dbias overwritten."""
+    ws = workspace(x.device, 3 * d)          # >= min(M, 128) partial rows of 3d floats
+    _check(lib().vlmo_ln_gelu_bwd(_p(dh), dh.stride(0), _p(x), x.stride(0), _p(w), _p(b), _p(mean), _p(rstd), _p(dx),
+                                  dx.stride(0) if dx is not None else 0, _p(dxb), dxb.stride(0) if dxb is not None else 0,
+                                  _p(dw), _p(db), _p(dbias), M, d, _p(ws), ws.numel() * 4, _stream()), 'vlmo_ln_gelu_bwd')
+
+
+def vqa_bce(z, y, B, V, *, row_loss=None, row_arg=None, row_score=None, dscale=None, alpha=1.0, dadd=None, dz=None):
+    """Row kernel of the VQA loss (include/vlmo_hip.h: vlmo_vqa_bce); z, y, dadd fp32, dz bf16 [B, multiple of 64]."""
+    _check(lib().vlmo_vqa_bce(_p(z), z.stride(0), _p(y), y.stride(0) if y is not None else 0, B, V, _p(row_loss),
+                              _p(row_arg), _p(row_score), _p(dscale), float(alpha), _p(dadd),
+                              dadd.stride(0) if dadd is not None else 0, _p(dz), dz.stride(0) if dz is not None else 0,
+                              _stream()), 'vlmo_vqa_bce')
 
 
 def block_fwd(desc):

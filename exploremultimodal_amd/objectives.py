@@ -1,4 +1,4 @@
-"""Pretraining objectives of VlmoModule.forward (models/vlmo/objectives.py:12-314, 532-607):
+"""Objectives of VlmoModule.forward (models/vlmo/objectives.py:12-389, 532-607): the pretraining ones and VQAv2;
 same function names, arguments and returned dict keys.  The backbone passes they trigger run
 on the HIP engine; the loss arithmetic on the gathered rows is stock torch.
 
@@ -69,7 +69,9 @@ def attach_row_indices(batch):
     compute_mim gather by index (``index_select``: the row count is known on the host) instead of by boolean mask, which
     has to ask the device for its count: four host synchronisations per step, two more in the backward.  Same rows, same
     order (ascending) as the boolean form.  A batch without these keys takes the reference's boolean path.  The keys
-    describe THIS batch's masks: whoever edits ``text_labels_mlm`` / ``image_bool_masked_pos`` afterwards drops them."""
+    describe THIS batch's masks: whoever edits ``text_labels_mlm`` / ``image_bool_masked_pos`` afterwards drops them.
+    ``_vqa_has_targets`` (a python bool) = the reference's gate ``torch.sum(vqa_targets) > 0`` (objectives.py:336)
+    read from the host copy, so compute_vqa does not ask the device."""
     lab = batch.get('text_labels_mlm')
     if torch.is_tensor(lab) and not lab.is_cuda:
         batch['_mlm_rows'] = (lab.reshape(-1) != -100).nonzero(as_tuple=False).reshape(-1)
@@ -80,6 +82,9 @@ def attach_row_indices(batch):
         patches = flat.shape[1]
         batch['_mim_rows'] = rows
         batch['_mim_tok_rows'] = rows + torch.div(rows, patches, rounding_mode='floor') + 1
+    vt = batch.get('vqa_targets')
+    if torch.is_tensor(vt) and not vt.is_cuda:
+        batch['_vqa_has_targets'] = bool(torch.sum(vt) > 0.0)
     return batch
 
 
@@ -251,3 +256,66 @@ def compute_mim(module, batch):
                                               module.config.model.img_vocab_size)
     return {'mim_task_loss': loss, 'mim_logits': logits, 'mim_labels': mim_labels, 'mim_mean_acc': acc,
             'mim_count': cnt}
+
+
+def compute_vqa_score(logits, target):
+    """objectives.py:12-21 -> (sum over rows of the target value at the arg-max / rows, rows)."""
+    logits = torch.max(logits, 1)[1]
+    one_hots = torch.zeros_like(target, device=target.device)
+    one_hots.scatter_(1, logits.view(-1, 1), 1)
+    scores = one_hots * target
+    count = len(logits)
+    return scores.sum() / count, count
+
+
+def _vqa_head(model, feats, targets):
+    """vqa_classifier(feats) and, with targets, its loss ``BCE-with-logits mean * vs`` and mean score
+    -> (logits, loss or None, mean score or None).  Features on the GPU take heads.VQAHeadFn (HIP), CPU features the
+    torch modules with the reference's formulas (objectives.py:346-351)."""
+    head = model.vqa_classifier
+    if feats.is_cuda:
+        from .heads import VQAHeadFn, _VQAShadows
+        fc1, ln, _, fc2 = head
+        if not hasattr(model, '_vqa_shadows'):
+            object.__setattr__(model, '_vqa_shadows', _VQAShadows())
+        out_dtype = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else torch.float32
+        logits, loss, _, score_rows = VQAHeadFn.apply(feats, fc1.weight, fc1.bias, ln.weight, ln.bias, fc2.weight,
+                                                      fc2.bias, targets, ln.eps, out_dtype, model._vqa_shadows)
+        return logits, loss, (score_rows.sum() / feats.shape[0] if score_rows is not None else None)
+    logits = head(feats)
+    if targets is None:
+        return logits, None, None
+    loss = F.binary_cross_entropy_with_logits(logits, targets) * targets.shape[1]
+    return logits, loss, compute_vqa_score(logits, targets)[0]
+
+
+def compute_vqa(model, batch):
+    """objectives.py:317-389 without the ISDA branch (VlmoModule refuses isda_lambda > 0).  The gate on the targets is
+    ``batch['_vqa_has_targets']`` when attach_row_indices set it, else the reference's ``torch.sum(targets) > 0``.  With
+    ``config.train.kl_alpha > 0`` in training (R-Drop) a second backbone pass with its own dropout masks adds
+    ``vqa_kl_task_loss`` and averages the two BCE losses."""
+    infer = model.infer(batch, infer_mode='img-txt', mask_txt=False, mask_img=False)
+    vqa_targets = batch.get('vqa_targets')
+    has = batch.get('_vqa_has_targets')
+    if has is None:
+        has = vqa_targets is not None and bool(torch.sum(vqa_targets) > 0.0)
+    vqa_logits, vqa_loss, vqa_mean_score = _vqa_head(model, infer['cls_feats'], vqa_targets if has else None)
+    ret = {'vqa_logits': vqa_logits, 'vqa_count': vqa_logits.size(0)}
+    if not has:
+        return ret
+    ret.update({'vqa_task_loss': vqa_loss, 'vqa_logits': vqa_logits, 'vqa_targets': vqa_targets,
+                'vqa_mean_score': vqa_mean_score, 'vqa_count': vqa_logits.size(0)})
+    kl_alpha = getattr(model.config.train, 'kl_alpha', 0.0)
+    if kl_alpha > 0. and model.training:
+        infer_2 = model.infer(batch, infer_mode='img-txt', mask_txt=False, mask_img=False)
+        vqa_logits_2, vqa_loss_2, _ = _vqa_head(model, infer_2['cls_feats'], vqa_targets)
+        vqa_loss = (vqa_loss + vqa_loss_2) / 2.
+        num_classes = vqa_targets.shape[1]
+        p = torch.log_softmax(vqa_logits.view(-1, num_classes), dim=-1)
+        p_tec = torch.softmax(vqa_logits.view(-1, num_classes), dim=-1)
+        q = torch.log_softmax(vqa_logits_2.view(-1, num_classes), dim=-1)
+        q_tec = torch.softmax(vqa_logits_2.view(-1, num_classes), dim=-1)
+        kl = F.kl_div(p, q_tec, reduction='none').sum()
+        r_kl = F.kl_div(q, p_tec, reduction='none').sum()
+        ret.update({'vqa_task_loss': vqa_loss, 'vqa_kl_task_loss': (kl + r_kl) / 4 * kl_alpha})
+    return ret

@@ -1,8 +1,10 @@
 """Host-side mirror of VlmoModule (models/vlmo/vlmo_module.py:14-442): same constructor
 (attribute-style config), parameter names, `infer` / `forward` / `load_from_ckpt` /
-`no_weight_decay` contracts.  Pretraining losses [mlm, mim, itc, itm]; the downstream
-(vqa / nlvr2 / irtr / mpp), EMA and negative-queue branches raise NotImplementedError
-(out of scope, off in conf/train/pretrain_mum.yaml)."""
+`no_weight_decay` contracts.  Pretraining losses [mlm, mim, itc, itm] and the VQAv2 fine-tuning
+loss [vqa] (the classifier and its loss on the HIP path of heads.VQAHeadFn); the ISDA variant of the
+VQA head (isda_lambda > 0), the other downstream heads (nlvr2 / irtr / mpp / refcoco), EMA and the
+negative queue raise NotImplementedError (out of scope, off in
+conf/train/pretrain_mum.yaml and conf/train/finetune_vqa.yaml)."""
 import math
 from collections import defaultdict
 from functools import partial
@@ -37,10 +39,10 @@ class VlmoModule(nn.Module):
 
         self.loss_names = config.train.loss_names
         hs = model_cfg.embed_dim
-        for unsupported in ('mpp', 'vqa', 'nlvr2', 'irtr', 'refcoco'):
+        for unsupported in ('mpp', 'nlvr2', 'irtr', 'refcoco'):
             if unsupported in self.loss_names:
-                raise NotImplementedError(f'loss {unsupported!r} belongs to a downstream phase outside the '
-                                          'pretraining hot path')
+                raise NotImplementedError(f'loss {unsupported!r} belongs to a downstream phase this engine does not '
+                                          'implement (pretraining and VQAv2 fine-tuning only)')
         if 'mlm' in self.loss_names:
             self.mlm_head = MLMHead(self.transformer.bert_config,
                                     weight=self.transformer.txt_embeddings.word_embeddings.weight)
@@ -61,6 +63,14 @@ class VlmoModule(nn.Module):
                 p.requires_grad = False
             self.mim_head = MIMHead(hs, model_cfg.img_vocab_size)
             self.mim_head.apply(self.transformer._init_weights)
+        if 'vqa' in self.loss_names:                     # vlmo_module.py:85-100
+            if getattr(config.train, 'isda_lambda', 0.0) > 0.:
+                raise NotImplementedError('isda_lambda > 0 (the ISDA head of the VQA classifier) is not implemented; '
+                                          'conf/train/finetune_vqa.yaml leaves it at 0')
+            vs = config.data.vqav2_label_size
+            self.vqa_classifier = nn.Sequential(nn.Linear(hs, hs * 2), norm_layer(hs * 2), nn.GELU(), nn.Linear(hs * 2, vs))
+            self.vqa_classifier.apply(self.transformer._init_weights)
+            self.vqa_last = None
 
         self.transformer_m = None
         if getattr(self.config, 'vlmo_ema', False):
@@ -303,8 +313,10 @@ class VlmoModule(nn.Module):
         if len(self.loss_names) == 0:
             ret.update(self.infer(batch))
             return ret
+        # the VQA pass is not part of the merged passes: with 'vqa' among the losses every objective runs pass by pass
         if (getattr(self.config.train, 'merge_passes', False) and batch['image'] is not None
-                and batch['text_ids'] is not None and getattr(self.config.train, 'mim_head_pos', 'img') == 'img'):
+                and batch['text_ids'] is not None and getattr(self.config.train, 'mim_head_pos', 'img') == 'img'
+                and 'vqa' not in self.loss_names):
             return self._forward_merged(batch)
         if 'mlm' in self.loss_names:
             ret.update(objectives.compute_mlm(self, batch))
@@ -315,6 +327,8 @@ class VlmoModule(nn.Module):
         if 'itm' in self.loss_names:
             itc_ret = ret if 'itc' in self.loss_names else None
             ret.update(objectives.compute_itm(self, batch, itc_ret))
+        if 'vqa' in self.loss_names:
+            ret.update(objectives.compute_vqa(self, batch))
         return ret
 
     @torch.jit.ignore

@@ -409,6 +409,32 @@ int vlmo_ce_reduce(const float* partial, int nchunk, const int32_t* labels, int 
  * partial [M, nchunk, 2] from VLMO_EPI_ARGMAX -> ids int64 [M] (first maximum wins). */
 int vlmo_argmax_reduce(const float* partial, int nchunk, int64_t* ids, int M, hipStream_t stream);
 
+/* ---- VQA classifier head (vlmo_module.py:85-93, objectives.py:12-21, 317-353) ---- */
+
+/* h [M, ldh] bf16 = GELU_erf(LayerNorm(x) * w + b), eps as given (1e-12), fp32 statistics -> mean, rstd [M].
+ * x fp32 [M, ldx]; 0 < d <= 2048, d % 4 == 0; ldx, ldh multiples of 4; columns [d, ldh) of h are written as 0
+ * (the zero pad of the next GEMM's reduction dimension). */
+int vlmo_ln_gelu_fwd(const float* x, int ldx, const float* w, const float* b, void* h, int ldh, float* mean,
+                     float* rstd, int M, int d, float eps, hipStream_t stream);
+/* Backward of vlmo_ln_gelu_fwd from dh = d loss / d h (fp32 [M, lddh]): recomputes the LayerNorm output, applies
+ * GELU', then the LayerNorm backward.  dx fp32 [M, lddx] and / or dxb bf16 [M, lddxb] (pad columns [d, lddxb) = 0);
+ * dw, db (LayerNorm weight / bias) and dbias (= column sums of dx: the bias gradient of the Linear that produced x)
+ * are OVERWRITTEN, each may be NULL.  Column sums are deterministic: fixed-order partial rows in ws, folded in order,
+ * no atomics.  ws: min(M, 128) * 3 * d floats. */
+int vlmo_ln_gelu_bwd(const float* dh, int lddh, const float* x, int ldx, const float* w, const float* b,
+                     const float* mean, const float* rstd, float* dx, int lddx, void* dxb, int lddxb, float* dw,
+                     float* db, float* dbias, int M, int d, float* ws, int64_t ws_bytes, hipStream_t stream);
+/* Per row of the fp32 logits z [B, ldz] (first V columns) against targets y fp32 [B, ldy]:
+ *   row_loss[r]  = sum_n max(z,0) - z*y + log1p(exp(-|z|))      (binary cross-entropy with logits, summed)
+ *   row_arg[r]   = arg-max of z[r, :V]; the FIRST maximum wins (smallest column among equal values)
+ *   row_score[r] = y[r, row_arg[r]]
+ * each output may be NULL; y may be NULL when row_loss and row_score are.  Backward mode (dz != NULL): also writes
+ * dz bf16 [B, lddz] = (sigmoid(z) - y) * alpha * (*dscale) (+ dadd fp32 [B, ldadd] when given), with the pad columns
+ * [V, lddz) = 0; lddz a multiple of 64.  dscale: device scalar (NULL = 1); y NULL = no loss term. */
+int vlmo_vqa_bce(const float* z, int ldz, const float* y, int ldy, int B, int V, float* row_loss, int32_t* row_arg,
+                 float* row_score, const float* dscale, float alpha, const float* dadd, int ldadd, void* dz, int lddz,
+                 hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
