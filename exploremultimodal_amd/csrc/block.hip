@@ -7,17 +7,10 @@
 #include <map>
 #include <vector>
 
-#include <stdlib.h>
 namespace {
 // VlmoEpilogue.relu bit 2: the fc1 epilogue saves GELU'(u) * dropout mask / (1 - p) in place of the pre-activation u, and the
-// GELU-derivative epilogue of dgrad_fc2 multiplies by it (measurement aid: VLMO_SAVE_GELU_DERIV=0 = the pre-activation path)
-int gelu_deriv_flag() {
-    static const int v = [] {
-        const char* e = getenv("VLMO_SAVE_GELU_DERIV");
-        return (e && e[0] == '0') ? 0 : 4;
-    }();
-    return v;
-}
+// GELU-derivative epilogue of dgrad_fc2 multiplies by it
+constexpr int GELU_DERIV = 4;
 
 
 // fork / join events of the calling thread, one set per device (a process may drive several GPUs)
@@ -117,7 +110,7 @@ extern "C" int vlmo_block_fwd(const VlmoBlockDesc* b, hipStream_t st) {
         e.drop_thresh = b->drop_thresh;
         e.inv_keep = b->inv_keep;
         e.seed = b->seed + 20 + 2 * x;
-        e.relu = gelu_deriv_flag();         // `u` holds GELU'(u) * mask / (1 - p): see the backward's EPI_DGELU
+        e.relu = GELU_DERIV;         // `u` holds GELU'(u) * mask / (1 - p): see the backward's EPI_DGELU
         a2[x] = bp(b->h, r0, hid, 2);
         w2[x] = b->w2[x];
         VlmoEpilogue& f = e2[x] = epi();
@@ -200,7 +193,7 @@ extern "C" int vlmo_block_bwd(const VlmoBlockDesc* b, hipStream_t st) {
         e.drop_thresh = b->drop_thresh;
         e.inv_keep = b->inv_keep;
         e.seed = b->seed + 20 + 2 * x;
-        e.relu = gelu_deriv_flag();
+        e.relu = GELU_DERIV;
         af[x] = bp(b->du, r0, hid, 2);
         wf[x] = b->w1T[x];
         VlmoEpilogue& f = ef[x] = epi();
@@ -329,7 +322,6 @@ int block_dgrad_chain(const VlmoBlockDesc* b, hipStream_t st, Deferred& D, const
     const void *ag[4], *wg[4], *af[4], *wf[4];
     int32_t rows[4];
     VlmoEpilogue eg[4], ef[4];
-    static const bool fold_db1 = !getenv("VLMO_FOLD_DB1") || atoi(getenv("VLMO_FOLD_DB1")) != 0;   // measurement aid
     int64_t colpart_off = (int64_t)(4 + b->n_experts) * slot / 4;       // floats (behind the fold slots)
     for (int x = 0; x < b->n_experts; ++x) {
         const size_t r0 = b->exp_row0[x];
@@ -352,12 +344,12 @@ int block_dgrad_chain(const VlmoBlockDesc* b, hipStream_t st, Deferred& D, const
         e.drop_thresh = b->drop_thresh;
         e.inv_keep = b->inv_keep;
         e.seed = b->seed + 20 + 2 * x;
-        e.relu = gelu_deriv_flag();
+        e.relu = GELU_DERIV;
         // fc1 bias gradient: the DGELU epilogue leaves column-sum partials (one row per 16 output rows, see
         // VlmoEpilogue.colpart) behind the (4 + experts) fold slots when the workspace has room; they join the block's
         // other column folds.  Else: a pass over du.
         const int nblk64 = (n + 15) / 16;       // 16-row blocks
-        if (fold_db1 && b->db1[x] && (colpart_off + (int64_t)nblk64 * hid) * 4 <= b->ws_bytes) {
+        if (b->db1[x] && (colpart_off + (int64_t)nblk64 * hid) * 4 <= b->ws_bytes) {
             e.colpart = (float*)b->ws_main + colpart_off;
             colpart_off += (int64_t)nblk64 * hid;
             VlmoColJob j{};
@@ -428,8 +420,7 @@ int block_dgrad_chain(const VlmoBlockDesc* b, hipStream_t st, Deferred& D, const
         e.ldo = d;
         TRY(vlmo_gemm_nt(VLMO_EPI_BIAS, VLMO_BF16, b->tile, b->dqkv, 3 * d, b->qkv_wT, 3 * d, M, d, 3 * d, &e, st));
     }
-    static const bool fuse_below = !getenv("VLMO_FUSE_BELOW") || atoi(getenv("VLMO_FUSE_BELOW")) != 0;   // measurement aid
-    const VlmoBlockDesc* n = fuse_below ? below : nullptr;
+    const VlmoBlockDesc* n = below;
     *fused_below = false;
     if (n && n->M == M && n->d == d && n->dx2 == b->dx0 && n->zd2 && n->dz2 && n->n_experts >= 1 && n->n_experts <= 2 &&
         n->exp_row0[0] == 0 && (n->n_experts == 1 ? n->exp_rows[0] == M

@@ -3,7 +3,6 @@
 // [B*H*W, C] (the reference runs this encoder in fp16 on GPU: dall_e/utils.py:37-42).
 #include "common.h"
 #include "vlmo_hip.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -208,8 +207,7 @@ extern "C" int vlmo_dvae_im2col(const float* x, void* out, int B, int C, int H, 
     const long total8 = (long)B * H * W * (Kpad / 8);
     const int grid = (int)((total8 + 255) / 256 < 65536 ? (total8 + 255) / 256 : 65536);
     const size_t row_lds = (size_t)(C * kw + 1) * (W + kw - 1) * sizeof(float);
-    static const bool gather = getenv("VLMO_IM2COL_GATHER") != nullptr;      // measurement aid: the element-gather form
-    if (kw == 7 && Kpad <= 2048 && row_lds <= 48 * 1024 && (long)B * H < 0x7fffffffL && !gather)
+    if (kw == 7 && Kpad <= 2048 && row_lds <= 48 * 1024 && (long)B * H < 0x7fffffffL)
         hipLaunchKernelGGL(im2col_row_kernel<7>, dim3(B * H), dim3(256), row_lds, stream, x, (f16*)out, C, H, W, Kpad);
     else if (kw == 7)
         hipLaunchKernelGGL(im2col_kernel<7>, dim3(grid), dim3(256), 0, stream, x, (f16*)out, B, C, H, W, kw, Kpad, total8);

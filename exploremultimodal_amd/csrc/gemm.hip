@@ -16,9 +16,7 @@
 // math fused in.
 #include "common.h"
 #include "vlmo_hip.h"
-#include <stdlib.h>
 #include <mutex>
-#include <string>
 #include <vector>
 #include <utility>
 #include <type_traits>
@@ -760,7 +758,7 @@ template <int... Is, typename F> __device__ __forceinline__ void static_for(std:
 // the split, and the tile height moves in 16-row steps (208 rows: 243 tiles for N = 768 at M = 16 704; 272 rows: 744 tiles
 // = three rounds for N = 3 072; 304 rows: 495 tiles = two rounds for N = 2 304).  Everything from the accumulators on is
 // written once and instantiated per wave group (`body`); both copies execute the same barrier sequence.
-template <typename T, int H16, int EPI, int SCHED = 1, int GD = 0>
+template <typename T, int H16, int EPI, int GD = 0>
 __global__ __launch_bounds__(512, 2) void gemm_nt16_kernel(const GemmNTGroups gp) {
     typedef typename Elem<T>::v8 v8;
     constexpr int TMA = (H16 + 1) / 2, TMB = H16 / 2;
@@ -772,7 +770,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt16_kernel(const GemmNTGroups gp
     static_assert(NW * 32 * 64 * 4 <= 2 * STAGE, "epilogue LDS must fit in the ring");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-    const uint64_t t_kernel = (SCHED & 8) ? __builtin_amdgcn_s_memtime() : 0;      // diagnostic build only
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
@@ -891,58 +888,26 @@ __global__ __launch_bounds__(512, 2) void gemm_nt16_kernel(const GemmNTGroups gp
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             if (wm == 1) bar();
-            // diagnostic build (SCHED & 8): s_memtime at every segment boundary of one K loop, sums per segment kind and the
-            // in-kernel clock (cycles per 100 MHz tick of s_memrealtime) -> e.colpart[workgroup][wave][8] (tools/nt16_probe.py)
-            constexpr bool PROBE = (SCHED & 8) != 0;
-            constexpr int SCH = SCHED & 7;
-            uint64_t seg_sum[4] = {0, 0, 0, 0}, t_prev = 0, t_begin = 0, r_begin = 0;
-            auto stamp = [&](int k) {
-                if constexpr (PROBE) {
-                    const uint64_t t = __builtin_amdgcn_s_memtime();
-                    seg_sum[k] += t - t_prev;
-                    t_prev = t;
-                }
-            };
-            if constexpr (PROBE) {
-                t_begin = t_prev = __builtin_amdgcn_s_memtime();
-                r_begin = __builtin_amdgcn_s_memrealtime();
-                // o[7] of the record: cycles from the kernel's first instruction to here (set-up, first DMA issued and landed)
-                if (p.e.colpart && lane == 0)
-                    ((uint64_t*)p.e.colpart)[((size_t)blockIdx.x * NW + wave) * 8 + 7] = t_begin - t_kernel;
-            }
             for (int kt = 0; kt < nk; ++kt) {
                 const char* cur = smem + (kt & 1) * STAGE;
                 const bool more = kt + 1 < nk;
                 read_half(cur, 0);
-                // SCHED 1: the LDS-DMA of the next K-tile is issued in the READ segment, behind the fragment reads (the other
-                // buffer was last read two segments ago by this group, one segment ago by the other, each behind lgkmcnt(0) +
+                // the LDS-DMA of the next K-tile is issued in the READ segment, behind the fragment reads (the other buffer
+                // was last read two segments ago by this group, one segment ago by the other, each behind lgkmcnt(0) +
                 // barrier): the issue cost of the eight DMA instructions (~60-180 cycles each) then runs beside the partner
                 // wave's MFMA segment instead of in front of this wave's own
-                if (SCH == 1 && more) stage((kt + 1) & 1, kt + 1);
+                if (more) stage((kt + 1) & 1, kt + 1);
                 bar();
-                stamp(0);
-                if (SCH == 0 && more) stage((kt + 1) & 1, kt + 1);
                 mfma_half();
                 bar();
-                stamp(1);
                 read_half(cur, 1);
                 if (more && wm == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 bar();
-                stamp(2);
                 mfma_half();
                 if (more && wm == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 bar();
-                stamp(3);
             }
             if (wm == 0) bar();
-            if constexpr (PROBE) {
-                const uint64_t t_end = __builtin_amdgcn_s_memtime(), r_end = __builtin_amdgcn_s_memrealtime();
-                if (p.e.colpart && lane == 0) {
-                    uint64_t* o = (uint64_t*)p.e.colpart + ((size_t)blockIdx.x * NW + wave) * 8;
-                    o[0] = seg_sum[0], o[1] = seg_sum[1], o[2] = seg_sum[2], o[3] = seg_sum[3];
-                    o[4] = t_end - t_begin, o[5] = r_end - r_begin, o[6] = (uint64_t)nk;
-                }
-            }
         }
 
         // ---- epilogue: accumulators -> wave-private LDS -> full-row segments, in passes of two 16-row tiles (one for the last
@@ -1057,11 +1022,6 @@ struct GemmTN {
 };
 enum { TN_ATOMIC = 0, TN_ACCUM = 1, TN_STORE = 2 };
 
-#ifndef VLMO_TN_DMA_IN_READ
-#define VLMO_TN_DMA_IN_READ 1
-#endif
-constexpr bool TN_DMA_IN_READ = VLMO_TN_DMA_IN_READ != 0;      // build-time A/B (make EXTRA=-DVLMO_TN_DMA_IN_READ=0)
-
 // 256 zero bytes: the staging source of token rows past the end of the reduction dimension
 __device__ __attribute__((aligned(256))) char tn_zero_page[256];
 
@@ -1070,17 +1030,17 @@ __device__ __forceinline__ int tn_swz(int row) { return ((row & 3) << 2) | ((row
 
 // Output tile BM x BN (multiples of 128) per workgroup of WM x WN waves; each operand's K-tile (64 token rows)
 // is staged as BM/128 resp. BN/128 side-by-side sub-images of [64 rows][128 columns] in the dual-use swizzle.
-// R4 (ping-pong kernel only): the reduction is staged in 32-token SLICES through a ring of four 32 KB slots instead of
+// PP (the ping-pong kernel): the reduction is staged in 32-token SLICES through a ring of four 32 KB slots instead of
 // 64-token tiles through two 64 KB buffers.  The reduction index of this kernel is the ROW of both operands, so a slice
 // is still made of whole 256-byte row pieces (the NT kernel cannot do this: its K runs along the rows, half a K-tile is
 // half of every cache line).  Slice h + 3 is issued in the read segment of slice h -- four DMA instructions per wave
 // and segment instead of eight in every other one -- and waited for with a counted vmcnt that leaves two slices in flight.
-template <typename T, int BM, int BN, int WM, int WN, bool PP = false, bool PROBE = false, bool R4 = false, bool M16 = false>
+template <typename T, int BM, int BN, int WM, int WN, bool PP = false>
 __device__ __forceinline__ void gemm_tn_body(const GemmTN& p, const int lid) {
     typedef typename Elem<T>::v8 v8;
     typedef typename Elem<T>::v4 v4;
     constexpr int NW = WM * WN;
-    constexpr int SROWS = R4 ? 32 : 64;                 // token rows per staged unit
+    constexpr int SROWS = PP ? 32 : 64;                 // token rows per staged unit
     constexpr int SUB = SROWS * 256;                    // one sub-image
     constexpr int NSA = BM / 128, NSB = BN / 128;
     constexpr int A_BYTES = NSA * SUB, STAGE = (NSA + NSB) * SUB;
@@ -1088,7 +1048,7 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTN& p, const int lid) {
     constexpr int IPS = SROWS / 4;                      // LDS-DMA instructions per sub-image and staged unit
     constexpr int IA = NSA * IPS / NW, IB = NSB * IPS / NW;   // ... per wave
     static_assert((NSA * IPS) % NW == 0 && (NSB * IPS) % NW == 0, "tile/wave mismatch");
-    static_assert(!R4 || (PP && IA + IB == 4), "slice ring: ping-pong schedule, four DMA instructions per wave and slice");
+    static_assert(!PP || IA + IB == 4, "slice ring: four DMA instructions per wave and slice");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1133,7 +1093,7 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTN& p, const int lid) {
     for (int i = 0; i < IA; ++i) a_vo[i] = (uint32_t)(a_row[i] * p.lda + a_off[i]) * 2u;
 #pragma unroll
     for (int i = 0; i < IB; ++i) b_vo[i] = (uint32_t)(b_row[i] * p.ldb + b_off[i]) * 2u;
-    // kt: index of the staged unit (64-token K-tile, or 32-token slice with R4)
+    // kt: index of the staged unit (64-token K-tile, or 32-token slice with PP)
     auto stage = [&](int buf, int kt) {
         char* s = smem + buf * STAGE;
         if (PP && fits32 && (kt + 1) * SROWS <= p.M) {
@@ -1158,132 +1118,6 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTN& p, const int lid) {
             glds16((const T*)p.B + (size_t)gr * p.ldb + b_off[i], s + A_BYTES + (i * NW + wave) * 1024);
         }
     };
-
-    if constexpr (M16) {
-        // ---- v_mfma_f32_16x16x32 variant of the slice ring (round 4; the NT kernels' port measured +8.6 % at the MFMA-paced
-        // probe shape): a 32-token slice is ONE k-step.  Operand lane l holds column l & 15, tokens 8 (l >> 4) + j: two
-        // transposed reads of 4 tokens x 16 columns each (tests/test_lds_layouts.py::test_gemm_tn16_fragments: right elements,
-        // conflict-free on the unchanged image).  C/D: column = l & 15, row = 4 (l >> 4) + register.
-        static_assert(PP && R4 && WM == 2, "16x16x32: slice ring, ping-pong schedule");
-        constexpr int T16M = BM / WM / 16, T16N = BN / WN / 16;
-        f32x4 acc[T16M][T16N];
-#pragma unroll
-        for (int i = 0; i < T16M; ++i)
-#pragma unroll
-            for (int j = 0; j < T16N; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3, l15 = lane & 15;
-        const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
-        uint32_t a_rd[2][T16M], b_rd[2][T16N];
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            const int m0 = 8 * g + 4 * half + q;
-            const int sw = tn_swz(m0);
-#pragma unroll
-            for (int t = 0; t < T16M; ++t) {
-                const int na = wm * (BM / WM) + t * 16 + 4 * pp;
-                a_rd[half][t] = lds0 + (na >> 7) * SUB + m0 * 256 + ((((na & 127) >> 3) ^ sw) << 4) + (na & 7) * 2;
-            }
-#pragma unroll
-            for (int t = 0; t < T16N; ++t) {
-                const int nb = wn * (BN / WN) + t * 16 + 4 * pp;
-                b_rd[half][t] = lds0 + A_BYTES + (nb >> 7) * SUB + m0 * 256 + ((((nb & 127) >> 3) ^ sw) << 4) + (nb & 7) * 2;
-            }
-        }
-        v8 af[T16M], bf[T16N];
-        typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-        auto tr = [&](uint32_t addr) -> v4 {        // inline asm: see the 32x32x16 path below (hipcc waits vmcnt(0) behind the builtin)
-            u32x2 r;
-            asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr));
-            return __builtin_bit_cast(v4, r);
-        };
-        auto read_slice = [&](int slot) {
-            const uint32_t so = (uint32_t)slot * STAGE;
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-#pragma unroll
-                for (int t = 0; t < T16N; ++t) {
-                    const v4 vb = tr(b_rd[half][t] + so);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) bf[t][4 * half + e] = vb[e];
-                }
-#pragma unroll
-                for (int t = 0; t < T16M; ++t) {
-                    const v4 va = tr(a_rd[half][t] + so);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) af[t][4 * half + e] = va[e];
-                }
-            }
-        };
-        auto mfma_slice = [&]() {
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < T16M; ++i)
-#pragma unroll
-                for (int j = 0; j < T16N; ++j) acc[i][j] = Elem<T>::mfma16(af[i], bf[j], acc[i][j]);
-            __builtin_amdgcn_s_setprio(0);
-        };
-        auto bar = [&]() {
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        const int ns = 2 * (kt1 - kt0), s0 = 2 * kt0;
-        auto wait_next = [&](int h) {
-            if (h + 3 < ns) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else if (h + 2 < ns) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        };
-        stage(0, s0);
-        stage(1, s0 + 1);
-        if (ns > 2) stage(2, s0 + 2);
-        wait_next(-1);
-        __builtin_amdgcn_s_barrier();
-        if (wm == 1) bar();
-        for (int h_ = 0; h_ < ns; ++h_) {
-            read_slice(h_ & 3);
-            if (h_ + 3 < ns) stage((h_ + 3) & 3, s0 + h_ + 3);
-            if (wm == 1 && h_ + 1 < ns) wait_next(h_);
-            bar();
-            mfma_slice();
-            if (wm == 0 && h_ + 1 < ns) wait_next(h_);
-            bar();
-        }
-        if (wm == 0) bar();
-        // epilogue: lane = output column (16 per tile), registers = four consecutive output rows
-#pragma unroll
-        for (int i = 0; i < T16M; ++i)
-#pragma unroll
-            for (int j = 0; j < T16N; ++j) {
-                const int gn = n2_0 + wn * (BN / WN) + j * 16 + l15;
-                const int gm0 = n1_0 + wm * (BM / WM) + i * 16 + 4 * g;
-                const bool okn = gn < p.N2;
-                if (!p.slab && p.mode == TN_ACCUM) {
-                    float old[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) old[r] = (okn && gm0 + r < p.N1) ? p.C[(size_t)(gm0 + r) * p.ldc + gn] : 0.f;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (okn && gm0 + r < p.N1) p.C[(size_t)(gm0 + r) * p.ldc + gn] = old[r] + p.alpha * acc[i][j][r];
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int gm = gm0 + r;
-                        if (gm < p.N1 && okn) {
-                            float* c = p.C + (size_t)gm * p.ldc + gn;
-                            if (p.slab)
-                                p.slab[((size_t)split * p.N1 + gm) * p.N2 + gn] = acc[i][j][r];
-                            else if (p.mode == TN_STORE)
-                                *c = p.alpha * acc[i][j][r];
-                            else
-                                atomicAdd(c, p.alpha * acc[i][j][r]);
-                        }
-                    }
-                }
-            }
-        return;
-    }
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -1337,8 +1171,7 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTN& p, const int lid) {
             return lds_tr4<T>(s_ + off + imm);
         }
     };
-    auto read_step = [&](const char* s_, int kt, int ks, v8* af, v8* bf) {
-        (void)kt;
+    auto read_step = [&](const char* s_, int ks, v8* af, v8* bf) {
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
 #pragma unroll
@@ -1357,7 +1190,7 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTN& p, const int lid) {
             }
         }
     };
-    if constexpr (PP && R4) {
+    if constexpr (PP) {
         static_assert(WM == 2, "ping-pong schedule needs two row groups");
         v8 af[2][TM], bf[2][TN];
         auto mfma_half = [&]() {
@@ -1390,117 +1223,19 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTN& p, const int lid) {
         wait_next(-1);
         __builtin_amdgcn_s_barrier();
         if (wm == 1) bar();
-        uint64_t seg_sum[4] = {0, 0, 0, 0}, t_prev = 0, t_begin = 0, r_begin = 0;
-        auto stamp = [&](int k) {
-            if constexpr (PROBE) {
-                const uint64_t t = __builtin_amdgcn_s_memtime();
-                seg_sum[k] += t - t_prev;
-                t_prev = t;
-            }
-        };
-        if constexpr (PROBE) {
-            t_begin = t_prev = __builtin_amdgcn_s_memtime();
-            r_begin = __builtin_amdgcn_s_memrealtime();
-        }
         for (int h_ = 0; h_ < ns; ++h_) {
             const char* cur = smem + (h_ & 3) * STAGE;
-            read_step(cur, 0, 0, af[0], bf[0]);
-            read_step(cur, 0, 1, af[1], bf[1]);
+            read_step(cur, 0, af[0], bf[0]);
+            read_step(cur, 1, af[1], bf[1]);
             // slot (h + 3) & 3 held slice h - 1: read by this group two segments ago, by the other one segment ago
             if (h_ + 3 < ns) stage((h_ + 3) & 3, s0 + h_ + 3);
             if (wm == 1 && h_ + 1 < ns) wait_next(h_);
             bar();
-            stamp((h_ & 1) * 2);
             mfma_half();
             if (wm == 0 && h_ + 1 < ns) wait_next(h_);
             bar();
-            stamp((h_ & 1) * 2 + 1);
         }
         if (wm == 0) bar();
-        if constexpr (PROBE) {
-            const uint64_t t_end = __builtin_amdgcn_s_memtime(), r_end = __builtin_amdgcn_s_memrealtime();
-            if (lane == 0) {
-                uint64_t* o = (uint64_t*)p.slab + ((size_t)blockIdx.x * NW + wave) * 8;
-                o[0] = seg_sum[0], o[1] = seg_sum[1], o[2] = seg_sum[2], o[3] = seg_sum[3];
-                o[4] = t_end - t_begin, o[5] = r_end - r_begin, o[6] = (uint64_t)(kt1 - kt0), o[7] = 1;
-            }
-            return;
-        }
-    } else if constexpr (PP) {
-        // ping-pong schedule: see gemm_nt_kernel (wm == 1 waves run one segment behind wm == 0)
-        static_assert(WM == 2, "ping-pong schedule needs two row groups");
-        v8 af[2][TM], bf[2][TN];
-        auto mfma_half = [&]() {
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[i][j] = Elem<T>::mfma(af[u][i], bf[u][j], acc[i][j]);
-            __builtin_amdgcn_s_setprio(0);
-        };
-        auto bar = [&]() {
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        // One whole K-tile is staged at the start of the first MFMA segment of the previous tile and waited for by the
-        // issuing wave before the barrier that opens it.  Measured against a half-tile variant with 1.5 K-tiles in
-        // flight and counted waits (DMA issued in the read segments): 610 vs 650 us for the two-block launch, 527 vs
-        // 585 us with L2-resident operands -- what bounds this loop is the CU's L1 fill rate, not exposed latency, and
-        // DMA issue beside the partner group's LDS reads costs more than the extra half tile in flight buys.
-        stage(0, kt0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (wm == 1) bar();
-        // diagnostic build (PROBE): cycles per segment kind and the in-kernel clock -> p.slab[workgroup][wave][8] (uint64)
-        uint64_t seg_sum[4] = {0, 0, 0, 0}, t_prev = 0, t_begin = 0, r_begin = 0;
-        auto stamp = [&](int k) {
-            if constexpr (PROBE) {
-                const uint64_t t = __builtin_amdgcn_s_memtime();
-                seg_sum[k] += t - t_prev;
-                t_prev = t;
-            }
-        };
-        if constexpr (PROBE) {
-            t_begin = t_prev = __builtin_amdgcn_s_memtime();
-            r_begin = __builtin_amdgcn_s_memrealtime();
-        }
-        for (int kt = kt0; kt < kt1; ++kt) {
-            const char* cur = smem + ((kt - kt0) & 1) * STAGE;
-            const bool more = kt + 1 < kt1;
-            read_step(cur, kt, 0, af[0], bf[0]);
-            read_step(cur, kt, 1, af[1], bf[1]);
-            if (TN_DMA_IN_READ && more) stage((kt - kt0 + 1) & 1, kt + 1);      // see gemm_nt_kernel: DMA issue beside the partner's MFMAs
-            bar();
-            stamp(0);
-            if (!TN_DMA_IN_READ && more) stage((kt - kt0 + 1) & 1, kt + 1);
-            mfma_half();
-            bar();
-            stamp(1);
-            read_step(cur, kt, 2, af[0], bf[0]);
-            read_step(cur, kt, 3, af[1], bf[1]);
-            if (more && wm == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            bar();
-            stamp(2);
-            mfma_half();
-            if (more && wm == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            bar();
-            stamp(3);
-        }
-        if (wm == 0) bar();
-        if constexpr (PROBE) {
-            const uint64_t t_end = __builtin_amdgcn_s_memtime(), r_end = __builtin_amdgcn_s_memrealtime();
-            if (lane == 0) {
-                uint64_t* o = (uint64_t*)p.slab + ((size_t)blockIdx.x * NW + wave) * 8;
-                o[0] = seg_sum[0], o[1] = seg_sum[1], o[2] = seg_sum[2], o[3] = seg_sum[3];
-                o[4] = t_end - t_begin, o[5] = r_end - r_begin, o[6] = (uint64_t)(kt1 - kt0), o[7] = 0;
-            }
-            return;     // the probe build leaves C alone
-        }
     } else {
         stage(0, kt0);
         for (int kt = kt0; kt < kt1; ++kt) {
@@ -1511,7 +1246,7 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTN& p, const int lid) {
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 v8 af[TM], bf[TN];
-                read_step(s, kt, ks, af, bf);
+                read_step(s, ks, af, bf);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1568,9 +1303,9 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTN& p, const int lid) {
         }
 }
 
-template <typename T, int BM, int BN, int WM, int WN, bool PP = false, bool PROBE = false, bool R4 = false>
+template <typename T, int BM, int BN, int WM, int WN, bool PP = false>
 __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_tn_kernel(const GemmTN p) {
-    gemm_tn_body<T, BM, BN, WM, WN, PP, PROBE, R4>(p, xcd_remap(blockIdx.x, gridDim.x));
+    gemm_tn_body<T, BM, BN, WM, WN, PP>(p, xcd_remap(blockIdx.x, gridDim.x));
 }
 
 // Up to MAX_TN_PROBS weight-gradient problems in ONE launch of 256x256 tiles (the four to six linears of one or
@@ -1590,7 +1325,7 @@ struct GemmTNMulti {
     GemmTN p[MAX_TN_PROBS];
     uint16_t order[MAX_TN_ORDER];
 };
-template <typename T, bool R4 = false, bool M16 = false>
+template <typename T>
 __global__ __launch_bounds__(512, 2) void gemm_tn_multi_kernel(const GemmTNMulti mp) {
     const uint32_t code = mp.order[blockIdx.x];
     if (code == TN_NOP) return;
@@ -1609,7 +1344,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_multi_kernel(const GemmTNMulti
     p.alpha = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, q.alpha)));
     p.slab = nullptr;
     p.mode = __builtin_amdgcn_readfirstlane(q.mode);
-    gemm_tn_body<T, 256, 256, 2, 4, true, false, R4, M16>(p, lid_in);
+    gemm_tn_body<T, 256, 256, 2, 4, true>(p, lid_in);
 }
 
 // C[r, c] += alpha * sum_s slab[s, r, c]   (one float4 per thread)
@@ -1682,7 +1417,7 @@ int launch_nt(int epi, GemmNTGroups& p, hipStream_t st) {
 }
 
 // 16x16x32 kernels: (16 * H16) x 256 tiles, one workgroup per CU
-template <typename T, int H16, int SCHED = 1, unsigned EMASK = 0xFu>
+template <typename T, int H16>
 int launch_nt16(int epi, GemmNTGroups& p, hipStream_t st) {
     constexpr int BM = 16 * H16, BN = 256, BK = 64;
     int tiles = 0;
@@ -1702,19 +1437,16 @@ int launch_nt16(int epi, GemmNTGroups& p, hipStream_t st) {
             return -1;
         }
 #define VLMO_LAUNCH16(E)                                                                        \
-    case E:                                                                                     \
-    if constexpr (((EMASK >> E) & 1u) == 0) {                                                   \
-        known = false;                                                                          \
-    } else {                                                                                    \
+    case E: {                                                                                   \
         constexpr bool HAS_GD = (E == EPI_BIAS_GELU || E == EPI_DGELU);                         \
         if (HAS_GD && gd) {                                                                     \
-            auto k = gemm_nt16_kernel<T, H16, E, SCHED, HAS_GD ? 1 : 0>;                        \
+            auto k = gemm_nt16_kernel<T, H16, E, HAS_GD ? 1 : 0>;                               \
             static DeviceOnce attr_set;                                                         \
             if (LDS > 65536 && attr_set.first())                                                \
                 (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); \
             hipLaunchKernelGGL(k, grid, block, LDS, st, p);                                     \
         } else {                                                                                \
-            auto k = gemm_nt16_kernel<T, H16, E, SCHED, 0>;                                     \
+            auto k = gemm_nt16_kernel<T, H16, E, 0>;                                            \
             static DeviceOnce attr_set;                                                         \
             if (LDS > 65536 && attr_set.first())                                                \
                 (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); \
@@ -1854,14 +1586,11 @@ int run_nt(int epi, int dtype, int tile, GemmNTGroups& gp, hipStream_t stream) {
         for (int q = 0; q < gp.ngroups; ++q) t256_all += (long)((gp.g[q].M + 255) / 256) * ((N + 255) / 256);
         const bool few_tiles = t256_all <= 128;
         if (few_tiles) tile = 0;
-        static const bool tile4 = !getenv("VLMO_NT_TILE4") || atoi(getenv("VLMO_NT_TILE4")) != 0;     // measurement aid
-        if (tile4 && tile == 0 && dtype == VLMO_BF16 && (epi == EPI_BIAS || epi == EPI_BIAS_GELU) && K <= 1024 && N >= 2048 && Mtot >= 4096)
+        if (tile == 0 && dtype == VLMO_BF16 && (epi == EPI_BIAS || epi == EPI_BIAS_GELU) && K <= 1024 && N >= 2048 && Mtot >= 4096)
             tile = 4;
         // 192-row ping-pong tiles when they cut the dispatch rounds (VLMo-Large at 32 pairs: M = 8 352 = 32.6 x 256, so
         // N = 1 024 is 132 tiles of 256x256 on 256 CUs but 176 tiles of 192x256, each 3/4 of the work)
-        static const int t192 = getenv("VLMO_NT_TILE192") ? atoi(getenv("VLMO_NT_TILE192")) : 2;       // measurement aid: 0 off, 1 only in place of 256x256, 2 in place of any
-        if (t192 && !few_tiles && dtype == VLMO_BF16 && (epi == EPI_BIAS || epi == EPI_BIAS_GELU || epi == EPI_RESID || epi == EPI_DGELU) && K >= 1024 &&
-            (tile == 3 || t192 == 2)) {
+        if (!few_tiles && dtype == VLMO_BF16 && (epi == EPI_BIAS || epi == EPI_BIAS_GELU || epi == EPI_RESID || epi == EPI_DGELU) && K >= 1024) {
             long t256 = 0, t192n = 0;
             for (int q = 0; q < gp.ngroups; ++q) {
                 t256 += (long)((gp.g[q].M + 255) / 256) * ((N + 255) / 256);
@@ -1879,18 +1608,14 @@ int run_nt(int epi, int dtype, int tile, GemmNTGroups& gp, hipStream_t stream) {
     // (0.77).  The tiles picked above cost, in the same units: 256x256 rounds x 42, 192x256 rounds x 38, 256x128x32 (two per
     // CU, the epilogue of one under the K loop of the other) rounds-of-512 x 38, 128x128 rounds-of-512 x 21 (16 when every
     // tile has a CU to itself).
-    static const int nt16 = getenv("VLMO_NT16") ? atoi(getenv("VLMO_NT16")) : 1;       // measurement aid: 0 = off
-    static const int nt16_epis = getenv("VLMO_NT16_EPIS") ? atoi(getenv("VLMO_NT16_EPIS")) : 0xF;     // bit e: epilogue e may take these tiles
     // at EQUAL tile height the 16x16x32 kernel is 4 - 8 % faster than the 32x32x16 ones (DMA issued in the read segment;
     // tools/nt16_bench.py at M = 12 608 / 33 408, profiles/r04_nt16_bigM.txt), so a tie in the model goes to it; problems from
     // 40 output tiles of 256 x 256 up (M = 12 608 at N = 768: 42 -> 36 us).  In-session A/Bs of the full four-loss objective
     // (B = 32, merged passes): (97 %, 150 tiles) -> (102, 100) -1.0 ms, -> (106, 40) another -1.3 ms, (110, 16) no further
     // change; VLMo-Large -0.3 ms (its N = 1 024 GEMMs at 8 352 rows were below the old threshold), VLMo-Base unchanged.
-    static const int nt16_tie = getenv("VLMO_NT16_TIE") ? atoi(getenv("VLMO_NT16_TIE")) : 106;        // measurement aid: percent of the old tile's cost
-    static const long nt16_min = getenv("VLMO_NT16_MIN") ? atol(getenv("VLMO_NT16_MIN")) : 40;
-    if (nt16 && ((nt16_epis >> epi) & 1) && (tile == 0 || tile == 3 || tile == 4 || tile == 8) && dtype == VLMO_BF16 && !gp.g[0].k1 && !gp.g[0].ckw &&
+    if ((tile == 0 || tile == 3 || tile == 4 || tile == 8) && dtype == VLMO_BF16 && !gp.g[0].k1 && !gp.g[0].ckw &&
         (epi == EPI_BIAS || epi == EPI_BIAS_GELU || epi == EPI_RESID || epi == EPI_DGELU) && N >= 512 && K >= 512 &&
-        Mtot * (long)N >= nt16_min * 65536l && tile_in < 0) {
+        Mtot * (long)N >= 40 * 65536l && tile_in < 0) {
         auto count = [&](int bm, int bn) {
             long t = 0;
             for (int q = 0; q < gp.ngroups; ++q) t += (long)((gp.g[q].M + bm - 1) / bm) * ((N + bn - 1) / bn);
@@ -1907,24 +1632,9 @@ int run_nt(int epi, int dtype, int tile, GemmNTGroups& gp, hipStream_t stream) {
             const double c = (double)((count(16 * h16, 256) + 255) / 256) * (h16 + 26);
             if (c < bc) bc = c, best = h16;
         }
-        if (bc * 100 <= cur * nt16_tie) tile = 300 + best;
+        if (bc * 100 <= cur * 106) tile = 300 + best;
     }
     if (tile >= 106 && tile <= 110) tile = 300 + 2 * (tile - 100);      // (32 * (tile - 100)) rows = an even H16
-    static const bool trace = getenv("VLMO_NT_TRACE") != nullptr;       // measurement aid: every distinct (epilogue, shape, tile) once
-    if (trace) {
-        static std::mutex mu;
-        static std::vector<std::string> seen;
-        char buf[256];
-        int o = snprintf(buf, sizeof buf, "vlmo_gemm_nt: epi %d N %d K %d tile %d (asked %d) M", epi, N, K, tile, tile_in);
-        for (int q = 0; q < gp.ngroups && o < 230; ++q) o += snprintf(buf + o, sizeof buf - o, " %d", gp.g[q].M);
-        std::lock_guard<std::mutex> lk(mu);
-        bool have = false;
-        for (auto& t : seen) have |= (t == buf);
-        if (!have) {
-            seen.emplace_back(buf);
-            fprintf(stderr, "%s\n", buf);
-        }
-    }
     if (tile >= 309 && tile <= 320) {
         // 16x16x32 MFMA, (16 * (tile - 300)) x 256 tile: bf16, plain GEMM (no convolution, no second segment)
         VLMO_CHECK_ARG(dtype == VLMO_BF16 && !gp.g[0].k1, "vlmo_gemm_nt: tiles 106..110 / 309..320 are bf16, single-source");
@@ -1944,11 +1654,6 @@ int run_nt(int epi, int dtype, int tile, GemmNTGroups& gp, hipStream_t stream) {
             default: return launch_nt16<bf16, 20>(epi, gp, stream);
         }
     }
-    if (tile >= 908 && tile <= 909) {       // diagnostic: segment stamps of the 256-row kernel, schedule 0 / 1 (e.colpart = stamp buffer)
-        VLMO_CHECK_ARG(epi == EPI_BIAS, "vlmo_gemm_nt: the probe build has the bias epilogue only");
-        return tile == 908 ? launch_nt16<bf16, 16, 8, 1u>(epi, gp, stream) : launch_nt16<bf16, 16, 9, 1u>(epi, gp, stream);
-    }
-    if (tile == 208) return launch_nt16<bf16, 16, 0, 1u>(epi, gp, stream);     // measurement aid: schedule 0 (DMA issued in the MFMA segment), bias epilogue
     VLMO_CHECK_ARG(tile == 0 || tile == 3 || tile == 4 || tile == 8, "vlmo_gemm_nt: tile must be -1, 0, 3, 4, 8, 106..110 or 309..320 (got %d)", tile);
     if (tile == 4 && !(dtype == VLMO_BF16 && (epi == EPI_BIAS || epi == EPI_BIAS_GELU))) tile = 0;
     if (tile == 8 && !(dtype == VLMO_BF16 && (epi == EPI_BIAS || epi == EPI_BIAS_GELU || epi == EPI_RESID || epi == EPI_DGELU))) tile = 3;
@@ -1969,19 +1674,13 @@ int run_nt(int epi, int dtype, int tile, GemmNTGroups& gp, hipStream_t stream) {
     return launch_nt<bf16, 128, 128, 2, 2>(epi, gp, stream);
 }
 
-// Row-tiles per group of the L2 tile order.  VLMO_GROUP_M fixes it (measurement aid).  Else by the bytes of the weight
-// matrix: a group is group_m row panels against ALL column tiles, so group_m = 1 streams the whole weight once per row
+// Row-tiles per group of the L2 tile order, by the bytes of the weight matrix: a group is group_m row panels against ALL column tiles, so group_m = 1 streams the whole weight once per row
 // panel -- cheap while the weight is of the size of an XCD's L2 (4 MB), and then the activation panel is fetched once;
 // larger weights want their column tiles reused across several row panels.  In-step sweeps (tools/ab_multi.sh, weight
 // gradients on the main stream): VLMo-Base (weights <= 4.7 MB) group_m 1 / 2 / 3 / 4 = 14.34 / 14.36 / 14.38 / 14.43 ms;
 // VLMo-Large (2 - 8.4 MB) 24.88 against 24.79 at 4; the dVAE encoder (output convolution: 67 MB) 6.03 against 5.92 ms at 4.
 // (Under the side stream round 3 had measured 2 - 6 equal, 8 +0.1 ms, 16 +0.35 ms.)
 int group_m_for(int N, int K) {
-    static const int forced = [] {
-        const char* sv = getenv("VLMO_GROUP_M");
-        return sv ? atoi(sv) : 0;
-    }();
-    if (forced > 0) return forced;
     return (long)N * K * 2 <= 5l << 20 ? 1 : 4;
 }
 }  // namespace
@@ -2059,25 +1758,6 @@ TnPlan tn_plan(int M, int N1, int N2, int splits_req, int force_tile) {
 }
 }  // namespace
 
-namespace {
-// measurement aid: VLMO_TN_RING4=0 selects the two-buffer 64-token staging of the bf16 ping-pong weight-gradient kernels
-// measurement aid: VLMO_TN_MFMA16=1 runs the batched weight-gradient launch on v_mfma_f32_16x16x32 (default: see DESIGN.md)
-bool tn_mfma16() {
-    static const bool v = [] {
-        const char* e = getenv("VLMO_TN_MFMA16");
-        return e && e[0] == '1';
-    }();
-    return v;
-}
-bool tn_ring4() {
-    static const bool v = [] {
-        const char* e = getenv("VLMO_TN_RING4");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-}  // namespace
-
 extern "C" int64_t vlmo_gemm_tn_ws_bytes(int M, int N1, int N2) {
     const TnPlan a = tn_plan(M, N1, N2, 0, 0);
     return (int64_t)a.splits * N1 * N2 * 4;
@@ -2091,8 +1771,8 @@ extern "C" int vlmo_gemm_tn(int dtype, const void* A, int lda, const void* B, in
     VLMO_CHECK_ARG(N1 % 8 == 0 && N2 % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0, "vlmo_gemm_tn: N1,N2,lda,ldb must be multiples of 8");
     VLMO_CHECK_ARG(lda >= N1 && ldb >= N2 && ldc >= N2, "vlmo_gemm_tn: leading dimension too small");
     VLMO_CHECK_ARG(dtype == VLMO_BF16 || dtype == VLMO_F16, "vlmo_gemm_tn: dtype must be bf16 or f16");
+    VLMO_CHECK_ARG(splits < 3000, "vlmo_gemm_tn: splits must be below 3000 (got %d)", splits);
     int force = 0;
-    const bool probe = splits >= 3000;      // diagnostic: 3000 + s = the 256x256 kernel with segment stamps -> ws (C untouched)
     if (splits >= 1000) {      // test hook: 1000 + s forces 128x128 tiles, 2000 + s forces 256x256
         force = splits >= 2000 ? 256 : 128;
         splits %= 1000;
@@ -2105,38 +1785,17 @@ extern "C" int vlmo_gemm_tn(int dtype, const void* A, int lda, const void* B, in
     GemmTN p{A, B, C, M, N1, N2, lda, ldb, ldc, pl.per, pl.tiles, alpha, use_slab ? ws : nullptr, TN_ATOMIC};
     dim3 grid(pl.tiles * pl.splits);
     ProfScope prof(64 + (pl.big ? 8 : 0), 2.0 * M * N1 * N2, stream);
-    const bool r4 = tn_ring4();
-    if (probe) {
-        VLMO_CHECK_ARG(pl.big && ws && ws_bytes >= (int64_t)pl.tiles * pl.splits * 8 * 64 && dtype == VLMO_BF16, "vlmo_gemm_tn: probe needs the 256x256 plan, bf16 and a stamp buffer");
-        constexpr int LDS = 2 * 4 * 64 * 256;
-        static DeviceOnce pattr;
-        if (pattr.first()) {
-            (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<bf16, 256, 256, 2, 4, true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<bf16, 256, 256, 2, 4, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        }
-        GemmTN pp_ = p;
-        pp_.slab = ws;
-        if (r4)
-            hipLaunchKernelGGL((gemm_tn_kernel<bf16, 256, 256, 2, 4, true, true, true>), grid, dim3(512), LDS, stream, pp_);
-        else
-            hipLaunchKernelGGL((gemm_tn_kernel<bf16, 256, 256, 2, 4, true, true, false>), grid, dim3(512), LDS, stream, pp_);
-        VLMO_CHECK_LAUNCH("vlmo_gemm_tn(probe)");
-        return 0;
-    }
     if (pl.big) {
         constexpr int LDS = 2 * 4 * 64 * 256;
         static DeviceOnce attr;
         if (attr.first()) {
-            (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<bf16, 256, 256, 2, 4, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<bf16, 256, 256, 2, 4, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<f16, 256, 256, 2, 4, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+            (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<bf16, 256, 256, 2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+            (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<f16, 256, 256, 2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         }
         if (dtype == VLMO_F16)
-            hipLaunchKernelGGL((gemm_tn_kernel<f16, 256, 256, 2, 4, true, false, true>), grid, dim3(512), LDS, stream, p);
-        else if (r4)
-            hipLaunchKernelGGL((gemm_tn_kernel<bf16, 256, 256, 2, 4, true, false, true>), grid, dim3(512), LDS, stream, p);
+            hipLaunchKernelGGL((gemm_tn_kernel<f16, 256, 256, 2, 4, true>), grid, dim3(512), LDS, stream, p);
         else
-            hipLaunchKernelGGL((gemm_tn_kernel<bf16, 256, 256, 2, 4, true, false, false>), grid, dim3(512), LDS, stream, p);
+            hipLaunchKernelGGL((gemm_tn_kernel<bf16, 256, 256, 2, 4, true>), grid, dim3(512), LDS, stream, p);
     } else {
         if (dtype == VLMO_F16)
             hipLaunchKernelGGL((gemm_tn_kernel<f16, 128, 128, 2, 2>), grid, dim3(256), 65536, stream, p);
@@ -2162,10 +1821,8 @@ extern "C" int vlmo_gemm_tn_multi(int dtype, const VlmoTnProblem* probs, int n, 
     static DeviceOnce attr;
     if (attr.first()) {
         constexpr int LDS = 2 * 4 * 64 * 256;
-        (void)hipFuncSetAttribute((const void*)gemm_tn_multi_kernel<bf16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm_tn_multi_kernel<bf16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm_tn_multi_kernel<bf16, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm_tn_multi_kernel<f16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)gemm_tn_multi_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)gemm_tn_multi_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     }
     for (int q0 = 0, nq = 0; q0 < n; q0 += nq) {
         // one launch = as many of the remaining problems as fit the problem table and the placement table
@@ -2196,11 +1853,6 @@ extern "C" int vlmo_gemm_tn_multi(int dtype, const VlmoTnProblem* probs, int n, 
             if (splits > min_nk / 8) splits = min_nk / 8;
             if (splits < 1) splits = 1;
         }
-        static const int force_splits = [] {
-            const char* sv = getenv("VLMO_TN_SPLITS");      // measurement aid
-            return sv ? atoi(sv) : 0;
-        }();
-        if (force_splits > 0) splits = force_splits;
         GemmTNMulti mp{};
         mp.n = nq;
         struct Job {
@@ -2255,13 +1907,9 @@ extern "C" int vlmo_gemm_tn_multi(int dtype, const VlmoTnProblem* probs, int n, 
         ProfScope prof(73, flops, stream);
         constexpr int LDS = 2 * 4 * 64 * 256;
         if (dtype == VLMO_F16)
-            hipLaunchKernelGGL((gemm_tn_multi_kernel<f16, true>), dim3(t), dim3(512), LDS, stream, mp);
-        else if (tn_ring4() && tn_mfma16())
-            hipLaunchKernelGGL((gemm_tn_multi_kernel<bf16, true, true>), dim3(t), dim3(512), LDS, stream, mp);
-        else if (tn_ring4())
-            hipLaunchKernelGGL((gemm_tn_multi_kernel<bf16, true>), dim3(t), dim3(512), LDS, stream, mp);
+            hipLaunchKernelGGL((gemm_tn_multi_kernel<f16>), dim3(t), dim3(512), LDS, stream, mp);
         else
-            hipLaunchKernelGGL((gemm_tn_multi_kernel<bf16, false>), dim3(t), dim3(512), LDS, stream, mp);
+            hipLaunchKernelGGL((gemm_tn_multi_kernel<bf16>), dim3(t), dim3(512), LDS, stream, mp);
         VLMO_CHECK_LAUNCH("vlmo_gemm_tn_multi");
     }
     return 0;
@@ -2461,22 +2109,14 @@ extern "C" int vlmo_conv2d_nhwc(int epi, int dtype, const void* x, int B, int H,
     p.ngroups = 1;
     p.g[0] = GemmNT{x, w, B * H * W, Cout, K, Cin, K, *e, H, W, Cin, kw, zero_page, 8, nullptr, 0, 0, 1.f};
     ProfScope prof(32 + epi, 2.0 * B * H * W * Cout * K, stream);
-    static const bool shared_dx = [] {
-        const char* v = getenv("VLMO_CONV3_DX");        // A/B: 0 = the generic per-tap kernels
-        return !(v && v[0] == '0');
-    }();
     // wide bottlenecks whose 256 x 256 tiles fill most of one dispatch round (group 3 of the dVAE at 64 images: 196 tiles):
     // the ping-pong kernel with per-tap staging -- half the staged bytes per flop of the 128 x 128 tile
-    static const bool pp_conv = [] {
-        const char* v = getenv("VLMO_CONV_PP");
-        return !(v && v[0] == '0');
-    }();
-    if (dtype == VLMO_F16 && epi == EPI_BIAS && pp_conv && Cout % 256 == 0) {
+    if (dtype == VLMO_F16 && epi == EPI_BIAS && Cout % 256 == 0) {
         const long t256 = (long)((B * H * W + 255) / 256) * (Cout / 256);
         if (t256 >= 160 && (t256 <= 256 || t256 >= 640))
             return launch_nt<f16, 256, 256, 2, 4, true, 64, 2, true, (1u << EPI_BIAS)>(epi, p, stream);
     }
-    if (dtype == VLMO_F16 && epi == EPI_BIAS && kw == 3 && shared_dx && Cin % 32 == 0 && Cout % 8 == 0 && e->ldo % 8 == 0) {
+    if (dtype == VLMO_F16 && epi == EPI_BIAS && kw == 3 && Cin % 32 == 0 && Cout % 8 == 0 && e->ldo % 8 == 0) {
         if (Cout <= 64) return launch_conv3_dx<4, 1>(x, B, H, W, Cin, w, Cout, zero_page, e, stream);
         return launch_conv3_dx<2, 2>(x, B, H, W, Cin, w, Cout, zero_page, e, stream);
     }

@@ -150,7 +150,7 @@ class GradReducer:
             with torch.cuda.device(dev):
                 busy = [torch.cuda.current_stream(dev), engine._side_stream(dev)]
                 make = lambda: torch.cuda.Stream(device=dev)
-                self.comm_stream = engine.pick_stream(dev, make, busy) if engine.PROBE_STREAMS else make()
+                self.comm_stream = engine.pick_stream(dev, make, busy)
         if self.comm_mode == 'native':
             if not self.on_gpu:
                 raise RuntimeError("comm='native' is the RCCL communicator of the HIP library: GPU parameters only")

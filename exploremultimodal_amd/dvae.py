@@ -22,7 +22,6 @@ import torch.nn as nn
 from . import hip
 
 logit_laplace_eps = 0.1
-OUTPUT_FP16_WEIGHTS = os.environ.get('VLMO_DVAE_OUTPUT_FP16', '0') == '1'
 # measurement switch: 0 = the output convolution as one launch whatever its last dispatch round looks like
 OUTPUT_ROW_SPLIT = os.environ.get('VLMO_DVAE_OUT_SPLIT', '1') != '0'
 
@@ -62,11 +61,6 @@ class Conv2d(nn.Module):
             lo = (w - hi.float()).to(torch.float16)
             self._shadow = (ver, torch.cat([hi, lo], 1).contiguous(), self.b.detach().float().contiguous())
         return self._shadow[1], self._shadow[2]
-
-    def shadow_fp16(self):
-        """the split shadow's high half alone: fp16(w) [n_out, n_in] (VLMO_DVAE_OUTPUT_FP16=1, a measurement switch)"""
-        w, b = self.shadow_split()
-        return w[:, :w.shape[1] // 2].contiguous(), b
 
     def shadow(self):
         """fp16 weight in the engine's layout [n_out, kw*kw*n_in] (tap-major, channel-minor; the 3-channel
@@ -241,16 +235,10 @@ class Encoder(nn.Module):
         M, C = rel.shape
         nchunk = (self.vocab_size + 63) // 64
         part = torch.empty((M, nchunk, 2), dtype=torch.float32, device=x.device)
-        if OUTPUT_FP16_WEIGHTS:
-            # measurement switch, NOT the default: the output convolution's weight rounded to fp16 (half the MFMA work;
-            # logits move by ~2e-4, two orders below the noise of the fp16 activations that feed them)
-            w16, bo = self.blocks.output.conv.shadow_fp16()
-            hip.gemm_nt(hip.EPI_ARGMAX, rel, w16, M, self.vocab_size, C, part, bias=bo, ldo=nchunk)
-        else:
-            wo, bo = self.blocks.output.conv.shadow_split()
-            for r0, r1, tile in self._row_parts(M, self.vocab_size):
-                hip.gemm_nt(hip.EPI_ARGMAX, rel[r0:r1], wo, r1 - r0, self.vocab_size, 2 * C, part[r0:r1], bias=bo,
-                            ldo=nchunk, A2=rel[r0:r1], k1=C, tile=tile)
+        wo, bo = self.blocks.output.conv.shadow_split()
+        for r0, r1, tile in self._row_parts(M, self.vocab_size):
+            hip.gemm_nt(hip.EPI_ARGMAX, rel[r0:r1], wo, r1 - r0, self.vocab_size, 2 * C, part[r0:r1], bias=bo,
+                        ldo=nchunk, A2=rel[r0:r1], k1=C, tile=tile)
         ids = torch.empty((M,), dtype=torch.int64, device=x.device)
         hip.argmax_reduce(part, nchunk, ids, M)
         return ids.view(B, h, w)

@@ -40,9 +40,6 @@ def _use_side_stream(sink, rows):
     if OVERLAP_WGRAD is not None:
         return OVERLAP_WGRAD
     return sink is not None or rows < ONE_STREAM_ROWS
-SIDE_MODE = _os.environ.get('VLMO_SIDE_STREAM', 'low')
-PROBE_STREAMS = _os.environ.get('VLMO_PROBE_STREAMS', '1') != '0'
-MERGE_SEPARATE_ATTENTION = _os.environ.get('VLMO_MERGE_ATTN', '1') != '0'
 DEFAULT_TILE = -1        # GEMM tile: -1 = chosen per shape by the library (see vlmo_gemm_nt)
 
 
@@ -170,7 +167,7 @@ class Plan:
     def attn_launches(self, fused):
         if fused and self.seg_vl is not None:
             return [(self.seg_vl, self.B, self.T + self.P)]
-        if self.seg_sep is not None and MERGE_SEPARATE_ATTENTION:
+        if self.seg_sep is not None:
             return [(self.seg_sep, 2 * self.B, max(self.T, self.P))]
         out = []
         if self.seg_txt is not None:
@@ -207,18 +204,12 @@ _SIDE = {}
 
 def _side_stream(dev):
     """The weight-gradient stream of a device: lowest dispatch priority, so the activation-gradient chain
-    on the caller's stream (the critical path) wins every freed compute-unit slot.  VLMO_SIDE_STREAM=
-    'low' (default) | 'normal' | 'cumask:<hex words, comma separated>' (measurement aid)."""
+    on the caller's stream (the critical path) wins every freed compute-unit slot."""
     s = _SIDE.get(dev)
     if s is None:
-        def make():
-            if SIDE_MODE.startswith('cumask:'):
-                raw = hip.side_stream_create(False, [int(w, 16) for w in SIDE_MODE[7:].split(',')])
-            else:
-                raw = hip.side_stream_create(SIDE_MODE != 'normal')
-            return torch.cuda.ExternalStream(raw, device=dev)
+        make = lambda: torch.cuda.ExternalStream(hip.side_stream_create(True), device=dev)
         with torch.cuda.device(dev):
-            s = pick_stream(dev, make, [torch.cuda.current_stream(dev)]) if PROBE_STREAMS else make()
+            s = pick_stream(dev, make, [torch.cuda.current_stream(dev)])
         _SIDE[dev] = s
     return s
 
@@ -553,9 +544,8 @@ def wgrad_batch_for(d, hid, cus=256, max_batch=4):
         if best_cost is None or cost < best_cost - 1e-9:
             best, best_cost = b, cost
     return best
-TMP_SETS = int(_os.environ.get('VLMO_TMP_SETS', '4'))            # rotation depth of the backward temporaries
+TMP_SETS = 4                                                     # rotation depth of the backward temporaries
 USE_STACK = _os.environ.get('VLMO_STACK', '1') != '0'            # one native call per pass (else one per block)
-WGRAD_STORE = _os.environ.get('VLMO_WGRAD_STORE', '1') != '0'    # weight-gradient matrices written, not zero-filled + accumulated
 
 _PERSIST = {}
 
@@ -857,7 +847,7 @@ class StackFn(torch.autograd.Function):
             permit = _TASK_FLATS['groups']
         grads_all = [None] * len(params)
         goff = 0
-        store_ok, acquired = WGRAD_STORE, []      # (flat, fresh, is_expert) of every gradient bucket of the pass
+        store_ok, acquired = True, []       # (flat, fresh, is_expert) of every gradient bucket of the pass
         for k in range(nb):                 # backward order: k-th processed block is i = nb-1-k
             i = nb - 1 - k
             D = descs[i]
@@ -897,7 +887,7 @@ class StackFn(torch.autograd.Function):
                 for gi, (gp_, gn_) in enumerate(groups):
                     if flats[gi] is None:
                         if whole is None:
-                            whole = torch.empty(tot, dtype=f32, device=dev) if WGRAD_STORE else torch.zeros(tot, dtype=f32, device=dev)
+                            whole = torch.empty(tot, dtype=f32, device=dev)
                         flats[gi] = whole[goff:goff + gn_]
                         lo = 0 if gi == 0 else 11 + 4 * (gi - 1)
                         if (reg is not None and _group_key(gp_) in permit
@@ -936,7 +926,7 @@ class StackFn(torch.autograd.Function):
             torch._foreach_zero_(vecs)
         else:
             for f_, fr, _ in acquired:
-                if fr and (sink is not None or WGRAD_STORE):
+                if fr:
                     f_.zero_()
         S = hip.StackDesc()
         S.n_blocks, S.wgrad_batch, S.n_tmp_sets, S.wgrad_store = nb, batch, nsets, int(store_ok)

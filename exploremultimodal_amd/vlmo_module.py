@@ -10,7 +10,6 @@ from collections import defaultdict
 from functools import partial
 
 import numpy as np
-import os
 
 import torch
 import torch.nn as nn
@@ -227,7 +226,7 @@ class VlmoModule(nn.Module):
         # text-only pass of B sequences alone is ~300 launches of 2 048-row kernels; riding with the 2B images it costs its rows.
         # Pairs: (ITC image_i, text_i), (MIM masked image_i, text_i again -- its text half is discarded, no gradient enters it).
         unfused = ('itc' in names and 'mim' in names and self.transformer_m is None
-                   and getattr(self.config.train, 'merge_unfused', os.environ.get('VLMO_MERGE_UNFUSED', '1') != '0'))
+                   and getattr(self.config.train, 'merge_unfused', True))
         if unfused:
             tr = self.transformer
             T, depth = tr.max_text_len, len(tr.blocks)

@@ -400,10 +400,9 @@ def test_attention_mixed_lengths_in_one_launch():
 
 def test_attention_backward_nine_tile_sequences_in_a_mixed_launch():
     """One launch with sequences on both sides of the 256-token boundary between the single-pass and the two-phase
-    backward (257 .. 288 tokens take the latter; with VLMO_ATTN_BWD_SPLIT=1 two launches: the tile pairs that touch the
-    ninth tile in the two-phase kernel, the rest in the single-pass kernel, which adds the first launch's partial rows),
-    a packed two-range sequence, key masks that cover a whole fringe, dropout: dq / dk / dv of every row and the
-    per-sequence column sums against the fp32 reference with the replicated mask."""
+    backward (a launch of 257 .. 288 tokens takes the latter for every sequence), a packed two-range sequence, key
+    masks that cover a whole ninth tile, dropout: dq / dk / dv of every row and the per-sequence column sums against
+    the fp32 reference with the replicated mask."""
     heads = 2
     d = heads * 64
     lens = [270, 200, 257, 64, 288, 256]

@@ -130,27 +130,3 @@ def test_gemm_nt16_fragments():
                 k0 = 32 * kh + 8 * (l >> 4)
                 np.testing.assert_array_equal(got[l], ids[row_base + (l & 15), k0:k0 + 8])
             assert S.b128_conflicts(addrs) == 1
-
-
-def test_gemm_tn16_fragments():
-    ids = _ids(64, 128)
-    lds = S.Lds(64 * 256)
-    for instr in range(16):
-        src = []
-        for lane in range(64):
-            r, ch = S.tn_stage_src(instr, lane)
-            src.append(ids[r, ch * 8:ch * 8 + 8])
-        lds.dma16(instr * 1024, src)
-    worst = 1
-    for ncol_base in range(0, 128, 16):
-        for ks in range(2):
-            for half in range(2):
-                addrs = [S.tn16_tr_addr(ncol_base, ks, half, l) for l in range(64)]
-                got = lds.read_tr(addrs)
-                for l in range(64):
-                    n = ncol_base + (l & 15)
-                    m0 = 32 * ks + 8 * (l >> 4) + 4 * half
-                    np.testing.assert_array_equal(got[l], ids[m0:m0 + 4, n])
-                worst = max(worst, S.tr_conflicts(addrs))
-    assert worst == 1
-

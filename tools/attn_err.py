@@ -1,5 +1,5 @@
 """Forward attention error against an fp64 soft-max on the same bf16 inputs (no dropout).
-python tools/attn_err.py   (VLMO_ATTN_FWD=chunked selects the chunked kernel)"""
+python tools/attn_err.py   (these lengths take attn_fwd1_kernel; VLMO_HIP_LIB compares another build)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,5 +1,5 @@
 """Micro-benchmark of vlmo_gemm_tn_multi on the weight gradients of `nblk` VLMo-Base blocks (random data).
-VLMO_TN_SPLITS=n forces the token-dimension split.  usage: python tools/tn_multi_bench.py [nblk] [M]"""
+usage: python tools/tn_multi_bench.py [nblk] [M]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -29,4 +29,4 @@ for _ in range(reps):
 b.record()
 torch.cuda.synchronize()
 t = a.elapsed_time(b) / reps * 1e-3
-print(f'tn_multi nblk={nblk} M={M} splits={os.environ.get("VLMO_TN_SPLITS", "auto")}: {t*1e6:8.1f} us  {fl/t/1e12:7.1f} TF/s', flush=True)
+print(f'tn_multi nblk={nblk} M={M}: {t*1e6:8.1f} us  {fl/t/1e12:7.1f} TF/s', flush=True)

@@ -31,4 +31,4 @@ for name, nsets in (('one operand set (Infinity-Cache resident)', 1), (f'{NSETS}
     t = timeit(lambda i: hip.gemm_tn(sets[i % nsets][0], sets[i % nsets][1], C, M, N1, N2))
     print(f'old split+slab  {name}: {t*1e6:7.1f} us {fl/t/1e12:7.1f} TF/s', flush=True)
     t = timeit(lambda i: hip.gemm_tn_multi([(sets[i % nsets][0], sets[i % nsets][1], C, M, N1, N2, True)]))
-    print(f'tn_multi splits={os.environ.get("VLMO_TN_SPLITS","auto")} {name}: {t*1e6:7.1f} us {fl/t/1e12:7.1f} TF/s', flush=True)
+    print(f'tn_multi {name}: {t*1e6:7.1f} us {fl/t/1e12:7.1f} TF/s', flush=True)
