@@ -1,6 +1,6 @@
-// One VLMo Block forward / backward per C-ABI call (vlmo.py:187-197): native orchestration
-// of the kernels in gemm.hip / attention.hip / layernorm.hip / elementwise.hip, so the Python
-// host issues one FFI call per block and stays far ahead of the GPU.
+// The VLMo Blocks (vlmo.py:187-197) of one backbone pass forward / backward per C-ABI call: native
+// orchestration of the kernels in gemm.hip / attention.hip / layernorm.hip / elementwise.hip, so the
+// Python host issues one FFI call per pass and stays far ahead of the GPU.
 #include "common.h"
 #include "vlmo_hip.h"
 #include <algorithm>
@@ -13,10 +13,10 @@ namespace {
 constexpr int GELU_DERIV = 4;
 
 
-// fork / join events of the calling thread, one set per device (a process may drive several GPUs)
+// vlmo_stack_bwd's fork / done event per deferred batch, of the calling thread, one pool per device (a process
+// may drive several GPUs)
 struct Events {
-    hipEvent_t fork = nullptr, join = nullptr;
-    std::vector<hipEvent_t> pool;      // vlmo_stack_bwd: fork / done event per deferred batch
+    std::vector<hipEvent_t> pool;
     hipEvent_t get(size_t i) {
         while (pool.size() <= i) {
             hipEvent_t e = nullptr;
@@ -30,12 +30,7 @@ Events& events() {
     static thread_local std::map<int, Events> per_device;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    Events& e = per_device[dev];
-    if (!e.fork) {
-        (void)hipEventCreateWithFlags(&e.fork, hipEventDisableTiming);
-        (void)hipEventCreateWithFlags(&e.join, hipEventDisableTiming);
-    }
-    return e;
+    return per_device[dev];
 }
 
 inline const char* bp(const void* p, size_t row, size_t ld, size_t esz) { return (const char*)p + row * ld * esz; }
@@ -56,11 +51,10 @@ VlmoEpilogue epi() {
     return e;
 }
 
-}  // namespace
-
-extern "C" int vlmo_block_fwd(const VlmoBlockDesc* b, hipStream_t st) {
-    VLMO_CHECK_ARG(b && b->x && b->x1 && b->x2, "vlmo_block_fwd: null descriptor/buffers");
-    VLMO_CHECK_ARG(b->n_experts >= 1 && b->n_experts <= 2 && b->n_attn >= 1 && b->n_attn <= 2, "vlmo_block_fwd: bad counts");
+// forward of one block on `st` (vlmo_stack_fwd runs it per block)
+int block_fwd(const VlmoBlockDesc* b, hipStream_t st) {
+    VLMO_CHECK_ARG(b && b->x && b->x1 && b->x2, "vlmo_stack_fwd: null block buffers");
+    VLMO_CHECK_ARG(b->n_experts >= 1 && b->n_experts <= 2 && b->n_attn >= 1 && b->n_attn <= 2, "vlmo_stack_fwd: bad counts");
     const int M = b->M, d = b->d, hid = b->hidden;
     TRY(vlmo_ln_fwd(b->x, b->n1w, b->n1b, b->y1, 0, b->mean1, b->rstd1, nullptr, M, d, b->eps, st));
     {
@@ -132,6 +126,8 @@ extern "C" int vlmo_block_fwd(const VlmoBlockDesc* b, hipStream_t st) {
     return 0;
 }
 
+}  // namespace
+
 extern "C" int vlmo_side_stream_create(int low_priority, const uint32_t* cu_mask, int cu_mask_words, hipStream_t* out) {
     VLMO_CHECK_ARG(out, "vlmo_side_stream_create: null out");
     hipError_t rc;
@@ -148,109 +144,6 @@ extern "C" int vlmo_side_stream_create(int low_priority, const uint32_t* cu_mask
     }
     return 0;
 }
-
-extern "C" int vlmo_block_bwd(const VlmoBlockDesc* b, hipStream_t st) {
-    VLMO_CHECK_ARG(b && b->dx2 && b->dx1 && b->dx0, "vlmo_block_bwd: null descriptor/buffers");
-    const int M = b->M, d = b->d, hid = b->hidden;
-    hipStream_t side = b->side_stream ? b->side_stream : st;
-    float* ws_side = b->side_stream ? b->ws_side : b->ws_main;
-    Events& ev = events();
-    auto fork = [&]() {     // side stream may read everything enqueued on the main stream so far
-        if (side != st) {
-            (void)hipEventRecord(ev.fork, st);
-            (void)hipStreamWaitEvent(side, ev.fork, 0);
-        }
-    };
-    // The column folds of the LayerNorm / LayerScale / bias gradients are deferred to the side stream (after
-    // the next fork) when the workspace has a slot per producer; else they run in place on the main stream.
-    const int64_t slot = reduce_ws_need(2 * d);
-    const bool defer = side != st && b->ws_bytes >= (int64_t)(3 + b->n_experts) * slot;
-    auto ws_slot = [&](int k) { return defer ? (float*)((char*)b->ws_main + k * slot) : b->ws_main; };
-    PartialReduce pend[6];
-    auto arm = [&](int k) { vlmo_defer_reduce = defer ? &pend[k] : nullptr; };
-    // ---- FFN half: per-expert residual-branch backward, then the two dgrad GEMMs of ALL experts as grouped
-    // launches on the main stream and every expert's weight gradients on the side stream
-    VLMO_CHECK_ARG(b->n_experts >= 1 && b->n_experts <= 2, "vlmo_block_bwd: 1..2 experts per block");
-    const void *ag[4], *wg[4], *af[4], *wf[4];
-    int32_t rows[4];
-    VlmoEpilogue eg[4], ef[4];
-    for (int x = 0; x < b->n_experts; ++x) {
-        const size_t r0 = b->exp_row0[x];
-        const int n = rows[x] = b->exp_rows[x];
-        arm(2 + x);
-        TRY(vlmo_resid_bwd(b->dx2 + r0 * d, bp(b->zd2, r0, d, 2), b->g2,
-                           b->row_index ? b->rs2 : (b->rs2 ? b->rs2 + r0 : nullptr),
-                           b->row_index ? b->row_index + r0 : nullptr, bp(b->dz2, r0, d, 2), b->dg2, b->db2[x], n, d, b->drop_thresh, b->inv_keep,
-                           b->seed + 21 + 2 * x, ws_slot(2 + x), slot, st));
-        vlmo_defer_reduce = nullptr;
-        ag[x] = bp(b->dz2, r0, d, 2);
-        wg[x] = b->w2T[x];
-        VlmoEpilogue& e = eg[x] = epi();
-        e.out = bp(b->du, r0, hid, 2);
-        e.ldo = hid;
-        e.aux = bp(b->u, r0, hid, 2);
-        e.ld2 = hid;
-        e.drop_thresh = b->drop_thresh;
-        e.inv_keep = b->inv_keep;
-        e.seed = b->seed + 20 + 2 * x;
-        e.relu = GELU_DERIV;
-        af[x] = bp(b->du, r0, hid, 2);
-        wf[x] = b->w1T[x];
-        VlmoEpilogue& f = ef[x] = epi();
-        f.out = bp(b->dy2, r0, d, 2);
-        f.ldo = d;
-    }
-    TRY(vlmo_gemm_nt_grouped(VLMO_EPI_DGELU, VLMO_BF16, b->tile, b->n_experts, ag, d, wg, d, rows, hid, d, eg, st));
-    fork();
-    for (int x = 0; x < b->n_experts; ++x) {
-        const size_t r0 = b->exp_row0[x];
-        const int n = b->exp_rows[x];
-        TRY(reduce_partials(pend[2 + x], side));
-        TRY(vlmo_gemm_tn(VLMO_BF16, bp(b->dz2, r0, d, 2), d, bp(b->h, r0, hid, 2), hid, b->dw2[x], hid, n, d, hid, 1.f, 0, b->ws_tn, b->ws_tn_bytes, side));
-        TRY(vlmo_colsum(VLMO_BF16, bp(b->du, r0, hid, 2), hid, b->db1[x], n, hid, ws_side, b->ws_bytes, side));
-        TRY(vlmo_gemm_tn(VLMO_BF16, bp(b->du, r0, hid, 2), hid, bp(b->y2, r0, d, 2), d, b->dw1[x], d, n, hid, d, 1.f, 0, b->ws_tn, b->ws_tn_bytes, side));
-    }
-    TRY(vlmo_gemm_nt_grouped(VLMO_EPI_BIAS, VLMO_BF16, b->tile, b->n_experts, af, hid, wf, hid, rows, d, hid, ef, st));
-    // norm2 backward fused with the attention branch's residual backward (it consumes the dx1 this writes):
-    // four column partials (dn2w, dn2b, dgamma_1, dproj_b) in slots 0-1
-    arm(0);
-    TRY(vlmo_ln_resid_bwd(b->dy2, b->x1, b->n2w, b->mean2, b->rstd2, b->dx2, b->dx1, b->dn2w, b->dn2b, b->zd1, b->g1,
-                          b->rs1, b->row_index, b->dz1, b->dg1, b->dproj_b, b->drop_thresh, b->inv_keep, b->seed + 1, M, d,
-                          ws_slot(0), 2 * slot, st));
-    vlmo_defer_reduce = nullptr;
-    {
-        VlmoEpilogue e = epi();
-        e.out = b->dctx;
-        e.ldo = d;
-        TRY(vlmo_gemm_nt(VLMO_EPI_BIAS, VLMO_BF16, b->tile, b->dz1, d, b->proj_wT, d, M, d, d, &e, st));
-    }
-    const float scale = 1.0f / sqrtf((float)(d / b->heads));
-    for (int a = 0; a < b->n_attn; ++a)
-        TRY(vlmo_attn_bwd(b->qkv, b->ctx, b->dctx, b->lse[a], b->lse_stride[a], b->seg[a], b->nseq[a], b->keymask,
-                          b->dqkv, nullptr, b->heads, d, b->maxlen[a], scale, b->attn_drop_thresh, b->attn_inv_keep,
-                          b->seed + 11 + b->attn_seed_idx[a], b->attn_seq0[a], st));
-    fork();     // one fork for the whole attention half: the proj gradient waits for it too (the side stream has slack)
-    TRY(reduce_partials(pend[0], side));
-    TRY(vlmo_gemm_tn(VLMO_BF16, b->dz1, d, b->ctx, d, b->dproj_w, d, M, d, d, 1.f, 0, b->ws_tn, b->ws_tn_bytes, side));
-    TRY(vlmo_colsum(VLMO_BF16, b->dqkv, 3 * d, b->dqkv_b, M, 3 * d, ws_side, b->ws_bytes, side));
-    TRY(vlmo_gemm_tn(VLMO_BF16, b->dqkv, 3 * d, b->y1, d, b->dqkv_w, d, M, 3 * d, d, 1.f, 0, b->ws_tn, b->ws_tn_bytes, side));
-    {
-        VlmoEpilogue e = epi();
-        e.out = b->dy1;
-        e.ldo = d;
-        TRY(vlmo_gemm_nt(VLMO_EPI_BIAS, VLMO_BF16, b->tile, b->dqkv, 3 * d, b->qkv_wT, 3 * d, M, d, 3 * d, &e, st));
-    }
-    // the last fold stays on the main stream (a fork for it would cost what it saves); its own slot: the
-    // side stream may still be reading slot 0
-    TRY(vlmo_ln_bwd(b->dy1, 0, nullptr, b->x, b->n1w, b->mean1, b->rstd1, b->dx1, b->dx0, b->dn1w, b->dn1b, M, d,
-                    ws_slot(2 + b->n_experts), slot, st));
-    if (side != st) {       // join: gradients complete, every buffer the side stream read is reusable
-        (void)hipEventRecord(ev.join, side);
-        (void)hipStreamWaitEvent(st, ev.join, 0);
-    }
-    return 0;
-}
-
 
 // ================================================================ whole block stacks in one call
 // vlmo_stack_fwd / vlmo_stack_bwd run the blocks of one backbone pass (vlmo.py:402-411) from native code:
@@ -462,7 +355,7 @@ int block_dgrad_chain(const VlmoBlockDesc* b, hipStream_t st, Deferred& D, const
 extern "C" int vlmo_stack_fwd(const VlmoStackDesc* s, hipStream_t st) {
     VLMO_CHECK_ARG(s && s->blocks && s->n_blocks >= 1, "vlmo_stack_fwd: empty stack");
     for (int i = 0; i < s->n_blocks; ++i)
-        if (int rc = vlmo_block_fwd(&s->blocks[i], st)) return rc;
+        if (int rc = block_fwd(&s->blocks[i], st)) return rc;
     return 0;
 }
 

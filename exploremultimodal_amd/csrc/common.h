@@ -59,9 +59,9 @@ struct DeviceOnce {
 #define VLMO_MAX_PARTIAL_BLOCKS 512
 int reduce_partials(const float* ws, int nblk, int ncols, float* out0, int n0, float* out1, hipStream_t stream,
                     float* out2 = nullptr, float* out3 = nullptr);
-// vlmo_block_bwd runs these tiny folds on its side stream (they only produce parameter gradients; on the
-// caller's stream each one is a launch + dependency bubble on the critical path): while `vlmo_defer_reduce`
-// points at a record, the NEXT reduce_partials() of this thread fills it instead of launching.
+// vlmo_stack_bwd defers these tiny folds into its batched column launches (they only produce parameter gradients;
+// launched one by one on the caller's stream, each is a launch + dependency bubble on the critical path): while
+// `vlmo_defer_reduce` points at a record, the NEXT reduce_partials() of this thread fills it instead of launching.
 struct PartialReduce {
     const float* ws = nullptr;
     int nblk = 0, ncols = 0;
@@ -72,9 +72,6 @@ struct PartialReduce {
     float* out3 = nullptr;
 };
 extern thread_local PartialReduce* vlmo_defer_reduce;
-inline int reduce_partials(const PartialReduce& r, hipStream_t stream) {
-    return r.ws ? reduce_partials(r.ws, r.nblk, r.ncols, r.out0, r.n0, r.out1, stream, r.out2, r.out3) : 0;
-}
 // layernorm.hip: LayerNorm backward fused with the residual-branch backward of the block below (see there)
 int ln_resid_seg_bwd(const void* dy, const float* x, const float* w, const float* mean, const float* rstd,
                      const float* dres, float* dx, float* dw, float* db, const void* zd, const float* gamma,

@@ -24,7 +24,7 @@ Design (MI355X-first):
 `bucket.shard`; the full gradient is then NOT written back.
 
 Transformer blocks of the HIP engine skip the pack step altogether: while a reducer
-is attached (engine.GRAD_SINK), BlockFn.backward accumulates its weight gradients
+is attached (engine.GRAD_SINK), StackFn.backward accumulates its weight gradients
 straight into a persistent flat fp32 buffer owned by the reducer ("sink bucket"),
 p.grad are views of it, and the whole buffer is cast to bf16 and all-reduced as soon
 as the last backward call that contributes to it in this step has been enqueued.
@@ -493,7 +493,7 @@ class GradReducer:
         self._pending_expect = {k: c for k, c in counts.items() if k not in self.sinks}
         self._armed = True
 
-    # ---- engine sink protocol (called from engine.BlockFn) -------------------------------------------
+    # ---- engine sink protocol (called from engine.StackFn) -------------------------------------------
     @staticmethod
     def _key(group):
         return tuple(id(p) for p in group)

@@ -292,7 +292,8 @@ class _Fork:
 
 def _fill_forward(D, meta, params, launches, lse_sizes, M, pb, pf, need_bwd, keep):
     """Forward part of a VlmoBlockDesc: geometry, parameters (fp32 vectors, bf16 weight shadows) and the saved-
-    activation slabs at pb (bf16) / pf (fp32).  params in BlockFn's order; x / x2 are set by the caller."""
+    activation slabs at pb (bf16) / pf (fp32).  params in per-block order (vlmo.Block._params); x / x2 are set by the
+    caller."""
     (g1, g2, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b) = params[:11]
     nexp = len(meta.expert_ranges)
     pl, d, H, hid = meta.plan, meta.d, meta.heads, meta.hidden
@@ -381,7 +382,7 @@ def _carve(flat, shapes):
 
 def shared_layout(params, d):
     """[(parameter, offset)] of a block's shared-parameter group inside its flat gradient bucket (the carve order of
-    _fill_grads; params in BlockFn's order).  q_bias / v_bias sit at the two ends of the 3d-wide qkv-bias slot."""
+    _fill_grads; params in per-block order).  q_bias / v_bias sit at the two ends of the 3d-wide qkv-bias slot."""
     (g1, g2, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b) = params[:11]
     o = 6 * d
     out = [(g1, 0), (g2, d), (n1w, 2 * d), (n1b, 3 * d), (n2w, 4 * d), (n2b, 5 * d), (qkv_w, o)]
@@ -401,7 +402,7 @@ def expert_layout(params, d, hid):
 
 def _fill_grads(D, flats, d, hid, nexp):
     """Parameter-gradient pointers of a VlmoBlockDesc from flat fp32 storage (flats[0]: shared parameters,
-    flats[1 + e]: expert e) -> gradient tensors in BlockFn's parameter order."""
+    flats[1 + e]: expert e) -> gradient tensors in per-block parameter order."""
     (dg1, dg2, dn1w, dn1b, dn2w, dn2b, dqkv_w, dproj_w, dproj_b, dqkv_b) = _carve(
         flats[0], [(d,)] * 6 + [(3 * d, d), (d, d), (d,), (3 * d,)])
     D.dg1, D.dg2, D.dn1w, D.dn1b, D.dn2w, D.dn2b = (t.data_ptr() for t in (dg1, dg2, dn1w, dn1b, dn2w, dn2b))
@@ -417,111 +418,7 @@ def _fill_grads(D, flats, d, hid, nexp):
 def _released(ctx_field):
     if ctx_field is None:
         raise RuntimeError('Trying to backward through an engine pass a second time: its saved activations were released '
-                           'by the first backward (retain_graph=True is not supported by engine.StackFn / BlockFn)')
-
-
-class BlockFn(torch.autograd.Function):
-    """One VLMo Block (vlmo.py:187-197) = norm1 -> qkv -> attention -> proj(+gamma_1, residual) -> norm2 ->
-    expert FFN(+gamma_2, residual), forward and backward each ONE native call (vlmo_block_fwd / vlmo_block_bwd).
-    params order: gamma_1, gamma_2, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b,
-    then (fc1_w, fc1_b, fc2_w, fc2_b) per expert range."""
-
-    @staticmethod
-    def forward(ctx, x, meta, *params):
-        nexp = len(meta.expert_ranges)
-        experts = [params[11 + 4 * i: 15 + 4 * i] for i in range(nexp)]
-        pl, d, H = meta.plan, meta.d, meta.heads
-        M, dev = x.shape[0], x.device
-        need_bwd = any(ctx.needs_input_grad)   # grad mode is off inside forward; this reflects the caller's
-        x = x.contiguous()
-        launches = pl.attn_launches(meta.fused)
-        lse_sizes = [nseq * H * (((ml + 31) // 32) * 32) for _, nseq, ml in launches]
-        # one bf16 slab: y1 | qkv(3) | ctx | zd1 | y2 | u(4) | h(4) | zd2  (units of M*d) ; one fp32 slab
-        sb = torch.empty(16 * M * d, dtype=torch.bfloat16, device=dev)
-        sf = torch.empty(M * d + 4 * M + sum(lse_sizes), dtype=torch.float32, device=dev)
-        x2 = torch.empty((M, d), dtype=torch.float32, device=dev)
-        D = hip.BlockDesc()
-        keep = [sb, sf, pl]
-        _fill_forward(D, meta, params, launches, lse_sizes, M, sb.data_ptr(), sf.data_ptr(), need_bwd, keep)
-        D.x, D.x2 = x.data_ptr(), x2.data_ptr()
-        hip.block_fwd(D)
-        if need_bwd:
-            ctx.meta, ctx.desc, ctx.keep = meta, D, keep
-            ctx.save_for_backward(x, *params)
-            ctx.sink = GRAD_SINK
-            if ctx.sink is not None:
-                # one bucket for the block's shared parameters, one per expert used by this call
-                ctx.sink_groups = [tuple(params[:11])] + [tuple(e) for e in experts]
-                for g_ in ctx.sink_groups:
-                    ctx.sink.expect(g_)
-        return x2
-
-    @staticmethod
-    def backward(ctx, dx2):
-        meta, D = ctx.meta, ctx.desc
-        _released(D)
-        x, *params = ctx.saved_tensors
-        nexp = len(meta.expert_ranges)
-        d, hid = meta.d, meta.hidden
-        M, dev = x.shape[0], x.device
-        f32 = torch.float32
-        dx2 = dx2.contiguous()
-        # every parameter gradient of this block lives in ONE zero-filled flat buffer (one memset)
-        sink = ctx.sink
-        shared_n = 6 * d + 3 * d * d + d * d + d + 3 * d
-        exp_n = 2 * hid * d + hid + d
-        if sink is not None:    # data-parallel run: accumulate straight into the reducer's persistent flat buckets
-            akey, aroom = id(params[0]), shared_n + 3 * exp_n       # one arena per block: shared + up to 3 experts
-            flats = [sink.acquire(ctx.sink_groups[0], shared_n, dev, akey, aroom,
-                                  layout=shared_layout(ctx.sink_groups[0], d))] + \
-                    [sink.acquire(g_, exp_n, dev, akey, aroom, layout=expert_layout(g_, d, hid))
-                     for g_ in ctx.sink_groups[1:]]
-        else:                   # ONE zero-filled flat buffer (one memset) carved into all gradients of the block
-            # (fresh gradients: to inplace_passes() a BlockFn node is a foreign producer, so no StackFn node of this
-            # backward adds into a buffer of these groups)
-            whole = torch.zeros(shared_n + nexp * exp_n, dtype=f32, device=dev)
-            flats = [whole[:shared_n]] + [whole[shared_n + i * exp_n: shared_n + (i + 1) * exp_n] for i in range(nexp)]
-
-        grads = _fill_grads(D, flats, d, hid, nexp)
-        _split_backward_attention(D, meta)
-        # temporaries: dz2 | du(4) | dy2(=dctx) | dz1 | dqkv(3) | dy1  bf16 ; dx1, dx0 fp32
-        tb = torch.empty(11 * M * d, dtype=torch.bfloat16, device=dev)
-        dx1 = torch.empty((M, d), dtype=f32, device=dev)
-        dx0 = torch.empty((M, d), dtype=f32, device=dev)
-        pb, md2 = tb.data_ptr(), M * d * 2
-        D.dz2, D.du, D.dy2, D.dz1, D.dqkv, D.dy1 = pb, pb + md2, pb + 5 * md2, pb + 6 * md2, pb + 7 * md2, pb + 10 * md2
-        D.dctx = D.dy2      # dy2 is consumed by ln_bwd on the main stream before dctx is written; never read on the side
-        D.dx2, D.dx1, D.dx0 = dx2.data_ptr(), dx1.data_ptr(), dx0.data_ptr()
-        # column-partial workspace: one 2d-wide slot per deferred fold of vlmo_block_bwd (3 + experts of them)
-        ncols = max(3 * d, hid, 2 * d * (3 + len(meta.expert_ranges)))
-        ws_main = hip.workspace(dev, ncols)
-        D.ws_main, D.ws_bytes = ws_main.data_ptr(), ws_main.numel() * 4
-        side = _side_stream(dev) if _use_side_stream(sink, M) else None
-        tn_need = hip.lib().vlmo_gemm_tn_ws_bytes(M, hid, d)
-        if side is not None:
-            with torch.cuda.stream(side):
-                ws_side = hip.workspace(dev, ncols)
-                ws_tn = hip.tn_workspace(dev, tn_need)
-            D.ws_side, D.side_stream = ws_side.data_ptr(), side.cuda_stream
-            D.ws_bytes = min(D.ws_bytes, ws_side.numel() * 4)
-        else:
-            D.ws_side, D.side_stream = None, None
-            ws_tn = hip.tn_workspace(dev, tn_need)
-        D.ws_tn, D.ws_tn_bytes = ws_tn.data_ptr(), ws_tn.numel() * 4
-        hip.block_bwd(D)
-        ctx.desc = ctx.keep = None
-        if sink is not None:
-            # the bucket IS the gradient storage: p.grad become views of it, autograd gets nothing to add
-            for p_, g_ in zip(params, grads):
-                if p_.requires_grad:
-                    if p_.grad is None:
-                        p_.grad = g_
-                    elif p_.grad.data_ptr() != g_.data_ptr():
-                        raise RuntimeError('a parameter of a data-parallel block already holds a foreign .grad; '
-                                           'use zero_grad(set_to_none=True)')
-            sink.release_all(ctx.sink_groups)
-            return (dx0, None) + (None,) * len(grads)
-        return (dx0, None, *grads)
+                           'by the first backward (retain_graph=True is not supported by engine.StackFn)')
 
 
 WGRAD_BATCH = int(_os.environ.get('VLMO_WGRAD_BATCH', '2'))     # blocks per deferred weight-gradient launch; 0 = by tile count
@@ -545,7 +442,7 @@ def wgrad_batch_for(d, hid, cus=256, max_batch=4):
             best, best_cost = b, cost
     return best
 TMP_SETS = 4                                                     # rotation depth of the backward temporaries
-USE_STACK = _os.environ.get('VLMO_STACK', '1') != '0'            # one native call per pass (else one per block)
+USE_STACK = True      # one StackFn call per pass; False (tests: no cross-block logic): one StackFn call per block
 
 _PERSIST = {}
 
@@ -582,9 +479,9 @@ INPLACE_ACCUM = _os.environ.get('VLMO_INPLACE_ACCUM', '1') != '0'      # kill sw
 #     INTO that buffer inside the weight-gradient kernels and returns None for the group.  That is only right while
 #     autograd's input buffer for each parameter of the group still IS the first node's view when the later nodes have
 #     run, i.e. while StackFn nodes are the parameter's only gradient producers: any other contribution (a weight
-#     regulariser, a weight reused outside the engine, a BlockFn pass) makes the input buffer add out of place -- the
-#     view shares its storage with the flat buffer, so it cannot add in place -- and every later node would add into an
-#     orphaned buffer, silently losing its gradient.  Whether that can happen is a property of the graph, so
+#     regulariser, a weight reused outside the engine) makes the input buffer add out of place -- the view shares its
+#     storage with the flat buffer, so it cannot add in place -- and every later node would add into an orphaned
+#     buffer, silently losing its gradient.  Whether that can happen is a property of the graph, so
 #     inplace_passes() walks it from the roots before the backward (sole_producer_groups) and permits the mechanism only
 #     for groups every trainable parameter of which is fed by StackFn nodes alone, and only to the nodes it walked,
 #     during the first graph task that runs inside it.  Outside inplace_passes(), every pass returns fresh gradients and
@@ -640,8 +537,7 @@ def sole_producer_groups(roots):
     """(engine nodes, {group key}): the StackFn nodes reachable from `roots`, and the parameter groups of theirs whose
     every trainable parameter receives its gradient from StackFn nodes ONLY and belongs to one group only -- the groups
     for which mechanism (1) is sound in a backward from exactly these roots.  An engine node is any node carrying
-    `grad_groups` ([(group key, parameters)], set by StackFn.forward); BlockFn nodes and every other op count as
-    foreign producers."""
+    `grad_groups` ([(group key, parameters)], set by StackFn.forward); every other op counts as a foreign producer."""
     seen, feeds = _walk(roots)
     nodes = [fn for fn in seen if getattr(fn, 'grad_groups', None) is not None]
     node_set = set(nodes)
@@ -735,7 +631,7 @@ def _same_views(layout, flat):
 class StackFn(torch.autograd.Function):
     """All Blocks of one backbone pass (the loops at vlmo.py:402-411) as ONE native call per direction
     (vlmo_stack_fwd / vlmo_stack_bwd).  metas: one BlockMeta per block, in forward order; params: the blocks'
-    parameter lists concatenated, each in BlockFn's order."""
+    parameter lists concatenated, each in per-block order (vlmo.Block._params)."""
 
     @staticmethod
     def forward(ctx, x, metas, *params):
@@ -914,7 +810,6 @@ class StackFn(torch.autograd.Function):
             D.dz2, D.du, D.dy2, D.dz1, D.dqkv, D.dy1 = pb, pb + md2, pb + 5 * md2, pb + 6 * md2, pb + 7 * md2, pb + 10 * md2
             D.dctx = D.dy2
             D.ws_main, D.ws_bytes = ws.data_ptr() + st_ * ws_n * 4, ws_n * 4
-            D.ws_side, D.side_stream, D.ws_tn, D.ws_tn_bytes = None, None, None, 0
             D.dx1 = dxs.data_ptr() + 2 * md * 4
             D.dx2 = dxo.data_ptr() if k == 0 else dxs.data_ptr() + ((k - 1) % 2) * md * 4
             D.dx0 = dx_in.data_ptr() if k == nb - 1 else dxs.data_ptr() + (k % 2) * md * 4

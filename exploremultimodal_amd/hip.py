@@ -53,8 +53,7 @@ class BlockDesc(ctypes.Structure):
                               'dg1', 'dg2', 'dn1w', 'dn1b', 'dn2w', 'dn2b', 'dqkv_w', 'dqkv_b',
                               'dproj_w', 'dproj_b')]
         + [(n, _fp * 2) for n in ('dw1', 'db1', 'dw2', 'db2')]
-        + [('ws_main', _fp), ('ws_side', _fp), ('ws_bytes', _i64), ('ws_tn', _fp), ('ws_tn_bytes', _i64),
-           ('side_stream', _fp)])
+        + [('ws_main', _fp), ('ws_bytes', _i64)])
 
 
 class StackDesc(ctypes.Structure):
@@ -104,8 +103,6 @@ _SIGS = {
     'vlmo_maxpool2_nhwc': [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     'vlmo_argmax_reduce': [_vp, _i32, _vp, _i32, _vp],
     'vlmo_ce_reduce': [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
-    'vlmo_block_fwd': [ctypes.POINTER(BlockDesc), _vp],
-    'vlmo_block_bwd': [ctypes.POINTER(BlockDesc), _vp],
     'vlmo_stack_fwd': [ctypes.POINTER(StackDesc), _vp],
     'vlmo_stack_bwd': [ctypes.POINTER(StackDesc), _vp],
     'vlmo_gemm_tn_multi': [_i32, ctypes.POINTER(TnProblem), _i32, _vp],
@@ -139,7 +136,7 @@ _SIGS = {
 }
 
 _lib = None
-ABI_VERSION = 5      # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
+ABI_VERSION = 6      # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
 
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is missing."""
@@ -556,14 +553,6 @@ def vqa_bce(z, y, B, V, *, row_loss=None, row_arg=None, row_score=None, dscale=N
                               _p(row_arg), _p(row_score), _p(dscale), float(alpha), _p(dadd),
                               dadd.stride(0) if dadd is not None else 0, _p(dz), dz.stride(0) if dz is not None else 0,
                               _stream()), 'vlmo_vqa_bce')
-
-
-def block_fwd(desc):
-    _check(lib().vlmo_block_fwd(ctypes.byref(desc), _stream()), 'vlmo_block_fwd')
-
-
-def block_bwd(desc):
-    _check(lib().vlmo_block_bwd(ctypes.byref(desc), _stream()), 'vlmo_block_bwd')
 
 
 PROFILE_TAGS = 96

@@ -130,6 +130,8 @@ class Block(nn.Module):
 
     # -- engine plumbing -----------------------------------------------------
     def _params(self, routes):
+        """The engine's per-block parameter order: gamma_1, gamma_2, norm1 w / b, qkv_w, q_bias, v_bias, proj_w, proj_b,
+        norm2 w / b, then (fc1_w, fc1_b, fc2_w, fc2_b) per route."""
         a = self.attn
         g1, g2 = (self.gamma_1, self.gamma_2) if self.gamma_1 is not None else (self._unit_scale, self._unit_scale)
         qb, vb = (a.q_bias, a.v_bias) if a.q_bias is not None else (a._zero_bias, a._zero_bias)
@@ -164,11 +166,9 @@ class Block(nn.Module):
         return meta, self._params(routes)
 
     def run(self, x, plan, routes, ranges, fused, shadows, seed, drop_scales=None):
-        """x: packed fp32 [M, d] -> this block's output (one native call per direction)."""
+        """x: packed fp32 [M, d] -> this block's output (a one-block engine.StackFn: one native call per direction)."""
         meta, params = self.meta(x, plan, routes, ranges, fused, shadows, seed, drop_scales)
-        if engine.USE_STACK:
-            return engine.StackFn.apply(x, [meta], *params)
-        return engine.BlockFn.apply(x, meta, *params)
+        return engine.StackFn.apply(x, [meta], *params)
 
     def forward(self, x, mask=None, route='vl'):
         """Reference signature (vlmo.py:187): x [B, N, d] -> (x, attn=None)."""

@@ -79,7 +79,10 @@ typedef struct VlmoEpilogue {
 } VlmoEpilogue;
 
 const char* vlmo_last_error(void);
-int vlmo_abi_version(void);
+/* Version of the struct layouts and signatures below; raised whenever one of them changes
+ * (exploremultimodal_amd/hip.py mirrors it as ABI_VERSION and refuses any other). */
+#define VLMO_ABI_VERSION 6
+int vlmo_abi_version(void);     /* = VLMO_ABI_VERSION of the header the library was built from */
 
 /* C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue.  tile: -1 = pick by shape, 0 = 128x128x64
  * (two workgroups per CU), 3 = 256x256x64 with the two-wave-group ping-pong schedule (one per CU),
@@ -280,19 +283,16 @@ int vlmo_mt_grad_norm(const VlmoTensorList* tl, float inv_scale, float max_norm,
  * ctl[1]; the whole step is skipped when ctl[2] != 0, like GradScaler.step) or NULL. */
 int vlmo_mt_adam(const VlmoTensorList* tl, const VlmoAdamArgs* a, const float* ctl, hipStream_t stream);
 
-/* The stream vlmo_block_bwd's weight-gradient work runs on (VlmoBlockDesc.side_stream).  It has the
+/* The stream vlmo_stack_bwd's deferred parameter-gradient work runs on (VlmoStackDesc.side_stream).  It has the
  * whole step of slack while the activation-gradient chain on the caller's stream is the critical
  * path, so it is created with the LOWEST dispatch priority of the device (low_priority != 0), and/or
  * confined to the compute units of cu_mask (cu_mask_words 32-bit words; NULL/0 = all CUs). */
 int vlmo_side_stream_create(int low_priority, const uint32_t* cu_mask, int cu_mask_words, hipStream_t* out);
 
-/* ---- one transformer Block in ONE call (vlmo.py:187-197 and its autograd) ---------------------
- * Enqueues norm1 -> qkv -> attention -> proj(+gamma_1, residual) -> norm2 -> expert FFN(s)
- * (+gamma_2, residual), resp. the whole backward of that, from native code: the host pays one
- * FFI call per block instead of ~12 / ~30.  Expert e works on rows [exp_row0[e], +exp_rows[e]);
- * attention launch a on seg[a] (sequences of at most maxlen[a] tokens).  All buffers caller-owned.
- * Backward runs the weight-gradient GEMMs and bias column sums on `side_stream` (if not NULL)
- * beside the input-gradient chain and joins before returning control of the buffers. */
+/* ---- one transformer Block of a stack (vlmo.py:187-197 and its autograd) ---------------------
+ * norm1 -> qkv -> attention -> proj(+gamma_1, residual) -> norm2 -> expert FFN(s) (+gamma_2,
+ * residual), resp. the whole backward of that.  Expert e works on rows [exp_row0[e], +exp_rows[e]);
+ * attention launch a on seg[a] (sequences of at most maxlen[a] tokens).  All buffers caller-owned. */
 typedef struct VlmoBlockDesc {
     int32_t M, d, hidden, heads;
     int32_t n_experts, exp_row0[2], exp_rows[2];   /* 1..2 experts */
@@ -325,17 +325,12 @@ typedef struct VlmoBlockDesc {
     void *dz2, *du, *dy2, *dz1, *dctx, *dqkv, *dy1;
     float *dg1, *dg2, *dn1w, *dn1b, *dn2w, *dn2b, *dqkv_w, *dqkv_b, *dproj_w, *dproj_b;
     float *dw1[2], *db1[2], *dw2[2], *db2[2];
-    float *ws_main, *ws_side;   /* column-reduction scratch per stream (vlmo_reduce_ws_bytes)            */
+    float* ws_main;             /* column-reduction scratch (see vlmo_stack_bwd)                         */
     int64_t ws_bytes;
-    float* ws_tn;               /* weight-gradient slab scratch (vlmo_gemm_tn_ws_bytes), used on the     */
-    int64_t ws_tn_bytes;        /* side stream; NULL = atomics                                           */
-    hipStream_t side_stream;
 } VlmoBlockDesc;
-int vlmo_block_fwd(const VlmoBlockDesc* b, hipStream_t stream);
-int vlmo_block_bwd(const VlmoBlockDesc* b, hipStream_t stream);
 
 /* ---- all blocks of one backbone pass in ONE call per direction (the loops at vlmo.py:402-411) -------------
- * blocks[] are in forward order; block i's x2 is block i+1's x.  vlmo_stack_fwd = vlmo_block_fwd per block.
+ * blocks[] are in forward order; block i's x2 is block i+1's x.  vlmo_stack_fwd runs the blocks' forwards in order.
  * vlmo_stack_bwd runs the activation-gradient chains of all blocks back to back on `stream` and defers the
  * parameter-gradient work (weight-gradient GEMMs, bias / layer-scale / LayerNorm column sums) to
  * `side_stream` in batches of `wgrad_batch` blocks, one vlmo_gemm_tn_multi + one vlmo_colwork_multi launch
@@ -343,10 +338,9 @@ int vlmo_block_bwd(const VlmoBlockDesc* b, hipStream_t stream);
  * the block's own chain, the caller gives the k-th block in backward order its own backward temporaries
  * (dz2, du, dz1, dqkv) and column workspace ws_main (>= (3 + n_experts) * vlmo_reduce_ws_bytes(2*d) bytes),
  * rotating over n_tmp_sets > wgrad_batch sets (set k % n_tmp_sets); the call waits for a set's deferred readers
- * before reusing it and joins the side stream before it returns control of the buffers.  ws_side, ws_tn and
- * the blocks' own side_stream field are ignored.  grad_ready (optional, [n_blocks] hipEvent_t handles from
- * vlmo_event_create): event i is recorded when block i's parameter gradients are complete, so a gradient
- * all-reduce on another stream can start per block (vlmo_stream_wait_event). */
+ * before reusing it and joins the side stream before it returns control of the buffers.  grad_ready (optional,
+ * [n_blocks] hipEvent_t handles from vlmo_event_create): event i is recorded when block i's parameter gradients
+ * are complete, so a gradient all-reduce on another stream can start per block (vlmo_stream_wait_event). */
 typedef struct VlmoStackDesc {
     int32_t n_blocks, wgrad_batch, n_tmp_sets;
     int32_t wgrad_store;        /* != 0: weight-gradient MATRICES are written (C = ...), not accumulated: no zero-fill, no

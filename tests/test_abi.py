@@ -1,5 +1,5 @@
 """The C-ABI library builds, loads and exports every symbol include/vlmo_hip.h
-declares (no compute: runs without a GPU)."""
+declares, at the ABI version the header states (no compute: runs without a GPU)."""
 import ctypes
 import os
 import re
@@ -9,12 +9,21 @@ from exploremultimodal_amd import hip
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _header():
+    return open(os.path.join(ROOT, 'include', 'vlmo_hip.h')).read()
+
+
 def _declared():
-    src = open(os.path.join(ROOT, 'include', 'vlmo_hip.h')).read()
-    return sorted(set(re.findall(r'\b(vlmo_[a-z0-9_]+)\s*\(', src)))
+    return sorted(set(re.findall(r'\b(vlmo_[a-z0-9_]+)\s*\(', _header())))
 
 
-def test_library_exports_header_symbols():
+def _header_abi_version():
+    m = re.search(r'^#define\s+VLMO_ABI_VERSION\s+(\d+)\s*$', _header(), re.M)
+    assert m, 'vlmo_hip.h does not define VLMO_ABI_VERSION'
+    return int(m.group(1))
+
+
+def test_library_exports_header_symbols_at_header_abi_version():
     import __graft_entry__ as ge
     if not os.path.exists(hip.LIB_PATH):
         ge.build()
@@ -25,7 +34,7 @@ def test_library_exports_header_symbols():
         assert hasattr(L, n), f'{n} declared in vlmo_hip.h but not exported'
     assert sorted(hip.exported_symbols()) == names, 'hip.py binding list and header disagree'
     L.vlmo_abi_version.restype = ctypes.c_int
-    assert L.vlmo_abi_version() == hip.ABI_VERSION == 5
+    assert L.vlmo_abi_version() == hip.ABI_VERSION == _header_abi_version()
 
 
 def test_missing_library_fails_loudly(monkeypatch):

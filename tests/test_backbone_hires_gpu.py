@@ -94,9 +94,9 @@ def test_base_width_480px_vs_oracle():
 
 
 def test_384px_dropout_paths_and_schedules_agree():
-    """Training mode at 384 px with attention dropout, dropout and drop-path on: the native stack path equals the
-    per-block path (outputs bit-identical), the one-stream schedule equals the side-stream schedule, and the split
-    backward attention switch changes nothing (the backward regenerates the forward's mask)."""
+    """Training mode at 384 px with attention dropout, dropout and drop-path on: one StackFn call per pass equals one
+    StackFn call per block (outputs bit-identical), the one-stream schedule equals the side-stream schedule, and the
+    split backward attention switch changes nothing (the backward regenerates the forward's mask)."""
     from exploremultimodal_amd import engine
     model, mc = build('mini', dict(img_size=384), drop=0.1, drop_path=0.1)
     model.train()
@@ -119,8 +119,7 @@ def test_384px_dropout_paths_and_schedules_agree():
         assert torch.equal(xs, x), name
         assert set(gr) == set(gs), name
         for n in gs:
-            frac = 4e-3 if (name == 'block' and n.endswith(('fc1.bias', 'q_bias', 'v_bias'))) else 1e-3
-            tol = frac * gs[n].abs().max().item() + 1e-9
+            tol = 1e-3 * gs[n].abs().max().item() + 1e-9
             assert (gr[n] - gs[n]).abs().max().item() <= tol, (name, n, (gr[n] - gs[n]).abs().max().item(), tol)
 
 

@@ -92,7 +92,7 @@ def _worker(rank, world, port, mode, q):
 
 
 def _sink_worker(rank, world, port, q):
-    """The engine-sink protocol (expect / acquire / release / finish) that BlockFn drives, on CPU tensors:
+    """The engine-sink protocol (expect / acquire / release / finish) that StackFn drives, on CPU tensors:
     two 'passes' accumulate into one bucket before it is reduced; a second step re-zeroes it."""
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
     dist.init_process_group('gloo', rank=rank, world_size=world)

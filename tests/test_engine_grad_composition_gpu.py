@@ -1,7 +1,9 @@
-"""Block-parameter gradients of the HIP engine (engine.StackFn / BlockFn and the reducer sink of dp.GradReducer) under
+"""Block-parameter gradients of the HIP engine (engine.StackFn and the reducer sink of dp.GradReducer) under
 losses that are not built from the backbone alone: weight regularisers, block weights reused outside the engine, frozen
 groups, gradients over a subset of a group, tensor hooks, accumulation across backward() calls.  These decide which
-buffer a weight-gradient launch writes or adds into and what autograd is handed.
+buffer a weight-gradient launch writes or adds into and what autograd is handed.  Every case runs with one StackFn node
+per pass (stack=True) and with one StackFn node per block (stack=False, engine.USE_STACK off): then the graph walk of
+engine.inplace_passes sees many engine nodes per parameter group instead of one.
 
 Reference A (tight): the same loss with engine.INPLACE_ACCUM off -- every pass returns fresh gradients and autograd
 sums them -- at the suite's bound for summation-order differences, 2e-3 * max|ref|.  Regulariser strengths are chosen

@@ -2,7 +2,7 @@
 autograd.Function stand-ins for StackFn carry `grad_groups` like the real node, and ToyStack follows the engine's
 protocol -- the first permitted node of a graph task registers its gradient buffer, later ones add into it and return
 None.  The walk must permit exactly the groups whose trainable parameters get their gradient from engine nodes alone;
-with a foreign producer (regulariser, reused weight, a BlockFn pass) the group must fall back to fresh gradients, and
+with a foreign producer (regulariser, reused weight, an engine node without grad_groups) the group must fall back to fresh gradients, and
 the gradients must come out as autograd's sum in every case."""
 import torch
 
@@ -36,7 +36,8 @@ class ToyStack(torch.autograd.Function):
 
 
 class ToyBlock(torch.autograd.Function):
-    """A cooperating-but-unwalked engine node: fresh gradients, no grad_groups (stands in for BlockFn)."""
+    """A cooperating-but-unwalked engine node: fresh gradients, no grad_groups (stands in for any engine node that
+    does not carry them)."""
 
     @staticmethod
     def forward(ctx, x, *params):
@@ -91,7 +92,7 @@ def test_foreign_producers_switch_off_exactly_the_affected_groups():
     assert engine.sole_producer_groups([passes() + 0.5 * a[1].pow(2)])[1] == {'B', 'C'}
     # B's weight reused outside the engine (order of the terms does not matter to the walk)
     assert engine.sole_producer_groups([(x * b[0]).square().mean() + passes()])[1] == {'A', 'C'}
-    # a BlockFn-style pass over C
+    # a pass over C by an engine node without grad_groups
     assert engine.sole_producer_groups([passes() + ToyBlock.apply(x, *c).sum()])[1] == {'A', 'B'}
     # a foreign use of a FROZEN parameter produces no gradient: the group stays permitted
     c[0].requires_grad_(False)
