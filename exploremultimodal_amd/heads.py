@@ -10,7 +10,12 @@ The small heads (ITC projection + normalise, 2-way ITM, pooler) are a few MFLOP 
 
 The VQA classifier (Linear(hs, 2hs) -> LayerNorm -> GELU -> Linear(2hs, 3129), vlmo_module.py:85-93) and its
 binary cross-entropy (objectives.py:317-353) run as ``VQAHeadFn``: the two Linears on the HIP GEMMs, the LayerNorm +
-GELU and the per-row loss / arg-max on the row kernels of csrc/vqa_head.hip."""
+GELU and the per-row loss / arg-max on the row kernels of csrc/vqa_head.hip.
+
+With ISDA (train.isda_lambda > 0, vlmo_module.py:95-101) the last Linear is ``vqa_last`` and ``ISDAHead`` holds the
+per-class feature statistics; a training step with answers runs as ``VQAIsdaHeadFn``: the estimator update and the
+logit augmentation of heads.py:6-83 on the kernels of csrc/isda.hip, without the reference's [B, vs, 2hs] tensors.
+``isda_update_`` / ``isda_augment`` restate the same arithmetic in torch for features on the CPU."""
 import torch
 import torch.nn as nn
 
@@ -203,6 +208,161 @@ class VQAHeadFn(torch.autograd.Function):
         xd, w1d, b1d, gd, bd, w2d, b2d = ctx.in_dtypes
         return (dx.to(xd), dw1[:h2, :hs].to(w1d), db1.to(b1d), dg.to(gd), dbeta.to(bd), dw2[:vs, :h2].to(w2d),
                 db2[:vs].to(b2d), None, None, None, None)
+
+
+class VQAIsdaHeadFn(torch.autograd.Function):
+    """``VQAHeadFn`` with ISDA (heads.py:6-83, objectives.py:325-344) between the last Linear and the loss ->
+    (augmented logits, loss, argmax, score_rows).  ``targets`` are required (ISDA runs only on a batch with answers).
+
+    Forward: the head as in VQAHeadFn up to the fp32 logits z [B, npad]; then (1) vlmo_isda_update: the estimator
+    buffers ``count`` [vs], ``emean``, ``cov`` [vs, 2hs] (fp32, updated IN PLACE) take this batch's LayerNorm + GELU
+    features (recomputed in fp32 from the pre-LayerNorm rows, not the bf16 GEMM operand) and k_n = first arg-max of
+    each target row; (2) ck = cov[k] after the update; (3) vlmo_isda_aug_fwd adds 0.5 * ratio * sum_a (W[j] - W[k_n])^2
+    ck[n] to z in place (pad columns stay zero); (4) the loss, arg-max and score of vqa_bce on the augmented z.
+    Backward: as VQAHeadFn; vlmo_isda_aug_bwd then adds the augmentation's gradient with respect to vqa_last.weight (through
+    W[j] and the gathered rows W[k_n]) to the fp32 dW2 accumulator before its cast, from the same bf16 logits gradient
+    the GEMMs use.  No gradient reaches the features through the augmentation.  With ratio 0 the augmentation is
+    skipped: logits, loss and gradients are VQAHeadFn's bit for bit (the estimator still updates, as upstream)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, ln_w, ln_b, w2, b2, targets, eps, out_dtype, shadows, count, emean, cov, ratio):
+        ctx.set_materialize_grads(False)
+        B, hs = x.shape
+        h2, vs = w1.shape[0], w2.shape[0]
+        if targets is None or tuple(targets.shape) != (B, vs):
+            raise ValueError(f'ISDA needs vqa targets [{B}, {vs}], got {None if targets is None else tuple(targets.shape)}')
+        if tuple(cov.shape) != (vs, h2) or tuple(emean.shape) != (vs, h2) or tuple(count.shape) != (vs,):
+            raise ValueError(f'ISDA estimator buffers must be [{vs}], [{vs}, {h2}], [{vs}, {h2}]')
+        w1s, w1t, w2s, w2t, b2p = shadows.get(w1, w2, b2)
+        k0, k1, npad = w1s.shape[1], w2s.shape[1], w2s.shape[0]
+        dev = x.device
+        xb = torch.zeros((B, k0), dtype=torch.bfloat16, device=dev) if k0 != hs else torch.empty((B, k0), dtype=torch.bfloat16, device=dev)
+        xb[:, :hs] = x.detach()
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        b1f, gf, bf = f32(b1), f32(ln_w), f32(ln_b)
+        u = torch.empty((B, h2), dtype=torch.float32, device=dev)
+        hip.gemm_nt(hip.EPI_F32, xb, w1s, B, h2, k0, u, bias=b1f)
+        h = torch.empty((B, k1), dtype=torch.bfloat16, device=dev)
+        mean = torch.empty(B, dtype=torch.float32, device=dev)
+        rstd = torch.empty(B, dtype=torch.float32, device=dev)
+        hip.ln_gelu_fwd(u, gf, bf, h, mean, rstd, B, h2, eps)
+        z = torch.empty((B, npad), dtype=torch.float32, device=dev)
+        hip.gemm_nt(hip.EPI_F32, h, w2s, B, npad, k1, z, bias=b2p)
+        y = targets.detach().to(torch.float32).contiguous()
+        k = torch.empty(B, dtype=torch.int32, device=dev)
+        hip.isda_update(u, y, B, vs, h2, count, emean, cov, k, ln_mean=mean, ln_rstd=rstd, ln_w=gf, ln_b=bf)
+        ratio = float(ratio)
+        w2f = ck = None
+        if ratio != 0.0:
+            w2f = f32(w2)
+            ck = cov.index_select(0, k)            # cov[k_n] after the update, kept for the backward
+            hip.isda_aug_fwd(w2f, k, ck, B, vs, h2, 0.5 * ratio, z)
+        rows = torch.empty(B, dtype=torch.float32, device=dev)
+        arg = torch.empty(B, dtype=torch.int32, device=dev)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        hip.vqa_bce(z, y, B, vs, row_loss=rows, row_arg=arg, row_score=score)
+        loss = rows.sum() / B
+        ctx.mark_non_differentiable(arg, score)
+        logits = z[:, :vs]
+        if out_dtype != torch.float32:
+            logits = logits.to(out_dtype)
+        ctx.save_for_backward(xb, u, h, mean, rstd, z, y, gf, bf, w1t, w2t, w2f, k, ck)
+        ctx.dims = (B, hs, h2, vs, eps, ratio)
+        ctx.in_dtypes = (x.dtype, w1.dtype, b1.dtype, ln_w.dtype, ln_b.dtype, w2.dtype, b2.dtype)
+        return logits, loss, arg, score
+
+    @staticmethod
+    def backward(ctx, dlogits, dloss, _darg, _dscore):
+        xb, u, h, mean, rstd, z, y, gf, bf, w1t, w2t, w2f, k, ck = ctx.saved_tensors
+        B, hs, h2, vs, eps, ratio = ctx.dims
+        dev = z.device
+        npad, k0, k1 = z.shape[1], xb.shape[1], h.shape[1]
+        dz = torch.empty((B, npad), dtype=torch.bfloat16, device=dev)
+        dadd = dlogits.to(torch.float32).contiguous() if dlogits is not None else None
+        with_loss = dloss is not None
+        dscale = dloss.detach().to(torch.float32).reshape(1).contiguous() if with_loss else None
+        hip.vqa_bce(z, y if with_loss else None, B, vs, dscale=dscale, alpha=1.0 / B, dadd=dadd, dz=dz)
+        dh = torch.empty((B, k1), dtype=torch.float32, device=dev)
+        hip.gemm_nt(hip.EPI_F32, dz, w2t, B, k1, npad, dh)
+        dw2 = torch.zeros((npad, k1), dtype=torch.float32, device=dev)
+        hip.gemm_tn(dz, h, dw2, B, npad, k1)
+        if ratio != 0.0:
+            hip.isda_aug_bwd(dz, w2f, k, ck, B, vs, h2, ratio, dw2)
+        db2 = torch.zeros(npad, dtype=torch.float32, device=dev)
+        for r0 in range(0, B, 1008):      # <= 1008 rows per call: one ordered add per column (reproducible)
+            r1 = min(B, r0 + 1008)
+            hip.colsum(dz[r0:r1], db2, r1 - r0, npad)
+        du = torch.empty((B, k1), dtype=torch.bfloat16, device=dev)
+        dg = torch.empty(h2, dtype=torch.float32, device=dev)
+        dbeta = torch.empty(h2, dtype=torch.float32, device=dev)
+        db1 = torch.empty(h2, dtype=torch.float32, device=dev)
+        hip.ln_gelu_bwd(dh, u, gf, bf, mean, rstd, B, h2, dxb=du, dw=dg, db=dbeta, dbias=db1)
+        dx = torch.empty((B, hs), dtype=torch.float32, device=dev)
+        hip.gemm_nt(hip.EPI_F32, du, w1t, B, hs, k1, dx)
+        dw1 = torch.zeros((k1, k0), dtype=torch.float32, device=dev)
+        hip.gemm_tn(du, xb, dw1, B, k1, k0)
+        xd, w1d, b1d, gd, bd, w2d, b2d = ctx.in_dtypes
+        return (dx.to(xd), dw1[:h2, :hs].to(w1d), db1.to(b1d), dg.to(gd), dbeta.to(bd), dw2[:vs, :h2].to(w2d),
+                db2[:vs].to(b2d), None, None, None, None, None, None, None, None)
+
+
+@torch.no_grad()
+def isda_update_(count, mean, cov, feats, targets):
+    """Estimator update (heads.py:16-50) in place, torch form for CPU features: per class with member rows
+    (targets != 0), their mean ``ave`` and population variance ``var``; w = n / (n + count);
+    cov <- cov (1 - w) + var w + w (1 - w) (mean - ave)^2, mean <- mean (1 - w) + ave w, count += n.  Only classes with
+    members are written."""
+    member = targets != 0
+    n = member.sum(0)
+    cls = n.nonzero().flatten()
+    if cls.numel() == 0:
+        return
+    m = member[:, cls].t().to(feats.dtype)                       # [T, B]
+    nc = n[cls].to(feats.dtype)[:, None]
+    ave = (m @ feats) / nc
+    var = (((feats[None] - ave[:, None]) ** 2) * m[..., None]).sum(1) / nc
+    w = nc / (nc + count[cls][:, None])
+    mo = mean[cls]
+    cov[cls] = cov[cls] * (1 - w) + var * w + w * (1 - w) * (mo - ave) ** 2
+    mean[cls] = mo * (1 - w) + ave * w
+    count[cls] += n[cls].to(count.dtype)
+
+
+def isda_augment(logits, weight, cov, k, ratio):
+    """logits + 0.5 * ratio * sum_a (W[j, a] - W[k_n, a])^2 cov[k_n, a] (heads.py:55-68), differentiable in ``weight``
+    only; the square expanded into three products, so no [B, vs, 2hs] tensor is formed."""
+    c = cov[k].detach()                                           # [B, A]
+    wk = weight[k]
+    quad = (weight * weight) @ c.t() - 2.0 * (weight @ (wk * c).t()) + (wk * wk * c).sum(1)[None]
+    return logits + 0.5 * ratio * quad.t()
+
+
+class EstimatorCV(nn.Module):
+    """heads.py:6-14: per-class feature count, mean and diagonal covariance (persistent fp32 buffers)."""
+
+    def __init__(self, hidden_size, class_num):
+        super().__init__()
+        self.class_num = class_num
+        self.register_buffer('count', torch.zeros(class_num))
+        self.register_buffer('mean', torch.zeros(class_num, hidden_size))
+        self.register_buffer('cov', torch.zeros(class_num, hidden_size))
+
+    def forward(self, features, labels):
+        isda_update_(self.count, self.mean, self.cov, features.detach(), labels)
+
+
+class ISDAHead(nn.Module):
+    """heads.py:53-83; ``forward`` is the torch form (CPU features), the GPU step runs VQAIsdaHeadFn."""
+
+    def __init__(self, hidden_size, class_num):
+        super().__init__()
+        self.estimator = EstimatorCV(hidden_size, class_num)
+        self.class_num = class_num
+
+    def forward(self, y, features, fc_weight, target, ratio):
+        self.estimator(features, target)
+        k = torch.max(target, 1)[1]
+        return isda_augment(y, fc_weight, self.estimator.cov, k, ratio)
 
 
 class BertPredictionHeadTransform(nn.Module):

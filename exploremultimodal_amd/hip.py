@@ -133,6 +133,9 @@ _SIGS = {
     'vlmo_ln_gelu_bwd': [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp,
                          _i64, _vp],
     'vlmo_vqa_bce': [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _i32, _vp],
+    'vlmo_isda_update': [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    'vlmo_isda_aug_fwd': [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _i64, _vp],
+    'vlmo_isda_aug_bwd': [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _i64, _vp],
 }
 
 _lib = None
@@ -156,6 +159,8 @@ def lib():
         L.vlmo_reduce_ws_bytes.restype = ctypes.c_int64
         L.vlmo_reduce_ws_bytes.argtypes = [_i32]
         L.vlmo_gemm_tn_ws_bytes.restype = ctypes.c_int64
+        L.vlmo_isda_ws_bytes.restype = ctypes.c_int64
+        L.vlmo_isda_ws_bytes.argtypes = [_i32, _i32, _i32]
         L.vlmo_gemm_tn_ws_bytes.argtypes = [_i32, _i32, _i32]
         for name, sig in _SIGS.items():
             fn = getattr(L, name)
@@ -166,7 +171,8 @@ def lib():
 
 
 def exported_symbols():
-    return ['vlmo_last_error', 'vlmo_abi_version', 'vlmo_reduce_ws_bytes', 'vlmo_gemm_tn_ws_bytes'] + list(_SIGS)
+    return ['vlmo_last_error', 'vlmo_abi_version', 'vlmo_reduce_ws_bytes', 'vlmo_gemm_tn_ws_bytes',
+            'vlmo_isda_ws_bytes'] + list(_SIGS)
 
 
 def _check(rc, name):
@@ -553,6 +559,37 @@ def vqa_bce(z, y, B, V, *, row_loss=None, row_arg=None, row_score=None, dscale=N
                               _p(row_arg), _p(row_score), _p(dscale), float(alpha), _p(dadd),
                               dadd.stride(0) if dadd is not None else 0, _p(dz), dz.stride(0) if dz is not None else 0,
                               _stream()), 'vlmo_vqa_bce')
+
+
+def isda_update(u, y, B, V, A, count, mean, cov, k, *, ln_mean=None, ln_rstd=None, ln_w=None, ln_b=None):
+    """ISDA estimator update in place (include/vlmo_hip.h: vlmo_isda_update) and k int32 [B] = first arg-max of each
+    target row.  With ln_w given the features are GELU(LayerNorm(u)) recomputed from the pre-LayerNorm rows u and
+    ln_mean / ln_rstd; without, u are the features."""
+    for t, n in ((count, 'count'), (mean, 'mean'), (cov, 'cov')):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f'isda_update: {n} must be contiguous fp32')
+    _check(lib().vlmo_isda_update(_p(u), u.stride(0), _p(ln_mean), _p(ln_rstd), _p(ln_w), _p(ln_b), _p(y), y.stride(0),
+                                  B, V, A, _p(count), _p(mean), _p(cov), _p(k), _stream()), 'vlmo_isda_update')
+
+
+def _isda_ws(device, B, V, A):
+    return torch.empty((lib().vlmo_isda_ws_bytes(B, V, A) + 3) // 4, dtype=torch.float32, device=device)
+
+
+def isda_aug_fwd(W, k, ck, B, V, A, scale, z):
+    """z[:, :V] += scale * sum_a (W[j] - W[k_n])^2 ck[n] (vlmo_isda_aug_fwd); W, ck, z fp32, k int32."""
+    ws = _isda_ws(z.device, B, V, A)
+    _check(lib().vlmo_isda_aug_fwd(_p(W), W.stride(0), _p(k), _p(ck), ck.stride(0), B, V, A, float(scale), _p(z),
+                                   z.stride(0), _p(ws), ws.numel() * 4, _stream()), 'vlmo_isda_aug_fwd')
+
+
+def isda_aug_bwd(G, W, k, ck, B, V, A, r, dw):
+    """dw[:V] += the augmentation's weight gradient for G = d loss / d z_aug bf16 (vlmo_isda_aug_bwd)."""
+    if G.dtype != torch.bfloat16:
+        raise ValueError('isda_aug_bwd: G must be bf16')
+    ws = _isda_ws(dw.device, B, V, A)
+    _check(lib().vlmo_isda_aug_bwd(_p(G), G.stride(0), _p(W), W.stride(0), _p(k), _p(ck), ck.stride(0), B, V, A,
+                                   float(r), _p(dw), dw.stride(0), _p(ws), ws.numel() * 4, _stream()), 'vlmo_isda_aug_bwd')
 
 
 PROFILE_TAGS = 96

@@ -268,21 +268,42 @@ def compute_vqa_score(logits, target):
     return scores.sum() / count, count
 
 
-def _vqa_head(model, feats, targets):
-    """vqa_classifier(feats) and, with targets, its loss ``BCE-with-logits mean * vs`` and mean score
-    -> (logits, loss or None, mean score or None).  Features on the GPU take heads.VQAHeadFn (HIP), CPU features the
-    torch modules with the reference's formulas (objectives.py:346-351)."""
+def isda_ratio(train_cfg):
+    """ISDA strength of this step: isda_lambda * cur_epoch / epochs (objectives.py:327-335), read at every forward."""
+    return train_cfg.isda_lambda * train_cfg.cur_epoch / train_cfg.epochs
+
+
+def _vqa_head(model, feats, targets, isda=False):
+    """vqa_classifier(feats) (then ``vqa_last`` when the module was built with ISDA) and, with targets, its loss
+    ``BCE-with-logits mean * vs`` and mean score -> (logits, loss or None, mean score or None).  ``isda``: update the
+    estimator and add the ISDA augmentation to the logits first (objectives.py:325-344).  Features on the GPU take
+    heads.VQAHeadFn / heads.VQAIsdaHeadFn (HIP), CPU features the torch modules with the reference's formulas
+    (objectives.py:346-351)."""
     head = model.vqa_classifier
+    last = model.vqa_last
     if feats.is_cuda:
-        from .heads import VQAHeadFn, _VQAShadows
-        fc1, ln, _, fc2 = head
+        from .heads import VQAHeadFn, VQAIsdaHeadFn, _VQAShadows
+        fc1, ln = head[0], head[1]
+        fc2 = head[3] if last is None else last
         if not hasattr(model, '_vqa_shadows'):
             object.__setattr__(model, '_vqa_shadows', _VQAShadows())
         out_dtype = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else torch.float32
-        logits, loss, _, score_rows = VQAHeadFn.apply(feats, fc1.weight, fc1.bias, ln.weight, ln.bias, fc2.weight,
-                                                      fc2.bias, targets, ln.eps, out_dtype, model._vqa_shadows)
+        if isda:
+            est = model.isda_head.estimator
+            logits, loss, _, score_rows = VQAIsdaHeadFn.apply(
+                feats, fc1.weight, fc1.bias, ln.weight, ln.bias, fc2.weight, fc2.bias, targets, ln.eps, out_dtype,
+                model._vqa_shadows, est.count, est.mean, est.cov, isda_ratio(model.config.train))
+        else:
+            logits, loss, _, score_rows = VQAHeadFn.apply(feats, fc1.weight, fc1.bias, ln.weight, ln.bias, fc2.weight,
+                                                          fc2.bias, targets, ln.eps, out_dtype, model._vqa_shadows)
         return logits, loss, (score_rows.sum() / feats.shape[0] if score_rows is not None else None)
     logits = head(feats)
+    if last is not None:
+        last_feats = logits
+        logits = last(last_feats)
+        if isda:
+            logits = model.isda_head(y=logits, features=last_feats, fc_weight=last.weight, target=targets,
+                                     ratio=isda_ratio(model.config.train))
     if targets is None:
         return logits, None, None
     loss = F.binary_cross_entropy_with_logits(logits, targets) * targets.shape[1]
@@ -290,16 +311,18 @@ def _vqa_head(model, feats, targets):
 
 
 def compute_vqa(model, batch):
-    """objectives.py:317-389 without the ISDA branch (VlmoModule refuses isda_lambda > 0).  The gate on the targets is
-    ``batch['_vqa_has_targets']`` when attach_row_indices set it, else the reference's ``torch.sum(targets) > 0``.  With
-    ``config.train.kl_alpha > 0`` in training (R-Drop) a second backbone pass with its own dropout masks adds
-    ``vqa_kl_task_loss`` and averages the two BCE losses."""
+    """objectives.py:317-389.  The gate on the targets is ``batch['_vqa_has_targets']`` when attach_row_indices set it,
+    else the reference's ``torch.sum(targets) > 0``.  With ISDA (the module built ``vqa_last``) a training step with
+    answers updates the estimator and returns the augmented logits, loss and score; eval mode or all-zero targets leave
+    the estimator alone.  With ``config.train.kl_alpha > 0`` in training (R-Drop) a second backbone pass with its own
+    dropout masks adds ``vqa_kl_task_loss`` and averages the two BCE losses (VlmoModule refuses R-Drop with ISDA)."""
     infer = model.infer(batch, infer_mode='img-txt', mask_txt=False, mask_img=False)
     vqa_targets = batch.get('vqa_targets')
     has = batch.get('_vqa_has_targets')
     if has is None:
         has = vqa_targets is not None and bool(torch.sum(vqa_targets) > 0.0)
-    vqa_logits, vqa_loss, vqa_mean_score = _vqa_head(model, infer['cls_feats'], vqa_targets if has else None)
+    isda = has and model.vqa_last is not None and model.training
+    vqa_logits, vqa_loss, vqa_mean_score = _vqa_head(model, infer['cls_feats'], vqa_targets if has else None, isda)
     ret = {'vqa_logits': vqa_logits, 'vqa_count': vqa_logits.size(0)}
     if not has:
         return ret

@@ -1,10 +1,14 @@
 """Host-side mirror of VlmoModule (models/vlmo/vlmo_module.py:14-442): same constructor
 (attribute-style config), parameter names, `infer` / `forward` / `load_from_ckpt` /
 `no_weight_decay` contracts.  Pretraining losses [mlm, mim, itc, itm] and the VQAv2 fine-tuning
-loss [vqa] (the classifier and its loss on the HIP path of heads.VQAHeadFn); the ISDA variant of the
-VQA head (isda_lambda > 0), the other downstream heads (nlvr2 / irtr / mpp / refcoco), EMA and the
-negative queue raise NotImplementedError (out of scope, off in
-conf/train/pretrain_mum.yaml and conf/train/finetune_vqa.yaml)."""
+loss [vqa] (the classifier and its loss on the HIP path of heads.VQAHeadFn).  With train.isda_lambda > 0
+the classifier's last Linear becomes ``vqa_last`` and ``isda_head`` keeps the ISDA estimator (buffers
+isda_head.estimator.{count, mean, cov}); training steps with answers run heads.VQAIsdaHeadFn.  ISDA
+needs train.epochs and train.cur_epoch (its ratio) and is refused with R-Drop (kl_alpha > 0), which
+fails upstream.  Each rank keeps its own estimator, as the reference's DDP with broadcast_buffers=False
+does.  The other downstream heads (nlvr2 / irtr / mpp / refcoco), EMA and the negative queue raise
+NotImplementedError (out of scope, off in conf/train/pretrain_mum.yaml and
+conf/train/finetune_vqa.yaml)."""
 import math
 from collections import defaultdict
 from functools import partial
@@ -15,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import objectives
-from .heads import ITCHead, ITMHead, MIMHead, MLMHead
+from .heads import ISDAHead, ITCHead, ITMHead, MIMHead, MLMHead
 from .vlmo import VLMO, LayerNorm
 
 
@@ -62,14 +66,26 @@ class VlmoModule(nn.Module):
                 p.requires_grad = False
             self.mim_head = MIMHead(hs, model_cfg.img_vocab_size)
             self.mim_head.apply(self.transformer._init_weights)
-        if 'vqa' in self.loss_names:                     # vlmo_module.py:85-100
-            if getattr(config.train, 'isda_lambda', 0.0) > 0.:
-                raise NotImplementedError('isda_lambda > 0 (the ISDA head of the VQA classifier) is not implemented; '
-                                          'conf/train/finetune_vqa.yaml leaves it at 0')
+        if 'vqa' in self.loss_names:                     # vlmo_module.py:85-101
+            isda_lambda = getattr(config.train, 'isda_lambda', 0.0)
+            if isda_lambda > 0.:
+                missing = [f for f in ('epochs', 'cur_epoch') if not hasattr(config.train, f)]
+                if missing:
+                    raise NotImplementedError(
+                        f'isda_lambda > 0 needs train.epochs and train.cur_epoch: the ISDA ratio is isda_lambda * '
+                        f'cur_epoch / epochs (objectives.py:327-335); this config lacks {", ".join(missing)}')
+                if getattr(config.train, 'kl_alpha', 0.0) > 0.:
+                    raise NotImplementedError(
+                        'isda_lambda > 0 with kl_alpha > 0 (R-Drop) is not supported: upstream the second pass feeds '
+                        'the 3-layer classifier output to the BCE loss, which fails on its shape')
             vs = config.data.vqav2_label_size
             self.vqa_classifier = nn.Sequential(nn.Linear(hs, hs * 2), norm_layer(hs * 2), nn.GELU(), nn.Linear(hs * 2, vs))
             self.vqa_classifier.apply(self.transformer._init_weights)
             self.vqa_last = None
+            if isda_lambda > 0.:
+                self.vqa_last = self.vqa_classifier[-1]
+                self.vqa_classifier = self.vqa_classifier[:-1]
+                self.isda_head = ISDAHead(hidden_size=hs * 2, class_num=vs)
 
         self.transformer_m = None
         if getattr(self.config, 'vlmo_ema', False):

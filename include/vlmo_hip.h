@@ -429,6 +429,34 @@ int vlmo_vqa_bce(const float* z, int ldz, const float* y, int ldy, int B, int V,
                  float* row_score, const float* dscale, float alpha, const float* dadd, int ldadd, void* dz, int lddz,
                  hipStream_t stream);
 
+/* ---- ISDA of the VQA classifier's last Linear (heads.py:6-83, objectives.py:325-344); csrc/isda.hip ---- */
+
+/* Estimator update, in place, and the arg-max class of every target row.  Features f [B, A] fp32: with ln_w given,
+ * f = GELU_erf(LayerNorm(u) * ln_w + ln_b) recomputed from the pre-LayerNorm rows u [B, ldu] and the statistics
+ * mean, rstd [B] of vlmo_ln_gelu_fwd; with ln_w NULL, f = u.  Targets y fp32 [B, ldy] (first V columns).  For each
+ * class c with n_c = #{n : y[n, c] != 0} > 0: ave, var = mean and population variance of its member rows (ascending
+ * n), w = n_c / (n_c + count[c]), cov[c] = cov[c](1 - w) + var w + w(1 - w)(emean[c] - ave)^2,
+ * emean[c] = emean[c](1 - w) + ave w, count[c] += n_c; classes with n_c = 0 are not written.  count [V],
+ * emean, cov [V, A] fp32 contiguous.  k int32 [B] = first arg-max of each target row (0 for an all-zero row).
+ * 0 < A <= 2048, A % 4 == 0, ldu % 4 == 0. */
+int vlmo_isda_update(const float* u, int ldu, const float* mean, const float* rstd, const float* ln_w,
+                     const float* ln_b, const float* y, int ldy, int B, int V, int A, float* count, float* emean,
+                     float* cov, int32_t* k, hipStream_t stream);
+/* Bytes of the workspace of vlmo_isda_aug_fwd / vlmo_isda_aug_bwd for (B, V, A). */
+int64_t vlmo_isda_ws_bytes(int B, int V, int A);
+/* z[n, j] += scale * sum_a (W[j, a] - W[k[n], a])^2 * ck[n, a] for n < B, j < V (columns >= V untouched).
+ * W fp32 [V, ldw], k int32 [B] with values in [0, V), ck fp32 [B, ldc] (the covariance rows cov[k[n]]), z fp32
+ * [B, ldz].  fp32 arithmetic; fixed-order partial sums over A in ws: bitwise reproducible. */
+int vlmo_isda_aug_fwd(const float* W, int ldw, const int32_t* k, const float* ck, int ldc, int B, int V, int A,
+                      float scale, float* z, int ldz, float* ws, int64_t ws_bytes, hipStream_t stream);
+/* Weight gradient of the augmentation for G = d loss / d z_aug (bf16 [B, ldg]) and r = 2 * scale:
+ *   dw[j, a] += r * sum_n G[n, j] (W[j, a] - W[k_n, a]) ck[n, a]
+ *             - r * sum_{n: k_n = j} ck[n, a] * sum_j' G[n, j'] (W[j', a] - W[j, a])
+ * dw fp32 [V, lddw] (an accumulator; rows >= V untouched).  No atomics, fixed summation order. */
+int vlmo_isda_aug_bwd(const void* G, int ldg, const float* W, int ldw, const int32_t* k, const float* ck, int ldc,
+                      int B, int V, int A, float r, float* dw, int lddw, float* ws, int64_t ws_bytes,
+                      hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

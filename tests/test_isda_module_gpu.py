@@ -1,0 +1,194 @@
+"""VQAv2 fine-tuning with ISDA through VlmoModule on the GPU: parity with the reference's own three-step run
+(tests/golden/vqa_isda_mini.npz, tools/gen_isda_golden.py), the augmentation term in isolation, the estimator and the
+vqa_last gradient rows; eval mode; a prefetched step without host synchronisation; autocast; peak memory at Base
+widths against the plain head; a short fine-tuning loop."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import synth
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+TRAIN = dict(isda_lambda=7.5, epochs=2, cur_epoch=1)
+
+
+def _build(**train):
+    from exploremultimodal_amd.build import build_model
+    cfg = synth.make_config('mini', loss_names=['vqa'], phase='finetune_vqa', img_size=224)
+    for k, v in dict(TRAIN, **train).items():
+        setattr(cfg.train, k, v)
+    mc = cfg.model
+    model = build_model(cfg)
+    sd = {'transformer.' + k: v for k, v in synth.synth_backbone_state_dict(mc, 0).items()}
+    sd.update(synth.synth_isda_head_state_dict(mc, 0))
+    sd.update(synth.synth_isda_estimator(2 * mc.embed_dim, 3129, 0))
+    r = model.load_state_dict(sd, strict=False)
+    assert not r.unexpected_keys and not r.missing_keys, (r.unexpected_keys, r.missing_keys)
+    return model.to(DEV), cfg
+
+
+def _batch(cfg, g, s, device=DEV):
+    b = synth.synth_batch(cfg.model, int(g['meta.B']), seed=1234 + s, mim=False)
+    b['vqa_targets'] = torch.from_numpy(g[f's{s}.vqa_targets'])
+    return {k: v.to(device) for k, v in b.items()} if device else b
+
+
+@pytest.fixture(scope='module')
+def golden(golden_dir):
+    return np.load(os.path.join(golden_dir, 'vqa_isda_mini.npz'))
+
+
+def _rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+def test_isda_module_matches_reference(golden):
+    model, cfg = _build()
+    est = model.isda_head.estimator
+    storage = {k: t.data_ptr() for k, t in est.state_dict().items()}
+    for s in range(3):
+        p = f's{s}.'
+        batch = _batch(cfg, golden, s)
+        model.eval()
+        with torch.no_grad():
+            plain = model(dict(batch))['vqa_logits'].float().cpu().numpy()        # no augmentation, no update
+        model.train()
+        model.zero_grad(set_to_none=True)
+        ret = model(dict(batch))
+        assert set(ret) == {'vqa_logits', 'vqa_count', 'vqa_task_loss', 'vqa_targets', 'vqa_mean_score'}
+        assert 'VQAIsdaHeadFn' in type(ret['vqa_task_loss'].grad_fn).__name__
+        logits = ret['vqa_logits'].detach().float().cpu().numpy()
+        assert np.abs(logits - golden[p + 'ret.vqa_logits']).max() <= 5e-2
+        assert np.abs(plain - golden[p + 'z']).max() <= 5e-2
+        # the augmentation on its own: the 5e-2 logits bound would hide a wrong one
+        aug, aug_ref = logits - plain, golden[p + 'ret.vqa_logits'] - golden[p + 'z']
+        assert np.abs(aug_ref).max() > 0.1
+        assert _rel(aug, aug_ref) <= 2e-2, s
+        ref = float(golden[p + 'ret.vqa_task_loss'])
+        assert abs(float(ret['vqa_task_loss']) - ref) <= 2e-2 + 2e-3 * abs(ref)
+        assert float(ret['vqa_mean_score']) == pytest.approx(float(golden[p + 'ret.vqa_mean_score']), abs=1e-6)
+        touched = torch.from_numpy(golden[p + 'touched'])
+        assert torch.equal(est.count.cpu(), torch.from_numpy(golden[p + 'count']))
+        assert _rel(est.mean.cpu()[touched], golden[p + 'mean_rows']) <= 2e-2
+        assert _rel(est.cov.cpu()[touched], golden[p + 'cov_rows']) <= 2e-2
+        ret['vqa_task_loss'].backward()
+        rows = torch.from_numpy(golden[p + 'grad_rows_idx'])
+        gw = model.vqa_last.weight.grad.cpu()[rows].numpy()
+        ref_rows = golden[p + 'grad_rows']
+        assert np.linalg.norm(gw - ref_rows) <= 3e-2 * np.linalg.norm(ref_rows), s
+        for name, prm in model.named_parameters():
+            key = p + 'grad_norm.' + name
+            if key in golden.files and name.startswith('vqa_'):
+                assert float(prm.grad.double().norm()) == pytest.approx(float(golden[key]), rel=3e-2), name
+    # updated in place: the same tensors, the same storage
+    assert {k: t.data_ptr() for k, t in est.state_dict().items()} == storage
+
+
+def test_isda_eval_matches_reference(golden):
+    model, cfg = _build()
+    before = {k: v.clone() for k, v in model.isda_head.estimator.state_dict().items()}
+    model.eval()
+    with torch.no_grad():
+        ret = model(_batch(cfg, golden, 0))
+    assert np.abs(ret['vqa_logits'].float().cpu().numpy() - golden['eval.vqa_logits']).max() <= 5e-2
+    ref = float(golden['eval.vqa_task_loss'])
+    assert abs(float(ret['vqa_task_loss']) - ref) <= 2e-2 + 2e-3 * abs(ref)
+    for k, v in model.isda_head.estimator.state_dict().items():
+        assert torch.equal(v, before[k]), k
+
+
+def test_isda_prefetched_step_has_no_host_sync(golden):
+    from exploremultimodal_amd.objectives import attach_row_indices
+    model, cfg = _build()
+    model.train()
+    host = _batch(cfg, golden, 0, device=None)
+    attach_row_indices(host)
+    batch = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in host.items()}
+    model(dict(batch))['vqa_task_loss'].backward()
+    model.zero_grad(set_to_none=True)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode('error')
+    try:
+        ret = model(dict(batch))
+        ret['vqa_task_loss'].backward()
+    finally:
+        torch.cuda.set_sync_debug_mode('default')
+    assert torch.isfinite(ret['vqa_task_loss']).item()
+    assert model.vqa_last.weight.grad is not None
+
+
+@pytest.mark.parametrize('amp_dtype', [torch.bfloat16, torch.float16])
+def test_isda_autocast_step(golden, amp_dtype):
+    model, cfg = _build()
+    model.train()
+    with torch.autocast('cuda', dtype=amp_dtype):
+        ret = model(_batch(cfg, golden, 0))
+    assert ret['vqa_logits'].dtype == amp_dtype and ret['vqa_task_loss'].dtype == torch.float32
+    ret['vqa_task_loss'].backward()
+    assert torch.isfinite(ret['vqa_task_loss']).item()
+    for k, t in model.isda_head.estimator.state_dict().items():
+        assert t.dtype == torch.float32 and torch.isfinite(t).all(), k
+    for k, p in model.named_parameters():
+        if p.grad is not None:
+            assert p.grad.dtype == p.dtype and torch.isfinite(p.grad).all(), k
+
+
+def test_isda_peak_memory_at_base_widths():
+    """Head alone at VLMo-Base widths (hs 768, 2hs 1536, 3129 answers), B 64: the ISDA step may hold at most 64 MB
+    more than the plain head (the reference form needs > 1.2 GB for one [B, vs, 2hs] fp32 tensor)."""
+    from exploremultimodal_amd.heads import VQAHeadFn, VQAIsdaHeadFn, _VQAShadows
+    B, hs, vs = 64, 768, 3129
+    g = torch.Generator(device=DEV).manual_seed(0)
+    x = torch.randn(B, hs, device=DEV, generator=g)
+    params = [torch.randn(2 * hs, hs, device=DEV, generator=g) * 0.02, torch.zeros(2 * hs, device=DEV),
+              torch.ones(2 * hs, device=DEV), torch.zeros(2 * hs, device=DEV),
+              torch.randn(vs, 2 * hs, device=DEV, generator=g) * 0.02, torch.zeros(vs, device=DEV)]
+    params = [p.requires_grad_(True) for p in params]
+    y = torch.zeros(B, vs, device=DEV)
+    y[torch.arange(B), torch.randint(0, vs, (B,), device=DEV, generator=g)] = 1.0
+    count = torch.zeros(vs, device=DEV)
+    mean = torch.zeros(vs, 2 * hs, device=DEV)
+    cov = torch.rand(vs, 2 * hs, device=DEV, generator=g)
+
+    def peak(fn):
+        for p in params:
+            p.grad = None
+        fn()                                   # warm: shadows, workspaces
+        for p in params:
+            p.grad = None
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        return torch.cuda.max_memory_allocated() - base
+
+    sh1, sh2 = _VQAShadows(), _VQAShadows()
+    plain = peak(lambda: VQAHeadFn.apply(x, *params, y, 1e-12, torch.float32, sh1)[1].backward())
+    isda = peak(lambda: VQAIsdaHeadFn.apply(x, *params, y, 1e-12, torch.float32, sh2, count, mean, cov, 3.75)[1].backward())
+    print(f'peak plain {plain / 2**20:.1f} MB, isda {isda / 2**20:.1f} MB')
+    assert isda - plain <= 64 * 2**20, (plain, isda)
+
+
+def test_isda_short_finetune_lowers_the_loss(golden):
+    from exploremultimodal_amd import optim
+    model, cfg = _build()
+    model.train()
+    batch = _batch(cfg, golden, 0)
+    groups = optim.get_parameter_groups(model, base_lr=1e-4, lr_mult_head=50, lr_mult_fusion=5, weight_decay=0.01,
+                                        skip_list=model.no_weight_decay())
+    opt = optim.FusedAdam(groups, betas=(0.9, 0.98), eps=1e-8)
+    scaler = optim.NativeScalerWithGradNormCount()
+    losses = []
+    for _ in range(6):
+        opt.zero_grad(set_to_none=True)
+        loss = model(dict(batch))['vqa_task_loss']
+        losses.append(float(loss))
+        scaler(loss, opt, clip_grad=5.0, parameters=[p for p in model.parameters() if p.requires_grad], update_grad=True)
+    torch.cuda.synchronize()
+    print('losses', losses)
+    assert all(np.isfinite(losses)) and losses[-1] < 0.9 * losses[0]

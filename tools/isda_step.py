@@ -1,0 +1,205 @@
+"""VQAv2 fine-tuning with ISDA on the GPU: (1) one full VLMo-Base fine-tune step (as tools/vqa_step.py: forward,
+backward, FusedAdam with the finetune_vqa.yaml groups, clip 5.0) with ISDA off (isda_lambda 0) and on (isda_lambda 0.5,
+cur_epoch 5 of 10, a seeded estimator), interleaved, at 384 px (B 32) and 480 px (B 16); (2) the classifier + loss
+alone, forward + backward: heads.VQAHeadFn, heads.VQAIsdaHeadFn and a torch restatement of the reference's ISDA form
+(EstimatorCV / ISDAHead with their [B, vs, 2hs] intermediates, nn.Sequential + BCE-with-logits), with the peak memory of
+each, at B in {16, 64, 512} and the Base (2hs 1536) and Large (2hs 2048) widths.
+
+    python tools/isda_step.py [--steps 10] [--warmup 3] [--res 384:32,480:16] [--ab-iters 20] [--json out.json]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+from exploremultimodal_amd import objectives, optim, synth  # noqa: E402
+from exploremultimodal_amd.build import build_model  # noqa: E402
+
+VS = 3129
+
+
+def _timed(fn, iters):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e3
+
+
+def _step_fn(res, B, isda):
+    cfg = synth.make_config('base', loss_names=['vqa'], phase='finetune_vqa', img_size=res, drop_rate=0.1,
+                            attn_drop_rate=0.1, drop_path_rate=0.1)
+    if isda:
+        cfg.train.isda_lambda, cfg.train.epochs, cfg.train.cur_epoch = 0.5, 10, 5
+    mc = cfg.model
+    model = build_model(cfg)
+    sd = {'transformer.' + k: v for k, v in synth.synth_backbone_state_dict(mc, 0).items()}
+    if isda:
+        sd.update(synth.synth_isda_head_state_dict(mc, 0))
+        sd.update(synth.synth_isda_estimator(2 * mc.embed_dim, VS, 0))
+    else:
+        sd.update(synth.synth_head_state_dict(mc, 0, ['vqa']))
+    model.load_state_dict(sd, strict=False)
+    model = model.cuda().train()
+    host = synth.synth_batch(mc, B, seed=1234, mim=False)
+    host['vqa_targets'] = synth.synth_vqa_targets(B, VS)
+    objectives.attach_row_indices(host)
+    batch = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in host.items()}
+    groups = optim.get_parameter_groups(model, base_lr=3e-6, lr_mult_head=50, lr_mult_fusion=5, weight_decay=0.01,
+                                        skip_list=model.no_weight_decay())
+    opt = optim.FusedAdam(groups, betas=(0.9, 0.98), eps=1e-8)
+    scaler = optim.NativeScalerWithGradNormCount()
+    params = [p for p in model.parameters() if p.requires_grad]
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = model(dict(batch))['vqa_task_loss']
+        scaler(loss, opt, clip_grad=5.0, parameters=params, update_grad=True)
+
+    return step
+
+
+def run_step(res, B, steps, warmup, rounds=3):
+    fns = {'off': _step_fn(res, B, False), 'on': _step_fn(res, B, True)}
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+    ms = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            ms[k].append(_timed(fn, steps))
+    off, on = statistics.median(ms['off']), statistics.median(ms['on'])
+    return dict(kind='finetune_step_isda', img_size=res, B=B, ms_off=round(off, 3), ms_on=round(on, 3),
+                delta_ms=round(on - off, 3), rounds_off=[round(v, 3) for v in ms['off']],
+                rounds_on=[round(v, 3) for v in ms['on']])
+
+
+class _RefEstimator:
+    """The reference's EstimatorCV.forward / ISDAHead.isda_aug, restated in torch with the same intermediates."""
+
+    def __init__(self, A):
+        self.count = torch.zeros(VS, device='cuda')
+        self.mean = torch.zeros(VS, A, device='cuda')
+        self.cov = torch.rand(VS, A, device='cuda')
+
+    @torch.no_grad()
+    def update(self, f, y):
+        N, A = f.shape
+        fe = f.view(N, 1, A).expand(N, VS, A)
+        oh = y.to(torch.bool).to(torch.long)
+        oh3 = oh.view(N, VS, 1).expand(N, VS, A)
+        fs = fe.mul(oh3)
+        amt = oh3.sum(0)
+        amt[amt == 0] = 1
+        ave = fs.sum(0) / amt
+        var = (fs - ave.expand(N, VS, A).mul(oh3)).pow(2).sum(0).div(amt)
+        sw = oh.sum(0).view(VS, 1).expand(VS, A)
+        w = sw.div(sw + self.count.view(VS, 1).expand(VS, A))
+        w[w != w] = 0
+        self.cov = self.cov.mul(1 - w) + var.mul(w) + w.mul(1 - w).mul((self.mean - ave).pow(2))
+        self.mean = self.mean.mul(1 - w) + ave.mul(w)
+        self.count += oh.sum(0)
+
+    def aug(self, W, f, k, ratio):
+        N, A = f.shape
+        Wij = W.expand(N, VS, A)
+        Wkj = torch.gather(Wij, 1, k.view(N, 1, 1).expand(N, VS, A))
+        c = self.cov[k]
+        return 0.5 * ratio * (W - Wkj).pow(2).mul(c.view(N, 1, A).expand(N, VS, A)).sum(2)
+
+
+def run_ab(hs, B, iters, rounds=3):
+    from exploremultimodal_amd.heads import VQAHeadFn, VQAIsdaHeadFn, _VQAShadows
+    torch.manual_seed(hs)
+    h2 = 2 * hs
+    cls = torch.nn.Sequential(torch.nn.Linear(hs, h2), torch.nn.LayerNorm(h2, eps=1e-12), torch.nn.GELU()).cuda()
+    last = torch.nn.Linear(h2, VS).cuda()
+    fc1, ln = cls[0], cls[1]
+    x = torch.randn(B, hs, device='cuda', requires_grad=True)
+    y = synth.synth_vqa_targets(B, VS).cuda()
+    count = torch.zeros(VS, device='cuda')
+    mean = torch.zeros(VS, h2, device='cuda')
+    cov = torch.rand(VS, h2, device='cuda')
+    sh1, sh2 = _VQAShadows(), _VQAShadows()
+    ref = _RefEstimator(h2)
+    ratio = 0.25
+
+    def plain():
+        VQAHeadFn.apply(x, fc1.weight, fc1.bias, ln.weight, ln.bias, last.weight, last.bias, y, ln.eps, torch.float32,
+                        sh1)[1].backward()
+
+    def isda():
+        VQAIsdaHeadFn.apply(x, fc1.weight, fc1.bias, ln.weight, ln.bias, last.weight, last.bias, y, ln.eps, torch.float32,
+                            sh2, count, mean, cov, ratio)[1].backward()
+
+    def torch_ref():
+        f = cls(x)
+        z = last(f)
+        ref.update(f.detach(), y)
+        k = torch.max(y, 1)[1]
+        z = z + ref.aug(last.weight, f, k, ratio)
+        loss = F.binary_cross_entropy_with_logits(z, y) * VS
+        objectives.compute_vqa_score(z, y)
+        loss.backward()
+
+    out = dict(kind='head_ab_isda', width=h2, B=B)
+    fns = {'plain': plain, 'isda': isda, 'torch_ref': torch_ref}
+    alive = {}
+    for name, fn in fns.items():
+        try:
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            out[name + '_peak_mb'] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+            alive[name] = fn
+        except torch.cuda.OutOfMemoryError:
+            out[name + '_us'] = 'oom'
+            torch.cuda.empty_cache()
+    times = {k: [] for k in alive}
+    for _ in range(rounds):
+        for k, fn in alive.items():
+            times[k].append(_timed(fn, iters if k != 'torch_ref' or B < 512 else max(2, iters // 10)) * 1e3)
+    for k, v in times.items():
+        out[k + '_us'] = round(statistics.median(v), 1)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--res', default='384:32,480:16')
+    ap.add_argument('--ab-iters', type=int, default=20)
+    ap.add_argument('--json', default=None)
+    args = ap.parse_args()
+    rows = []
+    for hs in (768, 1024):
+        for B in (16, 64, 512):
+            r = run_ab(hs, B, args.ab_iters)
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+            torch.cuda.empty_cache()
+    for item in filter(None, args.res.split(',')):
+        res, B = (int(v) for v in item.split(':'))
+        r = run_step(res, B, args.steps, args.warmup)
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+        torch.cuda.empty_cache()
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, 'w') as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == '__main__':
+    main()
