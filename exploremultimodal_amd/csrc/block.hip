@@ -1,5 +1,5 @@
 // The VLMo Blocks (vlmo.py:187-197) of one backbone pass forward / backward per C-ABI call: native
-// orchestration of the kernels in gemm.hip / attention.hip / layernorm.hip / elementwise.hip, so the
+// orchestration of the kernels in gemm_*.hip / attention.hip / layernorm.hip / elementwise.hip, so the
 // Python host issues one FFI call per pass and stays far ahead of the GPU.
 #include "common.h"
 #include "vlmo_hip.h"

@@ -1,5 +1,5 @@
 // Glue kernels of the dall_e dVAE encoder (dall_e/encoder.py:74-121) around the
-// implicit-GEMM convolutions of gemm.hip.  Activations are NHWC fp16 matrices
+// implicit-GEMM convolutions of conv.hip.  Activations are NHWC fp16 matrices
 // [B*H*W, C] (the reference runs this encoder in fp16 on GPU: dall_e/utils.py:37-42).
 #include "common.h"
 #include "vlmo_hip.h"

@@ -1,6 +1,6 @@
 // VQA classifier head (models/vlmo/vlmo_module.py:85-93: Linear(hs, 2hs) -> LayerNorm(2hs) -> GELU -> Linear(2hs, vs))
 // and its binary cross-entropy loss / score (models/vlmo/objectives.py:12-21, 317-353).  The two Linears run on the
-// GEMMs of gemm.hip; this file holds the row kernels between and after them:
+// GEMMs of gemm_nt.hip / gemm_tn.hip; this file holds the row kernels between and after them:
 //   ln_gelu_fwd   LayerNorm (fp32 statistics, eps 1e-12) + exact-erf GELU -> the bf16 operand of the second GEMM
 //   ln_gelu_bwd   recompute the LayerNorm output, GELU', LayerNorm backward; deterministic column sums (fixed-order
 //                 per-wave partials folded in order, no atomics) for d gamma, d beta and the first Linear's d bias

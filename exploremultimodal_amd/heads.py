@@ -4,7 +4,7 @@ The two vocabulary heads -- the MLM decoder tied to the word embedding (768 -> 3
 (768 -> 8 192 visual tokens) -- have a fused loss path (``loss_and_pred``): a HIP GEMM whose epilogue keeps per-row
 running (max, sum exp, arg-max, label logit) per 64-column chunk, so the [rows, vocabulary] logits never reach HBM, and
 a backward that recomputes (softmax - onehot) tile-wise into the bf16 operand of the input- and weight-gradient GEMMs
-(VLMO_EPI_CE / VLMO_EPI_CE_BWD, csrc/gemm.hip).  ``forward`` still returns the logits (reference contract:
+(VLMO_EPI_CE / VLMO_EPI_CE_BWD, csrc/gemm_common.h).  ``forward`` still returns the logits (reference contract:
 `mlm_logits` / `mim_logits` in the output dict); ``config.train.fused_ce`` selects the fused path in the objectives.
 The small heads (ITC projection + normalise, 2-way ITM, pooler) are a few MFLOP and stay torch ops.
 

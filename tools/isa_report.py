@@ -1,5 +1,5 @@
 """Per-kernel resource / instruction report from a hipcc -save-temps device assembly file.
-usage: python tools/isa_report.py build/gemm-hip-amdgcn-amd-amdhsa-gfx950.s [name filter]"""
+usage: python tools/isa_report.py build/gemm_nt16-hip-amdgcn-amd-amdhsa-gfx950.s [name filter]"""
 import re
 import sys
 
