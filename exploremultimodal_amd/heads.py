@@ -8,13 +8,14 @@ a backward that recomputes (softmax - onehot) tile-wise into the bf16 operand of
 `mlm_logits` / `mim_logits` in the output dict); ``config.train.fused_ce`` selects the fused path in the objectives.
 The small heads (ITC projection + normalise, 2-way ITM, pooler) are a few MFLOP and stay torch ops.
 
-The VQA classifier (Linear(hs, 2hs) -> LayerNorm -> GELU -> Linear(2hs, 3129), vlmo_module.py:85-93) and its
-binary cross-entropy (objectives.py:317-353) run as ``VQAHeadFn``: the two Linears on the HIP GEMMs, the LayerNorm +
-GELU and the per-row loss / arg-max on the row kernels of csrc/vqa_head.hip.
+A Linear -> LayerNorm -> GELU -> Linear classifier runs as ``_mlp_fwd`` / ``_mlp_bwd``: the Linears on the HIP GEMMs,
+LayerNorm + GELU on the row kernels of csrc/vqa_head.hip.  ``VQAHeadFn`` is that path for the VQA classifier (hs -> 2hs
+-> 3129, vlmo_module.py:85-93) with its binary cross-entropy (objectives.py:317-353) on the row kernel vlmo_vqa_bce.
 
 With ISDA (train.isda_lambda > 0, vlmo_module.py:95-101) the last Linear is ``vqa_last`` and ``ISDAHead`` holds the
-per-class feature statistics; a training step with answers runs as ``VQAIsdaHeadFn``: the estimator update and the
-logit augmentation of heads.py:6-83 on the kernels of csrc/isda.hip, without the reference's [B, vs, 2hs] tensors.
+per-class feature statistics; a training step with answers runs as ``VQAIsdaHeadFn``: the same path plus the estimator
+update and the logit augmentation of heads.py:6-83 on the kernels of csrc/isda.hip, without the reference's [B, vs, 2hs]
+tensors.
 ``isda_update_`` / ``isda_augment`` restate the same arithmetic in torch for features on the CPU."""
 import torch
 import torch.nn as nn
@@ -22,25 +23,48 @@ import torch.nn as nn
 from . import hip
 
 
-class _PaddedShadows:
-    """bf16 copies of a vocabulary head's weight padded to a multiple of 64 rows (W [Vp, d], W^T [d, Vp]) and its fp32
-    bias padded with -1e30 (so padded columns vanish from the soft-max), refreshed when a version counter changes."""
+def _pad64(n):
+    return (n + 63) // 64 * 64
+
+
+def lazy_attr(obj, name, factory):
+    """``obj.<name>``, made by ``factory()`` on first use; set past nn.Module.__setattr__ (a cache, not a submodule)."""
+    if not hasattr(obj, name):
+        object.__setattr__(obj, name, factory())
+    return getattr(obj, name)
+
+
+class _Shadows:
+    """Copies derived from parameters by ``_build``, rebuilt when a parameter's (version counter, data pointer) changes
+    (once per optimizer step)."""
 
     def __init__(self):
         self.key, self.val = None, None
 
-    def get(self, weight, bias):
-        key = (weight._version, weight.data_ptr(), None if bias is None else (bias._version, bias.data_ptr()))
+    def _cached(self, *params):
+        key = tuple(None if t is None else (t._version, t.data_ptr()) for t in params)
         if self.key != key:
-            V, d = weight.shape
-            Vp = (V + 63) // 64 * 64
-            w = torch.zeros((Vp, d), dtype=torch.bfloat16, device=weight.device)
-            w[:V] = weight.detach()
-            wt = w.t().contiguous()
-            b = torch.full((Vp,), -1e30, dtype=torch.float32, device=weight.device)
-            b[:V] = bias.detach() if bias is not None else 0.0
-            self.key, self.val = key, (w, wt, b, Vp)
+            self.key, self.val = key, self._build(*params)
         return self.val
+
+
+class _PaddedShadows(_Shadows):
+    """bf16 copies of a vocabulary head's weight padded to a multiple of 64 rows (W [Vp, d], W^T [d, Vp]) and its fp32
+    bias padded with -1e30 (so padded columns vanish from the soft-max)."""
+
+    def get(self, weight, bias):
+        return self._cached(weight, bias)
+
+    @staticmethod
+    def _build(weight, bias):
+        V, d = weight.shape
+        Vp = _pad64(V)
+        w = torch.zeros((Vp, d), dtype=torch.bfloat16, device=weight.device)
+        w[:V] = weight.detach()
+        wt = w.t().contiguous()
+        b = torch.full((Vp,), -1e30, dtype=torch.float32, device=weight.device)
+        b[:V] = bias.detach() if bias is not None else 0.0
+        return w, wt, b, Vp
 
 
 class LinearCrossEntropyFn(torch.autograd.Function):
@@ -93,121 +117,148 @@ class LinearCrossEntropyFn(torch.autograd.Function):
         return dx.to(xd), dw[:V].to(wd), (db.to(bd) if db is not None else None), None, None, None
 
 
-def _pad64(n):
-    return (n + 63) // 64 * 64
-
-
-class _VQAShadows:
+class _VQAShadows(_Shadows):
     """bf16 copies of the VQA classifier's two weight matrices, zero-padded for the GEMMs (reduction dimensions to a
-    multiple of 64, the 3129 answers to 3136), each with its transpose, and the zero-padded fp32 output bias; rebuilt
-    when a parameter's version counter changes (once per optimizer step)."""
-
-    def __init__(self):
-        self.key, self.val = None, None
+    multiple of 64, the 3129 answers to 3136), each with its transpose, and the zero-padded fp32 output bias."""
 
     def get(self, w1, w2, b2):
-        key = tuple((t._version, t.data_ptr()) for t in (w1, w2, b2))
-        if self.key != key:
-            h2, hs = w1.shape
-            vs = w2.shape[0]
-            k0, k1, npad = _pad64(hs), _pad64(h2), _pad64(vs)
-            dev = w1.device
-            w1s = torch.zeros((h2, k0), dtype=torch.bfloat16, device=dev)
-            w1s[:, :hs] = w1.detach()
-            w1t = torch.zeros((hs, k1), dtype=torch.bfloat16, device=dev)
-            w1t[:, :h2] = w1.detach().t()
-            w2s = torch.zeros((npad, k1), dtype=torch.bfloat16, device=dev)
-            w2s[:vs, :h2] = w2.detach()
-            w2t = w2s.t().contiguous()
-            b2p = torch.zeros(npad, dtype=torch.float32, device=dev)
-            b2p[:vs] = b2.detach()
-            self.key, self.val = key, (w1s, w1t, w2s, w2t, b2p)
-        return self.val
+        return self._cached(w1, w2, b2)
+
+    @staticmethod
+    def _build(w1, w2, b2):
+        h2, hs = w1.shape
+        vs = w2.shape[0]
+        k0, k1, npad = _pad64(hs), _pad64(h2), _pad64(vs)
+        dev = w1.device
+        w1s = torch.zeros((h2, k0), dtype=torch.bfloat16, device=dev)
+        w1s[:, :hs] = w1.detach()
+        w1t = torch.zeros((hs, k1), dtype=torch.bfloat16, device=dev)
+        w1t[:, :h2] = w1.detach().t()
+        w2s = torch.zeros((npad, k1), dtype=torch.bfloat16, device=dev)
+        w2s[:vs, :h2] = w2.detach()
+        w2t = w2s.t().contiguous()
+        b2p = torch.zeros(npad, dtype=torch.float32, device=dev)
+        b2p[:vs] = b2.detach()
+        return w1s, w1t, w2s, w2t, b2p
+
+
+def _f32(t):
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _mlp_fwd(x, w1, b1, ln_w, ln_b, w2, b2, eps, shadows):
+    """Linear(hs, h2) -> LayerNorm -> GELU -> Linear(h2, n) up to the fp32 logits z [B, npad]: x -> bf16 [B, K0] -> GEMM
+    (+b1, fp32 out) -> LayerNorm + GELU (bf16 [B, K1]) -> GEMM (+b2).  Pad columns are zero in every operand.  -> (the
+    tensors for ``_mlp_bwd``: z, xb, u, h, mean, rstd, gf, bf, w1t, w2t; dims (B, hs, h2, n); the seven input dtypes)."""
+    B, hs = x.shape
+    h2, n = w1.shape[0], w2.shape[0]
+    w1s, w1t, w2s, w2t, b2p = shadows.get(w1, w2, b2)
+    k0, k1, npad = w1s.shape[1], w2s.shape[1], w2s.shape[0]
+    dev = x.device
+    xb = torch.zeros((B, k0), dtype=torch.bfloat16, device=dev) if k0 != hs else torch.empty((B, k0), dtype=torch.bfloat16, device=dev)
+    xb[:, :hs] = x.detach()
+    b1f, gf, bf = _f32(b1), _f32(ln_w), _f32(ln_b)
+    u = torch.empty((B, h2), dtype=torch.float32, device=dev)
+    hip.gemm_nt(hip.EPI_F32, xb, w1s, B, h2, k0, u, bias=b1f)
+    h = torch.empty((B, k1), dtype=torch.bfloat16, device=dev)
+    mean = torch.empty(B, dtype=torch.float32, device=dev)
+    rstd = torch.empty(B, dtype=torch.float32, device=dev)
+    hip.ln_gelu_fwd(u, gf, bf, h, mean, rstd, B, h2, eps)
+    z = torch.empty((B, npad), dtype=torch.float32, device=dev)
+    hip.gemm_nt(hip.EPI_F32, h, w2s, B, npad, k1, z, bias=b2p)
+    return ((z, xb, u, h, mean, rstd, gf, bf, w1t, w2t), (B, hs, h2, n),
+            tuple(t.dtype for t in (x, w1, b1, ln_w, ln_b, w2, b2)))
+
+
+def _mlp_bwd(saved, dims, in_dtypes, dz, after_dw2=None):
+    """From dz, the bf16 gradient of z (pad columns zero): dh = dz W2, dW2 = dz^T h, db2 = column sums; the LayerNorm +
+    GELU backward writes the bf16 operand of dx = du W1, dW1 = du^T x and folds d gamma, d beta, db1 in the same pass.
+    ``after_dw2(dw2)`` may add to the fp32 dW2 accumulator [npad, K1] right after its GEMM.  Every reduction runs in a
+    fixed order: two runs give the same bits.  -> the seven gradients in their inputs' dtypes."""
+    z, xb, u, h, mean, rstd, gf, bf, w1t, w2t = saved
+    B, hs, h2, n = dims
+    dev = z.device
+    npad, k0, k1 = z.shape[1], xb.shape[1], h.shape[1]
+    dh = torch.empty((B, k1), dtype=torch.float32, device=dev)
+    hip.gemm_nt(hip.EPI_F32, dz, w2t, B, k1, npad, dh)
+    dw2 = torch.zeros((npad, k1), dtype=torch.float32, device=dev)
+    hip.gemm_tn(dz, h, dw2, B, npad, k1)
+    if after_dw2 is not None:
+        after_dw2(dw2)
+    db2 = torch.zeros(npad, dtype=torch.float32, device=dev)
+    for r0 in range(0, B, 1008):      # <= 1008 rows per call: one ordered add per column (reproducible)
+        r1 = min(B, r0 + 1008)
+        hip.colsum(dz[r0:r1], db2, r1 - r0, npad)
+    du = torch.empty((B, k1), dtype=torch.bfloat16, device=dev)
+    dg = torch.empty(h2, dtype=torch.float32, device=dev)
+    dbeta = torch.empty(h2, dtype=torch.float32, device=dev)
+    db1 = torch.empty(h2, dtype=torch.float32, device=dev)
+    hip.ln_gelu_bwd(dh, u, gf, bf, mean, rstd, B, h2, dxb=du, dw=dg, db=dbeta, dbias=db1)
+    dx = torch.empty((B, hs), dtype=torch.float32, device=dev)
+    hip.gemm_nt(hip.EPI_F32, du, w1t, B, hs, k1, dx)
+    dw1 = torch.zeros((k1, k0), dtype=torch.float32, device=dev)
+    hip.gemm_tn(du, xb, dw1, B, k1, k0)
+    xd, w1d, b1d, gd, bd, w2d, b2d = in_dtypes
+    return (dx.to(xd), dw1[:h2, :hs].to(w1d), db1.to(b1d), dg.to(gd), dbeta.to(bd), dw2[:n, :h2].to(w2d),
+            db2[:n].to(b2d))
+
+
+def _logits_out(z, n, out_dtype):
+    logits = z[:, :n]
+    return logits if out_dtype == torch.float32 else logits.to(out_dtype)
+
+
+def _vqa_loss(z, y, B, vs):
+    """-> (sum of the per-row BCE sums / B, arg-max int32 [B], target value at the arg-max [B]); no host read."""
+    rows = torch.empty(B, dtype=torch.float32, device=z.device)
+    arg = torch.empty(B, dtype=torch.int32, device=z.device)
+    score = torch.empty(B, dtype=torch.float32, device=z.device)
+    hip.vqa_bce(z, y, B, vs, row_loss=rows, row_arg=arg, row_score=score)
+    return rows.sum() / B, arg, score
+
+
+def _vqa_dz(z, y, B, vs, dlogits, dloss):
+    """bf16 [B, npad] gradient of z: (sigmoid(z) - y) * dloss / B when the loss takes part, plus ``dlogits``, the
+    gradient of the logits output (e.g. R-Drop's KL term)."""
+    dz = torch.empty((B, z.shape[1]), dtype=torch.bfloat16, device=z.device)
+    dadd = dlogits.to(torch.float32).contiguous() if dlogits is not None else None
+    with_loss = y is not None and dloss is not None
+    dscale = dloss.detach().to(torch.float32).reshape(1).contiguous() if with_loss else None
+    hip.vqa_bce(z, y if with_loss else None, B, vs, dscale=dscale, alpha=1.0 / B, dadd=dadd, dz=dz)
+    return dz
 
 
 class VQAHeadFn(torch.autograd.Function):
     """``vqa_classifier(x)`` and, when ``targets`` is given, ``BCE-with-logits(logits, targets) * vs`` with the per-row
     arg-max and the target value at it (objectives.py:12-21, 346-351) -> (logits, loss, argmax, score_rows).
 
-    Forward: x -> bf16 [B, K0] -> GEMM (+b1, fp32 out) -> LayerNorm + GELU (bf16 [B, K1]) -> GEMM (+b2, fp32 [B, 3136])
-    -> per-row BCE sum / arg-max / score.  The loss is sum(row sums) / B (= the mean over B * vs elements times vs); no
-    value goes to the host.  Backward: (sigmoid(z) - y) * dloss / B (+ the gradient of the logits output, e.g. R-Drop's
-    KL term) as the bf16 operand of dh = dz W2, dW2 = dz^T h, db2 = column sums; the LayerNorm + GELU backward writes
-    the bf16 operand of dx = du W1, dW1 = du^T x and folds d gamma, d beta and db1 in the same pass.  Pad columns are
-    zero in every operand, so they reach neither the loss, the arg-max, the logits nor a gradient.  Every reduction runs
-    in a fixed order: two runs give the same bits.  ``out_dtype``: dtype of the returned logits (the autocast dtype
-    under autocast, as the reference's nn.Linear returns); the loss is fp32 and every gradient has its input's dtype."""
+    Forward: ``_mlp_fwd`` (fp32 [B, 3136]) -> per-row BCE sum / arg-max / score.  The loss is sum(row sums) / B (= the
+    mean over B * vs elements times vs).  Backward: ``_vqa_dz`` -> ``_mlp_bwd``.  Pad columns reach neither the loss,
+    the arg-max, the logits nor a gradient.  ``out_dtype``: dtype of the returned logits (the autocast dtype under
+    autocast, as the reference's nn.Linear returns); the loss is fp32 and every gradient has its input's dtype."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, ln_w, ln_b, w2, b2, targets, eps, out_dtype, shadows):
         ctx.set_materialize_grads(False)
-        B, hs = x.shape
-        h2, vs = w1.shape[0], w2.shape[0]
-        w1s, w1t, w2s, w2t, b2p = shadows.get(w1, w2, b2)
-        k0, k1, npad = w1s.shape[1], w2s.shape[1], w2s.shape[0]
-        dev = x.device
-        xb = torch.zeros((B, k0), dtype=torch.bfloat16, device=dev) if k0 != hs else torch.empty((B, k0), dtype=torch.bfloat16, device=dev)
-        xb[:, :hs] = x.detach()
-        f32 = lambda t: t.detach().to(torch.float32).contiguous()
-        b1f, gf, bf = f32(b1), f32(ln_w), f32(ln_b)
-        u = torch.empty((B, h2), dtype=torch.float32, device=dev)
-        hip.gemm_nt(hip.EPI_F32, xb, w1s, B, h2, k0, u, bias=b1f)
-        h = torch.empty((B, k1), dtype=torch.bfloat16, device=dev)
-        mean = torch.empty(B, dtype=torch.float32, device=dev)
-        rstd = torch.empty(B, dtype=torch.float32, device=dev)
-        hip.ln_gelu_fwd(u, gf, bf, h, mean, rstd, B, h2, eps)
-        z = torch.empty((B, npad), dtype=torch.float32, device=dev)
-        hip.gemm_nt(hip.EPI_F32, h, w2s, B, npad, k1, z, bias=b2p)
+        saved, ctx.dims, ctx.in_dtypes = _mlp_fwd(x, w1, b1, ln_w, ln_b, w2, b2, eps, shadows)
+        B, _, _, vs = ctx.dims
+        z = saved[0]
         loss = arg = score = y = None
         if targets is not None:
             if tuple(targets.shape) != (B, vs):
                 raise ValueError(f'vqa targets must be [{B}, {vs}], got {tuple(targets.shape)}')
-            y = targets.detach().to(torch.float32).contiguous()
-            rows = torch.empty(B, dtype=torch.float32, device=dev)
-            arg = torch.empty(B, dtype=torch.int32, device=dev)
-            score = torch.empty(B, dtype=torch.float32, device=dev)
-            hip.vqa_bce(z, y, B, vs, row_loss=rows, row_arg=arg, row_score=score)
-            loss = rows.sum() / B
+            y = _f32(targets)
+            loss, arg, score = _vqa_loss(z, y, B, vs)
             ctx.mark_non_differentiable(arg, score)
-        logits = z[:, :vs]
-        if out_dtype != torch.float32:
-            logits = logits.to(out_dtype)
-        ctx.save_for_backward(xb, u, h, mean, rstd, z, y, gf, bf, w1t, w2t)
-        ctx.dims = (B, hs, h2, vs, eps)
-        ctx.in_dtypes = (x.dtype, w1.dtype, b1.dtype, ln_w.dtype, ln_b.dtype, w2.dtype, b2.dtype)
-        return logits, loss, arg, score
+        ctx.save_for_backward(*saved, y)
+        return _logits_out(z, vs, out_dtype), loss, arg, score
 
     @staticmethod
     def backward(ctx, dlogits, dloss, _darg, _dscore):
-        xb, u, h, mean, rstd, z, y, gf, bf, w1t, w2t = ctx.saved_tensors
-        B, hs, h2, vs, eps = ctx.dims
-        dev = z.device
-        npad, k0, k1 = z.shape[1], xb.shape[1], h.shape[1]
-        dz = torch.empty((B, npad), dtype=torch.bfloat16, device=dev)
-        dadd = dlogits.to(torch.float32).contiguous() if dlogits is not None else None
-        with_loss = y is not None and dloss is not None
-        dscale = dloss.detach().to(torch.float32).reshape(1).contiguous() if with_loss else None
-        hip.vqa_bce(z, y if with_loss else None, B, vs, dscale=dscale, alpha=1.0 / B, dadd=dadd, dz=dz)
-        dh = torch.empty((B, k1), dtype=torch.float32, device=dev)
-        hip.gemm_nt(hip.EPI_F32, dz, w2t, B, k1, npad, dh)
-        dw2 = torch.zeros((npad, k1), dtype=torch.float32, device=dev)
-        hip.gemm_tn(dz, h, dw2, B, npad, k1)
-        db2 = torch.zeros(npad, dtype=torch.float32, device=dev)
-        for r0 in range(0, B, 1008):      # <= 1008 rows per call: one ordered add per column (reproducible)
-            r1 = min(B, r0 + 1008)
-            hip.colsum(dz[r0:r1], db2, r1 - r0, npad)
-        du = torch.empty((B, k1), dtype=torch.bfloat16, device=dev)
-        dg = torch.empty(h2, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(h2, dtype=torch.float32, device=dev)
-        db1 = torch.empty(h2, dtype=torch.float32, device=dev)
-        hip.ln_gelu_bwd(dh, u, gf, bf, mean, rstd, B, h2, dxb=du, dw=dg, db=dbeta, dbias=db1)
-        dx = torch.empty((B, hs), dtype=torch.float32, device=dev)
-        hip.gemm_nt(hip.EPI_F32, du, w1t, B, hs, k1, dx)
-        dw1 = torch.zeros((k1, k0), dtype=torch.float32, device=dev)
-        hip.gemm_tn(du, xb, dw1, B, k1, k0)
-        xd, w1d, b1d, gd, bd, w2d, b2d = ctx.in_dtypes
-        return (dx.to(xd), dw1[:h2, :hs].to(w1d), db1.to(b1d), dg.to(gd), dbeta.to(bd), dw2[:vs, :h2].to(w2d),
-                db2[:vs].to(b2d), None, None, None, None)
+        *saved, y = ctx.saved_tensors
+        B, _, _, vs = ctx.dims
+        dz = _vqa_dz(saved[0], y, B, vs, dlogits, dloss)
+        return _mlp_bwd(saved, ctx.dims, ctx.in_dtypes, dz) + (None,) * 4
 
 
 class VQAIsdaHeadFn(torch.autograd.Function):
@@ -227,83 +278,34 @@ class VQAIsdaHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, ln_w, ln_b, w2, b2, targets, eps, out_dtype, shadows, count, emean, cov, ratio):
         ctx.set_materialize_grads(False)
-        B, hs = x.shape
-        h2, vs = w1.shape[0], w2.shape[0]
+        B, h2, vs = x.shape[0], w1.shape[0], w2.shape[0]
         if targets is None or tuple(targets.shape) != (B, vs):
             raise ValueError(f'ISDA needs vqa targets [{B}, {vs}], got {None if targets is None else tuple(targets.shape)}')
         if tuple(cov.shape) != (vs, h2) or tuple(emean.shape) != (vs, h2) or tuple(count.shape) != (vs,):
             raise ValueError(f'ISDA estimator buffers must be [{vs}], [{vs}, {h2}], [{vs}, {h2}]')
-        w1s, w1t, w2s, w2t, b2p = shadows.get(w1, w2, b2)
-        k0, k1, npad = w1s.shape[1], w2s.shape[1], w2s.shape[0]
-        dev = x.device
-        xb = torch.zeros((B, k0), dtype=torch.bfloat16, device=dev) if k0 != hs else torch.empty((B, k0), dtype=torch.bfloat16, device=dev)
-        xb[:, :hs] = x.detach()
-        f32 = lambda t: t.detach().to(torch.float32).contiguous()
-        b1f, gf, bf = f32(b1), f32(ln_w), f32(ln_b)
-        u = torch.empty((B, h2), dtype=torch.float32, device=dev)
-        hip.gemm_nt(hip.EPI_F32, xb, w1s, B, h2, k0, u, bias=b1f)
-        h = torch.empty((B, k1), dtype=torch.bfloat16, device=dev)
-        mean = torch.empty(B, dtype=torch.float32, device=dev)
-        rstd = torch.empty(B, dtype=torch.float32, device=dev)
-        hip.ln_gelu_fwd(u, gf, bf, h, mean, rstd, B, h2, eps)
-        z = torch.empty((B, npad), dtype=torch.float32, device=dev)
-        hip.gemm_nt(hip.EPI_F32, h, w2s, B, npad, k1, z, bias=b2p)
-        y = targets.detach().to(torch.float32).contiguous()
-        k = torch.empty(B, dtype=torch.int32, device=dev)
+        saved, ctx.dims, ctx.in_dtypes = _mlp_fwd(x, w1, b1, ln_w, ln_b, w2, b2, eps, shadows)
+        z, _, u, _, mean, rstd, gf, bf, _, _ = saved
+        y = _f32(targets)
+        k = torch.empty(B, dtype=torch.int32, device=x.device)
         hip.isda_update(u, y, B, vs, h2, count, emean, cov, k, ln_mean=mean, ln_rstd=rstd, ln_w=gf, ln_b=bf)
-        ratio = float(ratio)
+        ctx.ratio = float(ratio)
         w2f = ck = None
-        if ratio != 0.0:
-            w2f = f32(w2)
+        if ctx.ratio != 0.0:
+            w2f = _f32(w2)
             ck = cov.index_select(0, k)            # cov[k_n] after the update, kept for the backward
-            hip.isda_aug_fwd(w2f, k, ck, B, vs, h2, 0.5 * ratio, z)
-        rows = torch.empty(B, dtype=torch.float32, device=dev)
-        arg = torch.empty(B, dtype=torch.int32, device=dev)
-        score = torch.empty(B, dtype=torch.float32, device=dev)
-        hip.vqa_bce(z, y, B, vs, row_loss=rows, row_arg=arg, row_score=score)
-        loss = rows.sum() / B
+            hip.isda_aug_fwd(w2f, k, ck, B, vs, h2, 0.5 * ctx.ratio, z)
+        loss, arg, score = _vqa_loss(z, y, B, vs)
         ctx.mark_non_differentiable(arg, score)
-        logits = z[:, :vs]
-        if out_dtype != torch.float32:
-            logits = logits.to(out_dtype)
-        ctx.save_for_backward(xb, u, h, mean, rstd, z, y, gf, bf, w1t, w2t, w2f, k, ck)
-        ctx.dims = (B, hs, h2, vs, eps, ratio)
-        ctx.in_dtypes = (x.dtype, w1.dtype, b1.dtype, ln_w.dtype, ln_b.dtype, w2.dtype, b2.dtype)
-        return logits, loss, arg, score
+        ctx.save_for_backward(*saved, y, w2f, k, ck)
+        return _logits_out(z, vs, out_dtype), loss, arg, score
 
     @staticmethod
     def backward(ctx, dlogits, dloss, _darg, _dscore):
-        xb, u, h, mean, rstd, z, y, gf, bf, w1t, w2t, w2f, k, ck = ctx.saved_tensors
-        B, hs, h2, vs, eps, ratio = ctx.dims
-        dev = z.device
-        npad, k0, k1 = z.shape[1], xb.shape[1], h.shape[1]
-        dz = torch.empty((B, npad), dtype=torch.bfloat16, device=dev)
-        dadd = dlogits.to(torch.float32).contiguous() if dlogits is not None else None
-        with_loss = dloss is not None
-        dscale = dloss.detach().to(torch.float32).reshape(1).contiguous() if with_loss else None
-        hip.vqa_bce(z, y if with_loss else None, B, vs, dscale=dscale, alpha=1.0 / B, dadd=dadd, dz=dz)
-        dh = torch.empty((B, k1), dtype=torch.float32, device=dev)
-        hip.gemm_nt(hip.EPI_F32, dz, w2t, B, k1, npad, dh)
-        dw2 = torch.zeros((npad, k1), dtype=torch.float32, device=dev)
-        hip.gemm_tn(dz, h, dw2, B, npad, k1)
-        if ratio != 0.0:
-            hip.isda_aug_bwd(dz, w2f, k, ck, B, vs, h2, ratio, dw2)
-        db2 = torch.zeros(npad, dtype=torch.float32, device=dev)
-        for r0 in range(0, B, 1008):      # <= 1008 rows per call: one ordered add per column (reproducible)
-            r1 = min(B, r0 + 1008)
-            hip.colsum(dz[r0:r1], db2, r1 - r0, npad)
-        du = torch.empty((B, k1), dtype=torch.bfloat16, device=dev)
-        dg = torch.empty(h2, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(h2, dtype=torch.float32, device=dev)
-        db1 = torch.empty(h2, dtype=torch.float32, device=dev)
-        hip.ln_gelu_bwd(dh, u, gf, bf, mean, rstd, B, h2, dxb=du, dw=dg, db=dbeta, dbias=db1)
-        dx = torch.empty((B, hs), dtype=torch.float32, device=dev)
-        hip.gemm_nt(hip.EPI_F32, du, w1t, B, hs, k1, dx)
-        dw1 = torch.zeros((k1, k0), dtype=torch.float32, device=dev)
-        hip.gemm_tn(du, xb, dw1, B, k1, k0)
-        xd, w1d, b1d, gd, bd, w2d, b2d = ctx.in_dtypes
-        return (dx.to(xd), dw1[:h2, :hs].to(w1d), db1.to(b1d), dg.to(gd), dbeta.to(bd), dw2[:vs, :h2].to(w2d),
-                db2[:vs].to(b2d), None, None, None, None, None, None, None, None)
+        *saved, y, w2f, k, ck = ctx.saved_tensors
+        B, _, h2, vs = ctx.dims
+        dz = _vqa_dz(saved[0], y, B, vs, dlogits, dloss)
+        aug = (lambda dw2: hip.isda_aug_bwd(dz, w2f, k, ck, B, vs, h2, ctx.ratio, dw2)) if ctx.ratio != 0.0 else None
+        return _mlp_bwd(saved, ctx.dims, ctx.in_dtypes, dz, aug) + (None,) * 8
 
 
 @torch.no_grad()
@@ -393,10 +395,8 @@ class MLMHead(nn.Module):
 
     def loss_and_pred(self, x, labels, ignore_index=-100):
         """fused decoder + cross-entropy: (mean loss over rows whose label is not ignore_index, arg-max [n])."""
-        if not hasattr(self, '_ce_shadows'):
-            object.__setattr__(self, '_ce_shadows', _PaddedShadows())
         return LinearCrossEntropyFn.apply(self.transform(x), self.decoder.weight, self.bias, labels, ignore_index,
-                                          self._ce_shadows)
+                                          lazy_attr(self, '_ce_shadows', _PaddedShadows))
 
 
 class MIMHead(nn.Module):
@@ -410,9 +410,8 @@ class MIMHead(nn.Module):
         return self.fc(x)
 
     def loss_and_pred(self, x, labels, ignore_index=-100):
-        if not hasattr(self, '_ce_shadows'):
-            object.__setattr__(self, '_ce_shadows', _PaddedShadows())
-        return LinearCrossEntropyFn.apply(x, self.fc.weight, self.fc.bias, labels, ignore_index, self._ce_shadows)
+        return LinearCrossEntropyFn.apply(x, self.fc.weight, self.fc.bias, labels, ignore_index,
+                                          lazy_attr(self, '_ce_shadows', _PaddedShadows))
 
 
 class ITCHead(nn.Module):

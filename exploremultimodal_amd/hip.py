@@ -192,19 +192,28 @@ def _dt(t):
     return {torch.bfloat16: BF16, torch.float16: F16, torch.float32: F32}[t.dtype]
 
 
-_WS = {}
+_SCRATCH = {}
+
+
+def _scratch(kind, device, nbytes, floor):
+    """Persistent fp32 scratch of at least ``nbytes`` (allocated no smaller than ``floor``), one per (kind, device,
+    stream): reuse is ordered by the stream, and kernels on different streams never share a buffer."""
+    key = (kind, device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _SCRATCH.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = torch.empty(max(nbytes, floor) // 4, dtype=torch.float32, device=device)
+        _SCRATCH[key] = ws
+    return ws
 
 
 def workspace(device, ncols):
-    """Persistent scratch for the column-reducing kernels, one per (device, stream): reuse is ordered by
-    the stream, and kernels on different streams never share a buffer."""
-    need = lib().vlmo_reduce_ws_bytes(ncols)
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _WS.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty(max(need, 1 << 23) // 4, dtype=torch.float32, device=device)
-        _WS[key] = ws
-    return ws
+    """Scratch of the column-reducing kernels."""
+    return _scratch('reduce', device, lib().vlmo_reduce_ws_bytes(ncols), 1 << 23)
+
+
+def tn_workspace(device, nbytes):
+    """Slab scratch of the weight-gradient GEMM."""
+    return _scratch('tn', device, nbytes, 1 << 24)
 
 
 def drop_params(p, training):
@@ -215,18 +224,26 @@ def drop_params(p, training):
     return thresh, 65536.0 / (65536 - thresh)
 
 
+def _seed64(seed):
+    return seed & 0xFFFFFFFFFFFFFFFF
+
+
+def _epilogue(out, *, out2=None, bias=None, gamma=None, resid=None, row_scale=None, row_index=None, aux=None, ldo=None,
+              ld2=None, relu=False, drop=(0, 1.0), seed=0, beta=0.0, colpart=None):
+    """The Epilogue of one GEMM / convolution; ldo defaults to out's row stride, ld2 to out2's, else aux's, else 0."""
+    if ld2 is None:
+        ld2 = out2.stride(0) if out2 is not None else (aux.stride(0) if aux is not None else 0)
+    return Epilogue(_p(out), _p(out2), _p(bias), _p(gamma), _p(resid), _p(row_scale), _p(row_index), _p(aux),
+                    ldo if ldo is not None else out.stride(0), ld2, int(relu), drop[0], drop[1], beta, _seed64(seed),
+                    _p(colpart))
+
+
 # ------------------------------------------------------------------ wrappers
 
-def gemm_nt(epi, A, B, M, N, K, out, *, out2=None, bias=None, gamma=None, resid=None,
-            row_scale=None, row_index=None, aux=None, ldo=None, ld2=None, relu=False, drop=(0, 1.0), seed=0,
-            beta=0.0, tile=-1, lda=None, ldb=None, colpart=None, A2=None, k1=0, seg_scale=1.0):
-    """A2 / k1 / seg_scale: two-segment reduction (vlmo_gemm_nt_2src): columns [0, k1) of B meet A, [k1, K) meet A2, the
-    first segment's partial sum is multiplied by seg_scale."""
-    e = Epilogue(_p(out), _p(out2), _p(bias), _p(gamma), _p(resid), _p(row_scale), _p(row_index), _p(aux),
-                 ldo if ldo is not None else out.stride(0),
-                 ld2 if ld2 is not None else (out2.stride(0) if out2 is not None else
-                                              (aux.stride(0) if aux is not None else 0)),
-                 int(relu), drop[0], drop[1], beta, seed & 0xFFFFFFFFFFFFFFFF, _p(colpart))
+def gemm_nt(epi, A, B, M, N, K, out, *, tile=-1, lda=None, ldb=None, A2=None, k1=0, seg_scale=1.0, **epilogue):
+    """``epilogue``: the keywords of ``_epilogue``.  A2 / k1 / seg_scale: two-segment reduction (vlmo_gemm_nt_2src):
+    columns [0, k1) of B meet A, [k1, K) meet A2, the first segment's partial sum is multiplied by seg_scale."""
+    e = _epilogue(out, **epilogue)
     if A2 is not None:
         rc = lib().vlmo_gemm_nt_2src(epi, _dt(A), tile, _p(A), lda if lda is not None else A.stride(0), k1,
                                      float(seg_scale), _p(A2), A2.stride(0), _p(B),
@@ -245,33 +262,12 @@ def gemm_nt_grouped(epi, As, Bs, Ms, N, K, outs, *, per_group=None, tile=-1, **c
     n = len(As)
     es = (Epilogue * n)()
     for g in range(n):
-        kw = dict(common)
-        kw.update((per_group or [{}] * n)[g])
-        out, out2, aux = outs[g], kw.get('out2'), kw.get('aux')
-        drop = kw.get('drop', (0, 1.0))
-        es[g] = Epilogue(_p(out), _p(out2), _p(kw.get('bias')), _p(kw.get('gamma')), _p(kw.get('resid')),
-                         _p(kw.get('row_scale')), _p(kw.get('row_index')), _p(aux), out.stride(0),
-                         out2.stride(0) if out2 is not None else (aux.stride(0) if aux is not None else 0),
-                         int(kw.get('relu', False)), drop[0], drop[1], kw.get('beta', 0.0),
-                         kw.get('seed', 0) & 0xFFFFFFFFFFFFFFFF, _p(kw.get('colpart')))
+        es[g] = _epilogue(outs[g], **{**common, **(per_group[g] if per_group else {})})
     pa = (ctypes.c_void_p * n)(*[_p(a) for a in As])
     pb = (ctypes.c_void_p * n)(*[_p(b) for b in Bs])
     ms = (ctypes.c_int32 * n)(*Ms)
     rc = lib().vlmo_gemm_nt_grouped(epi, _dt(As[0]), tile, n, pa, As[0].stride(0), pb, Bs[0].stride(0), ms, N, K, es, _stream())
     _check(rc, 'vlmo_gemm_nt_grouped')
-
-
-_WS_TN = {}
-
-
-def tn_workspace(device, nbytes):
-    """Persistent slab scratch of the weight-gradient GEMM, one per (device, stream)."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _WS_TN.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = torch.empty(max(nbytes, 1 << 24) // 4, dtype=torch.float32, device=device)
-        _WS_TN[key] = ws
-    return ws
 
 
 def gemm_tn(A, B, C, M, N1, N2, alpha=1.0, splits=0, slab=True):
@@ -300,14 +296,14 @@ def ln_resid_bwd(dy, x, w, mean, rstd, dres, dx, dw, db, zd, gamma, row_scale, r
     ws = workspace(x.device, 4 * d)
     rc = lib().vlmo_ln_resid_bwd(_p(dy), _p(x), _p(w), _p(mean), _p(rstd), _p(dres), _p(dx), _p(dw), _p(db), _p(zd),
                                  _p(gamma), _p(row_scale), _p(row_index), _p(dz), _p(dgamma), _p(dbias), drop[0], drop[1],
-                                 seed & 0xFFFFFFFFFFFFFFFF, M, d, _p(ws), ws.numel() * 4, _stream())
+                                 _seed64(seed), M, d, _p(ws), ws.numel() * 4, _stream())
     _check(rc, 'vlmo_ln_resid_bwd')
 
 
 def attn_fwd(qkv, seg, nseq, keymask, ctx, lse, heads, d, max_len, scale, drop=(0, 1.0), seed=0, mask_seq0=0):
     rc = lib().vlmo_attn_fwd(_p(qkv), _p(seg), nseq, _p(keymask), _p(ctx), _p(lse),
                              lse.stride(0) if lse is not None else 0, heads, d, max_len, scale,
-                             drop[0], drop[1], seed & 0xFFFFFFFFFFFFFFFF, mask_seq0, _stream())
+                             drop[0], drop[1], _seed64(seed), mask_seq0, _stream())
     _check(rc, 'vlmo_attn_fwd')
 
 
@@ -315,14 +311,14 @@ def attn_bwd(qkv, ctx, dctx, lse, seg, nseq, keymask, dqkv, heads, d, max_len, s
              drop=(0, 1.0), seed=0, qv_colsum=None, mask_seq0=0):
     rc = lib().vlmo_attn_bwd(_p(qkv), _p(ctx), _p(dctx), _p(lse), lse.stride(0), _p(seg), nseq,
                              _p(keymask), _p(dqkv), _p(qv_colsum), heads, d, max_len, scale, drop[0], drop[1],
-                             seed & 0xFFFFFFFFFFFFFFFF, mask_seq0, _stream())
+                             _seed64(seed), mask_seq0, _stream())
     _check(rc, 'vlmo_attn_bwd')
 
 
 def resid_bwd(dx, zd, gamma, row_scale, dz, dgamma, dbias, M, d, drop=(0, 1.0), seed=0, row_index=None):
     ws = workspace(dx.device, 2 * d)
     rc = lib().vlmo_resid_bwd(_p(dx), _p(zd), _p(gamma), _p(row_scale), _p(row_index), _p(dz), _p(dgamma),
-                              _p(dbias), M, d, drop[0], drop[1], seed & 0xFFFFFFFFFFFFFFFF,
+                              _p(dbias), M, d, drop[0], drop[1], _seed64(seed),
                               _p(ws), ws.numel() * 4, _stream())
     _check(rc, 'vlmo_resid_bwd')
 
@@ -364,7 +360,7 @@ def embed_img_finish(proj, cls_tok, mask_tok, pos, type_row, masked, x, B, npatc
                      drop=(0, 1.0), seed=0):
     rc = lib().vlmo_embed_img_finish(_p(proj), _p(cls_tok), _p(mask_tok), _p(pos), _p(type_row),
                                      _p(masked), _p(x), B, npatch, d, drop[0], drop[1],
-                                     seed & 0xFFFFFFFFFFFFFFFF, _stream())
+                                     _seed64(seed), _stream())
     _check(rc, 'vlmo_embed_img_finish')
 
 
@@ -372,7 +368,7 @@ def embed_img_bwd(dx, masked, dproj, dcls, dmask, dpos, dtype_row, B, npatch, d,
                   seed=0):
     rc = lib().vlmo_embed_img_bwd(_p(dx), _p(masked), _p(dproj), _p(dcls), _p(dmask), _p(dpos),
                                   _p(dtype_row), B, npatch, d, drop[0], drop[1],
-                                  seed & 0xFFFFFFFFFFFFFFFF, _stream())
+                                  _seed64(seed), _stream())
     _check(rc, 'vlmo_embed_img_bwd')
 
 
@@ -380,7 +376,7 @@ def embed_txt_fwd(ids, word, pos, btype0, ln_w, ln_b, type0, x, xhat, rstd, B, T
                   drop=(0, 1.0), seed=0):
     rc = lib().vlmo_embed_txt_fwd(_p(ids), _p(word), _p(pos), _p(btype0), _p(ln_w), _p(ln_b),
                                   _p(type0), _p(x), _p(xhat), _p(rstd), B, T, d, eps, drop[0],
-                                  drop[1], seed & 0xFFFFFFFFFFFFFFFF, _stream())
+                                  drop[1], _seed64(seed), _stream())
     _check(rc, 'vlmo_embed_txt_fwd')
 
 
@@ -388,7 +384,7 @@ def embed_txt_bwd(dx, ids, xhat, rstd, ln_w, dword, dpos, dbtype0, dln_w, dln_b,
                   drop=(0, 1.0), seed=0):
     rc = lib().vlmo_embed_txt_bwd(_p(dx), _p(ids), _p(xhat), _p(rstd), _p(ln_w), _p(dword),
                                   _p(dpos), _p(dbtype0), _p(dln_w), _p(dln_b), _p(dtype0), B, T, d,
-                                  drop[0], drop[1], seed & 0xFFFFFFFFFFFFFFFF, _stream())
+                                  drop[0], drop[1], _seed64(seed), _stream())
     _check(rc, 'vlmo_embed_txt_bwd')
 
 
@@ -407,9 +403,7 @@ def zero_page(device):
 def conv2d_nhwc(epi, x, B, H, W, Cin, kw, w, Cout, out, *, out2=None, bias=None, resid=None, relu=False,
                 relu_in=False, beta=0.0, ldo=None):
     """relu: ReLU on the output; relu_in: the convolution reads relu(x) (applied to the fragments, x stays as it is)."""
-    e = Epilogue(_p(out), _p(out2), _p(bias), None, _p(resid), None, None, None,
-                 ldo if ldo is not None else out.stride(0), out2.stride(0) if out2 is not None else 0,
-                 int(relu) | (2 if relu_in else 0), 0, 1.0, beta, 0)
+    e = _epilogue(out, out2=out2, bias=bias, resid=resid, relu=int(relu) | (2 if relu_in else 0), beta=beta, ldo=ldo)
     rc = lib().vlmo_conv2d_nhwc(epi, _dt(x), _p(x), B, H, W, Cin, kw, _p(w), Cout, _p(zero_page(x.device)),
                                 ctypes.byref(e), _stream())
     _check(rc, 'vlmo_conv2d_nhwc')

@@ -282,20 +282,19 @@ def _vqa_head(model, feats, targets, isda=False):
     head = model.vqa_classifier
     last = model.vqa_last
     if feats.is_cuda:
-        from .heads import VQAHeadFn, VQAIsdaHeadFn, _VQAShadows
+        from .heads import VQAHeadFn, VQAIsdaHeadFn, _VQAShadows, lazy_attr
         fc1, ln = head[0], head[1]
         fc2 = head[3] if last is None else last
-        if not hasattr(model, '_vqa_shadows'):
-            object.__setattr__(model, '_vqa_shadows', _VQAShadows())
+        shadows = lazy_attr(model, '_vqa_shadows', _VQAShadows)
         out_dtype = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else torch.float32
         if isda:
             est = model.isda_head.estimator
             logits, loss, _, score_rows = VQAIsdaHeadFn.apply(
                 feats, fc1.weight, fc1.bias, ln.weight, ln.bias, fc2.weight, fc2.bias, targets, ln.eps, out_dtype,
-                model._vqa_shadows, est.count, est.mean, est.cov, isda_ratio(model.config.train))
+                shadows, est.count, est.mean, est.cov, isda_ratio(model.config.train))
         else:
             logits, loss, _, score_rows = VQAHeadFn.apply(feats, fc1.weight, fc1.bias, ln.weight, ln.bias, fc2.weight,
-                                                          fc2.bias, targets, ln.eps, out_dtype, model._vqa_shadows)
+                                                          fc2.bias, targets, ln.eps, out_dtype, shadows)
         return logits, loss, (score_rows.sum() / feats.shape[0] if score_rows is not None else None)
     logits = head(feats)
     if last is not None:
