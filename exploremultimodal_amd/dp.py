@@ -467,12 +467,12 @@ class GradReducer:
             if groups is None or getattr(fn, 'sink', None) is not self:
                 continue
             engine_nodes.add(fn)
-            flat = groups if (groups and isinstance(groups[0], tuple)) else [g_ for blk in groups for g_ in blk]
-            for g_ in flat:
-                k = self._key(g_)
-                counts[k] = counts.get(k, 0) + 1
-                for p in g_:
-                    key_of[id(p)] = k
+            for blk in groups:              # sink_groups: per block, its parameter groups
+                for g_ in blk:
+                    k = self._key(g_)
+                    counts[k] = counts.get(k, 0) + 1
+                    for p in g_:
+                        key_of[id(p)] = k
         # A sink parameter that ALSO receives a gradient from an op outside the engine (a weight regulariser, a weight
         # reused by a head): its AccumulateGrad node adds that contribution into p.grad -- the bucket view the engine
         # set -- in place, once every producer has run, i.e. possibly after the engine released the bucket.  Such a

@@ -12,7 +12,9 @@ The residual stream is fp32 (as under the reference's autocast), GEMM operands
 bf16 with fp32 accumulation, parameters fp32 masters with cached bf16 shadows.
 """
 import ctypes
+import os as _os
 import sys
+from collections import namedtuple
 
 import torch
 
@@ -20,7 +22,6 @@ from . import hip
 
 LN_EPS = 1e-12          # vlmo_module.py:21-23
 GRAD_SINK = None         # set by dp.GradReducer: block gradients are accumulated straight into its flat buckets
-import os as _os
 # Weight-gradient GEMMs + bias column sums on a side stream: '1' always, '0' never, unset = by the rule below.
 # The GEMM kernels take whole CUs (128 KB of LDS, every vector register), so two streams time-slice the chip instead of
 # sharing it: the overlap pays only where the main stream's kernels leave CUs idle (short kernels, partial dispatch
@@ -40,6 +41,8 @@ def _use_side_stream(sink, rows):
     if OVERLAP_WGRAD is not None:
         return OVERLAP_WGRAD
     return sink is not None or rows < ONE_STREAM_ROWS
+
+
 DEFAULT_TILE = -1        # GEMM tile: -1 = chosen per shape by the library (see vlmo_gemm_nt)
 
 
@@ -195,10 +198,6 @@ class BlockMeta:
         self.tile = DEFAULT_TILE
 
 
-def _empty(shape, dtype, dev):
-    return torch.empty(shape, dtype=dtype, device=dev)
-
-
 _SIDE = {}
 
 
@@ -266,35 +265,43 @@ def pick_stream(dev, make, against, tries=8):
     return first
 
 
-class _Fork:
-    """Run weight-gradient work on a side stream: fork() after the producers were enqueued on the main
-    stream, join() before the buffers it reads may be reused.  Off = everything on the main stream."""
+# ---- the per-block parameter order -------------------------------------------------------------------------------
+# vlmo.Block._params is its single producer: N_SHARED tensors every row of the block uses (gamma_1, gamma_2, norm1 w / b,
+# qkv_w, q_bias, v_bias, proj_w, proj_b, norm2 w / b), then N_EXPERT per expert FFN of the call (fc1_w, fc1_b, fc2_w,
+# fc2_b).  The shared tensors and each expert are one parameter GROUP: one flat gradient bucket, one reducer bucket, one
+# unit of in-place accumulation.  Everything below that needs the order goes through block_groups().
+N_SHARED, N_EXPERT = 11, 4
+QKV_W, PROJ_W = 4, 7            # the weight matrices inside the shared group
+FC1_W, FC2_W = 0, 2             # ... and inside an expert group
+ARENA_EXPERTS = 3               # experts a block can own (v, l, vl): the room of its reducer arena
 
-    def __init__(self, dev, enabled):
-        self.main = torch.cuda.current_stream(dev)
-        self.side = _side_stream(dev) if enabled else None
-
-    def __enter__(self):
-        if self.side is not None:
-            self.side.wait_stream(self.main)
-            self._ctx = torch.cuda.stream(self.side)
-            self._ctx.__enter__()
-        return self
-
-    def __exit__(self, *a):
-        if self.side is not None:
-            self._ctx.__exit__(*a)
-
-    def join(self):
-        if self.side is not None:
-            self.main.wait_stream(self.side)
+Group = namedtuple('Group', 'params lo hi')     # params == tuple(block parameter list[lo:hi]); lo == 0: the shared group
 
 
-def _fill_forward(D, meta, params, launches, lse_sizes, M, pb, pf, need_bwd, keep):
+def block_groups(bp):
+    """One block's parameter list (per-block order) as its groups: the shared group, then one per expert."""
+    nexp, rest = divmod(len(bp) - N_SHARED, N_EXPERT)
+    if nexp < 1 or rest:
+        raise ValueError(f'{len(bp)} tensors are not a block parameter list ({N_SHARED} shared + {N_EXPERT} per expert)')
+    cuts = [0] + [N_SHARED + N_EXPERT * e for e in range(nexp + 1)]
+    return [Group(tuple(bp[lo:hi]), lo, hi) for lo, hi in zip(cuts, cuts[1:])]
+
+
+def group_numel(g, d, hid):
+    """Elements of the group's flat gradient bucket (what _fill_grads carves; the shared one includes the k-bias hole)."""
+    return 2 * hid * d + hid + d if g.lo else 6 * d + 3 * d * d + d * d + d + 3 * d
+
+
+def group_layout(g, d, hid):
+    """[(parameter, offset)] of the group inside its flat gradient bucket."""
+    return expert_layout(g.params, d, hid) if g.lo else shared_layout(g.params, d)
+
+
+def _fill_forward(D, meta, groups, launches, lse_sizes, M, pb, pf, need_bwd, keep):
     """Forward part of a VlmoBlockDesc: geometry, parameters (fp32 vectors, bf16 weight shadows) and the saved-
-    activation slabs at pb (bf16) / pf (fp32).  params in per-block order (vlmo.Block._params); x / x2 are set by the
-    caller."""
-    (g1, g2, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b) = params[:11]
+    activation slabs at pb (bf16) / pf (fp32).  groups: block_groups() of the block's parameters; x / x2 are set by
+    the caller."""
+    (g1, g2, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b) = groups[0].params
     nexp = len(meta.expert_ranges)
     pl, d, H, hid = meta.plan, meta.d, meta.heads, meta.hidden
     sh = meta.shadows
@@ -334,8 +341,8 @@ def _fill_forward(D, meta, params, launches, lse_sizes, M, pb, pf, need_bwd, kee
     w, wt = sh.get(proj_w)
     D.proj_w, D.proj_wT = w.data_ptr(), wt.data_ptr()
     keep += [w, wt]
-    for i in range(nexp):
-        w1, b1, w2, b2 = params[11 + 4 * i: 15 + 4 * i]
+    for i, g in enumerate(groups[1:]):
+        w1, b1, w2, b2 = g.params
         a, at = sh.get(w1)
         c, ct = sh.get(w2)
         D.w1[i], D.w1T[i], D.w2[i], D.w2T[i] = a.data_ptr(), at.data_ptr(), c.data_ptr(), ct.data_ptr()
@@ -383,7 +390,7 @@ def _carve(flat, shapes):
 def shared_layout(params, d):
     """[(parameter, offset)] of a block's shared-parameter group inside its flat gradient bucket (the carve order of
     _fill_grads; params in per-block order).  q_bias / v_bias sit at the two ends of the 3d-wide qkv-bias slot."""
-    (g1, g2, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b) = params[:11]
+    (g1, g2, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b) = params[:N_SHARED]
     o = 6 * d
     out = [(g1, 0), (g2, d), (n1w, 2 * d), (n1b, 3 * d), (n2w, 4 * d), (n2b, 5 * d), (qkv_w, o)]
     o += 3 * d * d
@@ -441,6 +448,8 @@ def wgrad_batch_for(d, hid, cus=256, max_batch=4):
         if best_cost is None or cost < best_cost - 1e-9:
             best, best_cost = b, cost
     return best
+
+
 TMP_SETS = 4                                                     # rotation depth of the backward temporaries
 USE_STACK = True      # one StackFn call per pass; False (tests: no cross-block logic): one StackFn call per block
 
@@ -599,7 +608,7 @@ def _task_flats(node):
 
 def _group_key(gparams):
     # a weight matrix of the group (qkv weight / fc1 weight): gamma_1 may be a stand-in shared by all blocks (init_values=None)
-    return gparams[4].data_ptr() if len(gparams) == 11 else gparams[0].data_ptr()
+    return gparams[QKV_W if len(gparams) == N_SHARED else FC1_W].data_ptr()
 
 
 def _grad_flat(gparams, n):
@@ -628,6 +637,138 @@ def _same_views(layout, flat):
     return True
 
 
+# ---- the steps of StackFn.backward -------------------------------------------------------------------------------
+_Scratch = namedtuple('_Scratch', 'nsets batch tb ws ws_n dxs')
+
+
+def _backward_scratch(dev, nb, M, d, hid, B):
+    """Scratch sizing: how many sets of backward temporaries rotate (nsets) and how many blocks share one deferred
+    weight-gradient launch (batch), and the three persistent buffers: tb, the bf16 temporaries
+    (dz2 | du(4) | dy2=dctx | dz1 | dqkv(3) | dy1), one set per block in flight; ws, per set the column-fold slots + the
+    du column partials of the DGELU epilogue + the attention backward's per-sequence dq | dv sums (ws_n fp32 each);
+    dxs, the dx ping-pong and dx1."""
+    want = wgrad_batch_for(d, hid)
+    nsets = max(1, min(max(TMP_SETS, want + 1), nb))
+    batch = max(1, min(want, nsets - 1)) if nb > nsets else max(1, want)
+    md = M * d
+    tb = _persist(dev, 'tb', nsets * 11 * md, torch.bfloat16)
+    slot = hip.lib().vlmo_reduce_ws_bytes(2 * d)
+    ws_n = 6 * slot // 4 + (M // 16 + 4) * hid + 4 * B * d
+    ws = _persist(dev, 'ws', nsets * ws_n, torch.float32)
+    dxs = _persist(dev, 'dx', 3 * md, torch.float32)
+    return _Scratch(nsets, batch, tb, ws, ws_n, dxs)
+
+
+def _sink_buckets(sink, groups, d, hid, dev):
+    """Sink route: the buckets of one block from the gradient reducer, [(flat, fresh)] per group.  The groups of a block
+    sit next to each other in one arena (named by the block's first parameter, with room for every expert the block
+    owns) so that the reducer sends them as one collective; fresh = nothing fed the bucket yet in this window."""
+    akey = id(groups[0].params[0])
+    aroom = group_numel(groups[0], d, hid) + ARENA_EXPERTS * group_numel(groups[1], d, hid)
+    return [sink.acquire(g.params, group_numel(g, d, hid), dev, akey, aroom, layout=group_layout(g, d, hid), lazy_zero=True)
+            for g in groups]
+
+
+FRESH, FROM_TASK, FROM_GRAD = 0, 1, 2       # where _local_bucket found a group's bucket
+
+
+def _local_bucket(g, d, hid, wanted, reg, permitted, into_grad, fresh):
+    """Local route (no reducer): the gradient bucket of ONE group and how it was obtained.
+    wanted: the graph task asks for the gradient of every trainable parameter of the group -- accumulating in place is
+    only considered then.  reg: the running task's {group key: flat} when an inplace_passes() walk permitted this node,
+    else None; permitted: the group keys that walk found to have no other producer; into_grad: inside
+    accumulate_into_grad(); fresh(): new storage for the bucket.
+      FROM_TASK  an earlier node of this graph task registered a buffer for the group: accumulate into it;
+      FROM_GRAD  the parameters hold exactly this layout's views of one flat buffer as .grad, unhooked (an earlier
+                 backward of the step): accumulate into that;
+      FRESH      new storage, handed to autograd -- and registered for the later nodes of the task only when the walk
+                 permitted the group."""
+    key = _group_key(g.params)
+    if wanted:
+        if reg is not None and key in reg:
+            return reg[key], FROM_TASK
+        if into_grad:
+            have = _grad_flat(g.params, group_numel(g, d, hid))
+            if have is not None and _same_views(group_layout(g, d, hid), have):
+                return have, FROM_GRAD
+    flat = fresh()
+    if wanted and reg is not None and key in permitted:
+        reg[key] = flat
+    return flat, FRESH
+
+
+def _local_buckets(groups, wants, d, hid, reg, permitted, into_grad, storage, off):
+    """Local route for one block: [(flat, fresh)] per group like _sink_buckets, and the storage offset behind the block.
+    wants: needs_input_grad of the block's parameters; storage(off, n): fresh storage (every group has its place in
+    it, taken or not)."""
+    got = []
+    for g in groups:
+        n = group_numel(g, d, hid)
+        wanted = all(w or not p_.requires_grad for p_, w in zip(g.params, wants[g.lo:g.hi]))
+        flat, how = _local_bucket(g, d, hid, wanted, reg, permitted, into_grad, lambda: storage(off, n))
+        got.append((flat, how == FRESH))
+        off += n
+    return got, off
+
+
+def _fresh_storage(numel, dev):
+    """storage(off, n) -> [off, off + n) of ONE fp32 buffer of `numel` elements, allocated when first asked for."""
+    whole = []
+
+    def storage(off, n):
+        if not whole:
+            whole.append(torch.empty(numel, dtype=torch.float32, device=dev))
+        return whole[0][off:off + n]
+    return storage
+
+
+def _wire_temporaries(D, k, nb, md, sc, dxo, dx_in):
+    """Temporaries of the k-th block the backward processes: its set of the rotating bf16 temporaries and workspaces,
+    and the dx chain (dx2 = incoming: dxo for the first, else the previous block's dx0; dx0 = outgoing: dx_in for the
+    last, else the other half of the ping-pong)."""
+    st_ = k % sc.nsets
+    pb = sc.tb.data_ptr() + st_ * 11 * md * 2
+    md2 = md * 2
+    D.dz2, D.du, D.dy2, D.dz1, D.dqkv, D.dy1 = pb, pb + md2, pb + 5 * md2, pb + 6 * md2, pb + 7 * md2, pb + 10 * md2
+    D.dctx = D.dy2
+    D.ws_main, D.ws_bytes = sc.ws.data_ptr() + st_ * sc.ws_n * 4, sc.ws_n * 4
+    D.dx1 = sc.dxs.data_ptr() + 2 * md * 4
+    D.dx2 = dxo.data_ptr() if k == 0 else sc.dxs.data_ptr() + ((k - 1) % 2) * md * 4
+    D.dx0 = dx_in.data_ptr() if k == nb - 1 else sc.dxs.data_ptr() + (k % 2) * md * 4
+
+
+def _zero_buckets(acquired, store_ok, d, hid):
+    """Zeroing.  acquired: (flat, fresh, is_expert) of every bucket of the pass.  In store mode (every bucket fresh) the
+    deferred launches WRITE the weight-gradient matrices, so only the vector gradients (accumulated with atomics by the
+    column folds) are zeroed, in one multi-tensor fill: [g1 g2 n1w n1b n2w n2b | qkv_w proj_w | proj_b qkv_b] and
+    [w1 | b1 | w2 | b2].  Otherwise the launches accumulate, and the fresh buckets are zeroed whole."""
+    if store_ok:
+        vecs = []
+        for f_, _, is_exp in acquired:
+            vecs += [f_[hid * d:hid * d + hid], f_[2 * hid * d + hid:]] if is_exp else [f_[:6 * d], f_[6 * d + 4 * d * d:]]
+        torch._foreach_zero_(vecs)
+    else:
+        for f_, fr, _ in acquired:
+            if fr:
+                f_.zero_()
+
+
+def _hand_to_sink(sink, groups, spans, grads_all, evs):
+    """Hand-off under a reducer, block by block in backward order: the parameters take their bucket views as .grad
+    (autograd is handed nothing), then the block's buckets are released behind its grad_ready event."""
+    for i in reversed(range(len(groups))):
+        o = spans[i][0]
+        for g in groups[i]:
+            for p_, g_ in zip(g.params, grads_all[o + g.lo:o + g.hi]):
+                if p_.requires_grad:
+                    if p_.grad is None:
+                        p_.grad = g_
+                    elif p_.grad.data_ptr() != g_.data_ptr():
+                        raise RuntimeError('a parameter of a data-parallel block already holds a foreign .grad; '
+                                           'use zero_grad(set_to_none=True)')
+        sink.release_all([g.params for g in groups[i]], ready_event=evs[i] if evs is not None else None)
+
+
 class StackFn(torch.autograd.Function):
     """All Blocks of one backbone pass (the loops at vlmo.py:402-411) as ONE native call per direction
     (vlmo_stack_fwd / vlmo_stack_bwd).  metas: one BlockMeta per block, in forward order; params: the blocks'
@@ -642,6 +783,12 @@ class StackFn(torch.autograd.Function):
         need_bwd = any(ctx.needs_input_grad)
         x = x.contiguous()
         md = M * d
+        spans, groups, pofs = [], [], 0     # per block: (offset, count) in params, and its parameter groups
+        for mt in metas:
+            npar = N_SHARED + N_EXPERT * len(mt.expert_ranges)
+            spans.append((pofs, npar))
+            groups.append(block_groups(params[pofs:pofs + npar]))
+            pofs += npar
         # per block: one bf16 slab  y1 | qkv(3) | ctx | zd1 | y2 | u(4) | h(4) | zd2  (units of M*d) and one fp32
         # slab  x1 | mean1 rstd1 mean2 rstd2 | lse...  ; the blocks' outputs x2 (= the next block's saved input)
         lse_sizes, launches = [], []
@@ -657,28 +804,19 @@ class StackFn(torch.autograd.Function):
         descs = (hip.BlockDesc * nb)()
         keep = [SB, SF, X2, pl]
         if m0.shadows is not None:          # every stale weight shadow of the pass in one launch (ShadowCache.refresh)
-            stale, po = [], 0
-            for mt in metas:
-                ne = len(mt.expert_ranges)
-                bp = params[po:po + 11 + 4 * ne]
-                po += 11 + 4 * ne
-                stale += [bp[4], bp[7]] + [bp[11 + 4 * e] for e in range(ne)] + [bp[13 + 4 * e] for e in range(ne)]
+            stale = []
+            for (sh, *ex) in groups:
+                stale += [sh.params[QKV_W], sh.params[PROJ_W]] + [g.params[FC1_W] for g in ex] + [g.params[FC2_W] for g in ex]
             m0.shadows.refresh(stale)
-        pofs, sf_off = 0, 0
+        sf_off = 0
         xin = x.data_ptr()
-        spans = []
         for i, mt in enumerate(metas):
-            nexp = len(mt.expert_ranges)
-            npar = 11 + 4 * nexp
-            bp = params[pofs:pofs + npar]
-            spans.append((pofs, npar))
-            pofs += npar
             D = descs[i]
             pb = SB.data_ptr() + (i * 16 * md * 2 if need_bwd else 0)
             pf = SF.data_ptr() + (sf_off * 4 if need_bwd else 0)
             sf_off += sf_n[i]
             x2 = X2[i if need_bwd else i % 2]
-            _fill_forward(D, mt, bp, launches[i], lse_sizes[i], M, pb, pf, need_bwd, keep)
+            _fill_forward(D, mt, groups[i], launches[i], lse_sizes[i], M, pb, pf, need_bwd, keep)
             D.x, D.x2 = xin, x2.data_ptr()
             xin = x2.data_ptr()
         S = hip.StackDesc()
@@ -687,144 +825,59 @@ class StackFn(torch.autograd.Function):
         hip.stack_fwd(S)
         out = X2[(nb - 1) if need_bwd else (nb - 1) % 2]
         if need_bwd:
-            ctx.metas, ctx.descs, ctx.keep, ctx.spans = metas, descs, keep, spans
+            ctx.metas, ctx.descs, ctx.keep, ctx.spans, ctx.groups = metas, descs, keep, spans, groups
             ctx.save_for_backward(x, *params)
             ctx.sink = GRAD_SINK
             if ctx.sink is None:
                 # the parameter groups this node produces gradients for, read by inplace_passes()' graph walk
-                ctx.grad_groups = []
-                for (o, n_) in spans:
-                    bp = params[o:o + n_]
-                    ctx.grad_groups += [(_group_key(g_), tuple(g_))
-                                        for g_ in [bp[:11]] + [bp[11 + 4 * e: 15 + 4 * e] for e in range((n_ - 11) // 4)]]
+                ctx.grad_groups = [(_group_key(g.params), g.params) for blk in groups for g in blk]
             else:
-                ctx.sink_groups = []
-                for (o, n_) in spans:
-                    bp = params[o:o + n_]
-                    groups = [tuple(bp[:11])] + [tuple(bp[11 + 4 * e: 15 + 4 * e]) for e in range((n_ - 11) // 4)]
-                    ctx.sink_groups.append(groups)
-                    for g_ in groups:
-                        ctx.sink.expect(g_)
+                # ... and, per block, by the reducer's (dp.GradReducer.prepare), which counts one backward call per group
+                ctx.sink_groups = [[g.params for g in blk] for blk in groups]
+                for blk in ctx.sink_groups:
+                    for gp in blk:
+                        ctx.sink.expect(gp)
         return out
 
     @staticmethod
     def backward(ctx, dxo):
-        metas, descs, spans = ctx.metas, ctx.descs, ctx.spans
+        metas, descs, spans, groups = ctx.metas, ctx.descs, ctx.spans, ctx.groups
         _released(descs)
         x, *params = ctx.saved_tensors
         nb = len(metas)
         m0 = metas[0]
         d, hid = m0.d, m0.hidden
         M, dev = x.shape[0], x.device
-        md = M * d
-        f32 = torch.float32
         dxo = dxo.contiguous()
         sink = ctx.sink
-        shared_n = 6 * d + 3 * d * d + d * d + d + 3 * d
-        exp_n = 2 * hid * d + hid + d
-        want = wgrad_batch_for(d, hid)
-        nsets = max(1, min(max(TMP_SETS, want + 1), nb))
-        batch = max(1, min(want, nsets - 1)) if nb > nsets else max(1, want)
-        # persistent scratch: backward temporaries (dz2 | du(4) | dy2=dctx | dz1 | dqkv(3) | dy1 bf16) and column
-        # workspaces, one set per block in flight; dx1 and the dx ping-pong
-        tb = _persist(dev, 'tb', nsets * 11 * md, torch.bfloat16)
-        slot = hip.lib().vlmo_reduce_ws_bytes(2 * d)
-        # column-fold slots + the du column partials of the DGELU epilogue + the attention backward's per-sequence dq | dv sums
-        ws_n = 6 * slot // 4 + (M // 16 + 4) * hid + 4 * m0.plan.B * d
-        ws = _persist(dev, 'ws', nsets * ws_n, f32)
-        dxs = _persist(dev, 'dx', 3 * md, f32)
-        dx_in = torch.empty((M, d), dtype=f32, device=dev)
+        sc = _backward_scratch(dev, nb, M, d, hid, m0.plan.B)
+        dx_in = torch.empty((M, d), dtype=torch.float32, device=dev)
         if sink is None:
-            tot = sum(shared_n + ((n_ - 11) // 4) * exp_n for (_, n_) in spans)
-            # no memset of the weight-gradient matrices: the deferred launches WRITE them (wgrad_store); only the vector
-            # gradients (accumulated with atomics by the column folds) are zeroed, in one multi-tensor fill
-            whole = None        # allocated when the first group needs fresh gradient storage
+            storage = _fresh_storage(sum(group_numel(g, d, hid) for blk in groups for g in blk), dev)
             reg = _task_flats(ctx) if INPLACE_ACCUM else None
-            permit = _TASK_FLATS['groups']
+            permitted, into_grad, off = _TASK_FLATS['groups'], INPLACE_ACCUM and _INTO_GRAD[0], 0
         grads_all = [None] * len(params)
-        goff = 0
         store_ok, acquired = True, []       # (flat, fresh, is_expert) of every gradient bucket of the pass
         for k in range(nb):                 # backward order: k-th processed block is i = nb-1-k
             i = nb - 1 - k
-            D = descs[i]
-            o, n_ = spans[i]
-            nexp = (n_ - 11) // 4
+            D, blk, (o, n_) = descs[i], groups[i], spans[i]
             if sink is not None:
-                akey, aroom = id(params[o]), shared_n + 3 * exp_n
-                groups = ctx.sink_groups[i]
-                got = [sink.acquire(groups[0], shared_n, dev, akey, aroom, layout=shared_layout(groups[0], d), lazy_zero=True)] + \
-                      [sink.acquire(g_, exp_n, dev, akey, aroom, layout=expert_layout(g_, d, hid), lazy_zero=True)
-                       for g_ in groups[1:]]
-                flats = [f_ for f_, _ in got]
-                store_ok = store_ok and all(fr for _, fr in got)      # a bucket an earlier pass of the step already fed: accumulate
-                acquired += [(f_, fr, j > 0) for j, (f_, fr) in enumerate(got)]
+                got = _sink_buckets(sink, blk, d, hid, dev)
             else:
-                bp = params[o:o + n_]
-                groups = [(bp[:11], shared_n)] + [(bp[11 + 4 * e: 15 + 4 * e], exp_n) for e in range(nexp)]
-                ni = ctx.needs_input_grad[2 + o: 2 + o + n_]
-                flats, kept = [], []
-                for gi, (gp_, gn_) in enumerate(groups):
-                    lo = 0 if gi == 0 else 11 + 4 * (gi - 1)
-                    wanted = all(w or not p_.requires_grad for p_, w in zip(gp_, ni[lo:lo + len(gp_)]))
-                    have, how = None, 0
-                    if INPLACE_ACCUM and wanted:
-                        if reg is not None and _group_key(gp_) in reg:
-                            have, how = reg[_group_key(gp_)], 1                     # an earlier node of this backward
-                        elif _INTO_GRAD[0]:
-                            # an earlier backward of this step: only when the parameters hold exactly this layout's views
-                            have = _grad_flat(gp_, gn_)
-                            lay = (shared_layout(gp_, d) if gi == 0 else expert_layout(gp_, d, hid)) if have is not None else None
-                            if have is not None and _same_views(lay, have):
-                                how = 2
-                            else:
-                                have = None
-                    flats.append(have)
-                    kept.append(how)
-                for gi, (gp_, gn_) in enumerate(groups):
-                    if flats[gi] is None:
-                        if whole is None:
-                            whole = torch.empty(tot, dtype=f32, device=dev)
-                        flats[gi] = whole[goff:goff + gn_]
-                        lo = 0 if gi == 0 else 11 + 4 * (gi - 1)
-                        if (reg is not None and _group_key(gp_) in permit
-                                and all(w or not p_.requires_grad for p_, w in zip(gp_, ni[lo:lo + len(gp_)]))):
-                            reg[_group_key(gp_)] = flats[gi]
-                    goff += gn_
-                    acquired.append((flats[gi], kept[gi] == 0, gi > 0))
-                if any(kept):
-                    store_ok = False
-            grads = _fill_grads(D, flats, d, hid, nexp)
-            if sink is not None:
-                grads_all[o:o + n_] = grads
-            else:
-                # groups accumulated in place hand nothing to autograd
-                for gi in range(len(groups)):
-                    lo = 0 if gi == 0 else 11 + 4 * (gi - 1)
-                    hi = 11 if gi == 0 else lo + 4
-                    if not kept[gi]:
-                        grads_all[o + lo:o + hi] = grads[lo:hi]
+                got, off = _local_buckets(blk, ctx.needs_input_grad[2 + o:2 + o + n_], d, hid, reg, permitted, into_grad,
+                                          storage, off)
+            # a bucket that an earlier pass of the step already fed is accumulated into: no store mode for this pass
+            store_ok = store_ok and all(fr for _, fr in got)
+            acquired += [(f_, fr, g.lo > 0) for g, (f_, fr) in zip(blk, got)]
+            grads = _fill_grads(D, [f_ for f_, _ in got], d, hid, len(blk) - 1)
+            for g, (_, fr) in zip(blk, got):
+                if fr or sink is not None:  # groups accumulated in place hand nothing to autograd
+                    grads_all[o + g.lo:o + g.hi] = grads[g.lo:g.hi]
             _split_backward_attention(D, metas[i])
-            st_ = k % nsets
-            pb = tb.data_ptr() + st_ * 11 * md * 2
-            md2 = md * 2
-            D.dz2, D.du, D.dy2, D.dz1, D.dqkv, D.dy1 = pb, pb + md2, pb + 5 * md2, pb + 6 * md2, pb + 7 * md2, pb + 10 * md2
-            D.dctx = D.dy2
-            D.ws_main, D.ws_bytes = ws.data_ptr() + st_ * ws_n * 4, ws_n * 4
-            D.dx1 = dxs.data_ptr() + 2 * md * 4
-            D.dx2 = dxo.data_ptr() if k == 0 else dxs.data_ptr() + ((k - 1) % 2) * md * 4
-            D.dx0 = dx_in.data_ptr() if k == nb - 1 else dxs.data_ptr() + (k % 2) * md * 4
-        if store_ok:
-            # vector gradients only: [g1 g2 n1w n1b n2w n2b | qkv_w proj_w | proj_b qkv_b] and [w1 | b1 | w2 | b2]
-            vecs = []
-            for f_, _, is_exp in acquired:
-                vecs += [f_[hid * d:hid * d + hid], f_[2 * hid * d + hid:]] if is_exp else [f_[:6 * d], f_[6 * d + 4 * d * d:]]
-            torch._foreach_zero_(vecs)
-        else:
-            for f_, fr, _ in acquired:
-                if fr:
-                    f_.zero_()
+            _wire_temporaries(D, k, nb, M * d, sc, dxo, dx_in)
+        _zero_buckets(acquired, store_ok, d, hid)
         S = hip.StackDesc()
-        S.n_blocks, S.wgrad_batch, S.n_tmp_sets, S.wgrad_store = nb, batch, nsets, int(store_ok)
+        S.n_blocks, S.wgrad_batch, S.n_tmp_sets, S.wgrad_store = nb, sc.batch, sc.nsets, int(store_ok)
         S.blocks = ctypes.cast(descs, ctypes.POINTER(hip.BlockDesc))
         side = _side_stream(dev) if _use_side_stream(sink, M) else None
         S.side_stream = side.cuda_stream if side is not None else None
@@ -836,17 +889,7 @@ class StackFn(torch.autograd.Function):
         hip.stack_bwd(S)
         ctx.descs = ctx.keep = None
         if sink is not None:
-            for k in range(nb):
-                i = nb - 1 - k
-                o, n_ = spans[i]
-                for p_, g_ in zip(params[o:o + n_], grads_all[o:o + n_]):
-                    if p_.requires_grad:
-                        if p_.grad is None:
-                            p_.grad = g_
-                        elif p_.grad.data_ptr() != g_.data_ptr():
-                            raise RuntimeError('a parameter of a data-parallel block already holds a foreign .grad; '
-                                               'use zero_grad(set_to_none=True)')
-                sink.release_all(ctx.sink_groups[i], ready_event=evs[i] if evs is not None else None)
+            _hand_to_sink(sink, groups, spans, grads_all, evs)
             return (dx_in, None) + (None,) * len(params)
         return (dx_in, None, *grads_all)
 

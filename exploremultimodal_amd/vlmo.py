@@ -131,7 +131,9 @@ class Block(nn.Module):
     # -- engine plumbing -----------------------------------------------------
     def _params(self, routes):
         """The engine's per-block parameter order: gamma_1, gamma_2, norm1 w / b, qkv_w, q_bias, v_bias, proj_w, proj_b,
-        norm2 w / b, then (fc1_w, fc1_b, fc2_w, fc2_b) per route."""
+        norm2 w / b, then (fc1_w, fc1_b, fc2_w, fc2_b) per route.  This is the only place that produces it; the engine reads
+        it through engine.block_groups() and the counts and weight positions named beside it (N_SHARED, N_EXPERT, QKV_W,
+        PROJ_W, FC1_W, FC2_W), which change with this list."""
         a = self.attn
         g1, g2 = (self.gamma_1, self.gamma_2) if self.gamma_1 is not None else (self._unit_scale, self._unit_scale)
         qb, vb = (a.q_bias, a.v_bias) if a.q_bias is not None else (a._zero_bias, a._zero_bias)
