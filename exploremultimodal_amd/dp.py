@@ -30,50 +30,94 @@ p.grad are views of it, and the whole buffer is cast to bf16 and all-reduced as 
 as the last backward call that contributes to it in this step has been enqueued.
 Only parameters outside the blocks (embeddings, final norm, heads) use the hook path.
 """
+import os
 import re
+import time
+from contextlib import contextmanager
 
 import torch
 import torch.distributed as dist
 
+from . import engine, hip
 
-class _Bucket:
+_ACCUMULATE_GRAD = 'torch::autograd::AccumulateGrad'
+
+
+def _pad(n, world):
+    """n rounded up to a multiple of world * 8: every rank's slice of a bucket has the same, 16-byte aligned size."""
+    q = world * 8
+    return (n + q - 1) // q * q
+
+
+def _engine_groups(fn, sink):
+    """Per block, the parameter groups whose gradients the autograd node `fn` will hand to `sink`: engine.StackFn leaves
+    `sink` and `sink_groups` on its node.  None for every other node."""
+    if not isinstance(fn, torch.autograd.function.BackwardCFunction):
+        return None
+    try:
+        return fn.sink_groups if fn.sink is sink else None
+    except AttributeError:          # a custom Function that is not the engine's
+        return None
+
+
+def _storage(n, device, comm_dtype, wire=torch.empty):
+    """(flat, comm): the fp32 buffer and what goes over the links -- the same tensor for an fp32 wire."""
+    flat = torch.zeros(n, dtype=torch.float32, device=device)
+    return flat, (flat if comm_dtype == torch.float32 else wire(n, dtype=comm_dtype, device=device))
+
+
+class _Flat:
+    """What hook buckets and sink buckets have in common: padded flat storage, its wire buffer and the state of the
+    exchange (GradReducer._exchange).  `flat` and `comm` are set by the subclass."""
+    __slots__ = ('numel', 'padded', 'flat', 'comm', 'shard_comm', 'shard32', 'shard', 'rs_pack', 'work', 'unpacked',
+                 'has_grad', 'expected')
+
+    def __init__(self, numel, world):
+        self.numel, self.padded = numel, _pad(numel, world)
+        # gradient partition: this rank's slice as it arrives, in fp32 (the same tensor for an fp32 wire) and, once unpacked,
+        # as `shard`; rs_pack is the scaled copy an fp32 wire sends.  Made at the first exchange and then kept.
+        self.shard_comm = self.shard32 = self.shard = self.rs_pack = None
+        self.work = None        # handle of the collective in flight
+        self.unpacked = False   # ... and whether its result is already back in flat / shard32
+        self.has_grad = False   # a collective has been issued for it in this accumulation window (GradReducer.prepare)
+        self.expected = 0       # hook buckets: parameters this pass touches; sink buckets: backward calls still to come
+
+
+class _Bucket(_Flat):
+    """Hook bucket: the gradients autograd leaves in p.grad are gathered into the wire buffer when the last one arrived."""
+    __slots__ = ('name', 'params', 'offsets', 'used', 'had', 'pending', 'launched')
+
     def __init__(self, name, params, device, comm_dtype, world):
         self.name, self.params = name, params
         self.offsets, n = [], 0
         for p in params:
             self.offsets.append(n)
             n += p.numel()
-        self.numel = n
-        self.padded = ((n + world * 8 - 1) // (world * 8)) * (world * 8)
-        self.flat = torch.zeros(self.padded, dtype=torch.float32, device=device)
-        self.comm = self.flat if comm_dtype == torch.float32 else torch.zeros(
-            self.padded, dtype=comm_dtype, device=device)
-        self.shard = None
-        self.expected = 0
+        super().__init__(n, world)
+        self.flat, self.comm = _storage(self.padded, device, comm_dtype, wire=torch.zeros)
         self.pending = 0
-        self.work = None
         self.launched = False
         self.used = []
-        self.has_grad = False   # reduced in the current accumulation window (see GradReducer.prepare)
-        self.had = []
+        self.had = []           # per parameter: a gradient went into the last exchange
 
 
 class _Arena:
     """Contiguous storage for the sink buckets of ONE transformer block (its shared parameters and up to three
     experts): buckets that become ready together are reduced as one collective over their common range."""
+    __slots__ = ('flat', 'comm', 'used')
 
     def __init__(self, capacity, device, comm_dtype):
-        self.flat = torch.zeros(capacity, dtype=torch.float32, device=device)
-        self.comm = self.flat if comm_dtype == torch.float32 else torch.empty(capacity, dtype=comm_dtype, device=device)
+        self.flat, self.comm = _storage(capacity, device, comm_dtype)
         self.used = 0
 
 
-class _SinkBucket:
+class _SinkBucket(_Flat):
     """Flat fp32 gradient storage of one engine block call signature (see module docstring)."""
+    __slots__ = ('arena', 'offset', 'fresh', 'reduced', 'params', 'layout')
+    had = None      # fed as a whole by the engine, no per-parameter record: zero.ZeroAdam tells the two kinds apart by it
 
-    def __init__(self, numel, device, comm_dtype, world, arena=None):
-        self.numel = numel
-        self.padded = ((numel + world * 8 - 1) // (world * 8)) * (world * 8)
+    def __init__(self, numel, device, comm_dtype, world, arena=None, params=(), layout=None):
+        super().__init__(numel, world)
         self.arena, self.offset = None, 0
         if arena is not None and arena.used + self.padded <= arena.flat.numel():
             self.arena, self.offset = arena, arena.used
@@ -81,15 +125,11 @@ class _SinkBucket:
             self.flat = arena.flat[self.offset:self.offset + self.padded]
             self.comm = self.flat if comm_dtype == torch.float32 else arena.comm[self.offset:self.offset + self.padded]
         else:
-            self.flat = torch.zeros(self.padded, dtype=torch.float32, device=device)
-            self.comm = self.flat if comm_dtype == torch.float32 else torch.empty(
-                self.padded, dtype=comm_dtype, device=device)
-        self.expected = 0       # backward calls still to come in this step
+            self.flat, self.comm = _storage(self.padded, device, comm_dtype)
+        self.params = params
+        self.layout = layout    # [(parameter, offset in the flat bucket)]: what zero.ZeroAdam shards
         self.fresh = True       # zero before the first accumulation of the step
         self.reduced = False    # a collective has been issued for this step's contents
-        self.work = None
-        self.shard = None
-        self.has_grad = False   # a collective has been issued for it in the current accumulation window
 
 
 class _Enqueued:
@@ -108,7 +148,6 @@ class GradReducer:
         comm_dtype: torch.bfloat16 (half the bytes per link, one pack and one unpack pass over every bucket), torch.float32
         (the buckets are exchanged in place), or None = decided at start-up: timed with the other candidates when there is
         more than one rank (autotune), fp32 at world size 1 (nothing crosses a link, the two passes would be pure cost)."""
-        import os
         self._auto_dtype = comm_dtype is None
         if comm_dtype is None:
             comm_dtype = torch.bfloat16
@@ -145,7 +184,6 @@ class GradReducer:
         self.comm_stream = None
         if self.on_gpu:
             # a stream that really runs beside the caller's stream and the weight-gradient stream (engine.pick_stream)
-            from . import engine
             dev = self.device
             with torch.cuda.device(dev):
                 busy = [torch.cuda.current_stream(dev), engine._side_stream(dev)]
@@ -154,20 +192,19 @@ class GradReducer:
         if self.comm_mode == 'native':
             if not self.on_gpu:
                 raise RuntimeError("comm='native' is the RCCL communicator of the HIP library: GPU parameters only")
-            from . import hip
-            # bootstrap over the existing process group: rank 0 draws the id, everybody joins
-            uid = [hip.comm_unique_id() if self.rank == 0 else None]
-            src = dist.get_global_rank(self.pg, 0) if self.pg is not dist.group.WORLD else 0
-            dist.broadcast_object_list(uid, src=src, group=self.pg)
-            with torch.cuda.device(self.device):
-                self.native = hip.comm_init(uid[0], self.rank, self.world)
+            self.native = self._make_native()
         self._armed = False
-        self._foreign = {}
+        self._window_done = True    # the last finish() was an update step: the next prepare() opens an accumulation window
+        self._foreign = {}          # id(sink parameter with a producer outside the engine) -> key of its bucket
+        self._pending_expect = {}   # backward calls expected for sink buckets that do not exist yet
+        self._ready_event = None    # native event the next sink exchange waits for (release_all)
         self.sinks = {}
         self.arenas = {}
         self._sink_params = set()
+        # optional timing of the exchange: event pairs on the communication stream around pack -> collective -> unpack
+        self.timing = False
+        self._tev = []
         if engine_sink and self.on_gpu:
-            from . import engine
             engine.GRAD_SINK = self
         if broadcast_params and self.world > 1:
             self.sync_params(module)
@@ -187,6 +224,17 @@ class GradReducer:
         elif self._auto_dtype and self.world == 1:
             self._set_comm_dtype(torch.float32)
 
+    def _root(self):
+        """Global rank of the group's rank 0, the source of every broadcast."""
+        return dist.get_global_rank(self.pg, 0) if self.pg is not dist.group.WORLD else 0
+
+    def _make_native(self):
+        """A communicator of the HIP library over the existing process group: rank 0 draws the id, everybody joins."""
+        uid = [hip.comm_unique_id() if self.rank == 0 else None]
+        dist.broadcast_object_list(uid, src=self._root(), group=self.pg)
+        with torch.cuda.device(self.device):
+            return hip.comm_init(uid[0], self.rank, self.world)
+
     # ------------------------------------------------------------ start-up choice of the exchange
     def _set_comm_dtype(self, dtype):
         """Switch the exchange dtype before any sink bucket exists (the hook buckets' wire buffers are re-made)."""
@@ -198,9 +246,8 @@ class GradReducer:
             b.comm = b.flat if dtype == torch.float32 else torch.zeros(b.padded, dtype=dtype, device=self.device)
 
     def _time_exchange(self, buf, reps, wire=None):
-        """seconds per in-place sum of `buf` over the ranks with the current settings (max over `reps` after 2 warm-ups is
-        not needed: the median of the timed repetitions; every rank times its own, the caller takes the max over ranks)."""
-        import time
+        """Seconds per exchange of `buf` over the ranks with the current settings (through `wire` when given): the median of
+        `reps` timed repetitions after two warm-ups.  Every rank times its own; the caller takes the max over the ranks."""
         ts = []
         for i in range(reps + 2):
             if self.on_gpu:
@@ -233,8 +280,7 @@ class GradReducer:
         table of candidates -> seconds and stores it (with the choice) in self.tuned."""
         if self.world < 2:
             return None
-        n = numel or max(b.padded for b in self.buckets)
-        n = ((n + self.world * 8 - 1) // (self.world * 8)) * (self.world * 8)
+        n = _pad(numel or max(b.padded for b in self.buckets), self.world)
         buf = torch.zeros(n, dtype=torch.float32 if self.on_gpu else self.comm_dtype, device=self.device)
         dtypes = [torch.bfloat16, torch.float32] if try_dtype else [self.comm_dtype]
         wires = {d: (None if d == buf.dtype else torch.zeros(n, dtype=d, device=self.device)) for d in dtypes}
@@ -244,17 +290,11 @@ class GradReducer:
             # the library's own communicator joins the candidates; a failure to create it on ANY rank drops it everywhere
             ok = torch.ones(1, dtype=torch.int32, device=self.device)
             try:
-                from . import hip
-                uid = [hip.comm_unique_id() if self.rank == 0 else None]
-                src = dist.get_global_rank(self.pg, 0) if self.pg is not dist.group.WORLD else 0
-                dist.broadcast_object_list(uid, src=src, group=self.pg)
-                with torch.cuda.device(self.device):
-                    made_native = hip.comm_init(uid[0], self.rank, self.world)
+                made_native = self._make_native()
             except Exception:       # noqa: BLE001 -- any failure means "not a candidate"
                 ok.zero_()
             dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=self.pg)
             if int(ok.item()) == 0 and made_native is not None:
-                from . import hip
                 hip.comm_destroy(made_native)
                 made_native = None
         comms = [('torch', None)] if native0 is None else [('native', native0)]
@@ -275,7 +315,6 @@ class GradReducer:
         self.native, self.rs_ag, self.comm_mode = handle, form == 'rs_ag', cname
         self._set_comm_dtype(dsel)
         if made_native is not None and handle is not made_native:
-            from . import hip
             if self.on_gpu:
                 torch.cuda.synchronize(self.device)
             hip.comm_destroy(made_native)
@@ -286,9 +325,6 @@ class GradReducer:
             print(f'[GradReducer] exchange of a {n / 1e6:.1f} M-element gradient bucket over {self.world} ranks: '
                   f'{self.tuned["candidates_ms"]} ms -> {self.tuned["chosen"]}', flush=True)
         return self.tuned
-
-    # optional timing of the exchange: event pairs on the communication stream around pack -> collective -> unpack
-    timing = False
 
     def _t0(self):
         if self.timing and self.on_gpu:
@@ -301,15 +337,15 @@ class GradReducer:
         if e0 is not None:
             e1 = torch.cuda.Event(enable_timing=True)
             e1.record(torch.cuda.current_stream(self.device))
-            self.__dict__.setdefault('_tev', []).append((e0, e1))
+            self._tev.append((e0, e1))
 
     def comm_ms(self):
         """milliseconds the communication stream spent in pack / collective / unpack since timing was switched on
         (synchronises); resets the record."""
         if self.on_gpu:
             torch.cuda.synchronize(self.device)
-        tot = sum(a.elapsed_time(b) for a, b in self.__dict__.get('_tev', []))
-        self.__dict__['_tev'] = []
+        tot = sum(a.elapsed_time(b) for a, b in self._tev)
+        self._tev = []
         return tot
 
     def agree_finite(self, *losses):
@@ -328,7 +364,6 @@ class GradReducer:
         form of the exchange, bytes on the wire per step and rank (before the ring / tree factor)."""
         ranks = self.world
         if self.native is not None:
-            from . import hip
             ranks = hip.comm_count(self.native)
         return {'ranks_in_communicator': ranks, 'communicator': self.comm_mode, 'backend': dist.get_backend(self.pg),
                 'collective': ('reduce_scatter' if self.reduce_scatter else ('rs_ag' if self.rs_ag else 'all_reduce')),
@@ -337,7 +372,6 @@ class GradReducer:
 
     def close(self):
         """Detach from the engine (block gradients go back through autograd) and drop the buckets."""
-        from . import engine
         if engine.GRAD_SINK is self:
             engine.GRAD_SINK = None
         self.sinks.clear()
@@ -345,7 +379,6 @@ class GradReducer:
         self._sink_params.clear()
         self._armed = False
         if self.native is not None:
-            from . import hip
             torch.cuda.synchronize(self.device)
             hip.comm_destroy(self.native)
             self.native = None
@@ -361,7 +394,6 @@ class GradReducer:
         n = t.numel() // self.world
         mine = t[self.rank * n:(self.rank + 1) * n] if split else None
         if self.native is not None:
-            from . import hip
             if split:
                 hip.comm_reduce_scatter(self.native, mine, t)
                 hip.comm_all_gather(self.native, t, mine)
@@ -375,7 +407,6 @@ class GradReducer:
 
     def _c_reduce_scatter(self, out, src):
         if self.native is not None:
-            from . import hip
             hip.comm_reduce_scatter(self.native, out, src)
             return _Enqueued()
         return dist.reduce_scatter_tensor(out, src, group=self.pg, async_op=True)
@@ -383,7 +414,6 @@ class GradReducer:
     def all_gather(self, out, src):
         """out [world * n] <- every rank's src [n] (src may be out's own slice), on the CURRENT stream."""
         if self.native is not None:
-            from . import hip
             hip.comm_all_gather(self.native, out, src)
         else:
             dist.all_gather_into_tensor(out, src, group=self.pg)
@@ -391,7 +421,6 @@ class GradReducer:
     def all_reduce_now(self, t):
         """in-place sum on the CURRENT stream (small tensors: the squared gradient norm of the sharded step)."""
         if self.native is not None:
-            from . import hip
             hip.comm_all_reduce(self.native, t)
         else:
             dist.all_reduce(t, group=self.pg)
@@ -399,14 +428,12 @@ class GradReducer:
     def _pack(self, flat, comm):
         """comm (bf16) = flat (fp32) / world in ONE pass on the current stream."""
         if self.on_gpu and comm.dtype == torch.bfloat16 and flat.data_ptr() % 16 == 0 and comm.data_ptr() % 16 == 0:
-            from . import hip
             hip.grad_pack(flat, comm, 1.0 / self.world)
         else:
             torch.mul(flat, 1.0 / self.world, out=comm)
 
     def _unpack_into(self, comm, flat):
         if self.on_gpu and comm.dtype == torch.bfloat16 and flat.data_ptr() % 16 == 0 and comm.data_ptr() % 16 == 0:
-            from . import hip
             hip.grad_unpack(comm, flat)
         else:
             flat.copy_(comm)
@@ -417,8 +444,7 @@ class GradReducer:
         with torch.no_grad():
             ts = list(module.parameters()) + list(module.buffers())
             for t in ts:
-                dist.broadcast(t.data, src=dist.get_global_rank(self.pg, 0) if self.pg is not dist.group.WORLD else 0,
-                               group=self.pg)
+                dist.broadcast(t.data, src=self._root(), group=self.pg)
             # the broadcast wrote through .data: bump the version counters so that bf16 weight shadows cached by a
             # forward that ran before the reducer was built are re-cast (engine.ShadowCache keys on _version)
             torch.autograd.graph.increment_version(ts)
@@ -430,19 +456,19 @@ class GradReducer:
     # ------------------------------------------------------------ per-step API
     def prepare(self, loss):
         """Find the parameters this backward will touch (autograd graph walk) and arm the hooks."""
-        used = set()
+        leaves = {}                 # AccumulateGrad node -> the tensor it accumulates into
         seen, stack = set(), [loss.grad_fn] if loss.grad_fn is not None else []
         while stack:
             fn = stack.pop()
             if fn is None or fn in seen:
                 continue
             seen.add(fn)
-            v = getattr(fn, 'variable', None)
-            if v is not None and v in self._of:
-                used.add(v)
+            if fn.name() == _ACCUMULATE_GRAD:
+                leaves[fn] = fn.variable
             for nxt, _ in fn.next_functions:
                 stack.append(nxt)
-        if getattr(self, '_window_done', True):
+        used = {v for v in leaves.values() if v in self._of}
+        if self._window_done:
             # first backward of a new accumulation window (the previous finish() was an update step): nothing has been
             # reduced yet.  zero.ZeroAdam reads these flags: a bucket that receives no gradient in this window (every pass
             # feeding it dropped, modality absent) must not be stepped with the PREVIOUS window's shard.
@@ -463,8 +489,8 @@ class GradReducer:
         # last real contribution and never left holding local, un-averaged gradients.
         counts, key_of, engine_nodes = {}, {}, set()
         for fn in seen:
-            groups = getattr(fn, 'sink_groups', None)
-            if groups is None or getattr(fn, 'sink', None) is not self:
+            groups = _engine_groups(fn, self)
+            if groups is None:
                 continue
             engine_nodes.add(fn)
             for blk in groups:              # sink_groups: per block, its parameter groups
@@ -483,8 +509,8 @@ class GradReducer:
             if fn in engine_nodes:
                 continue
             for nxt, _ in fn.next_functions:
-                v = getattr(nxt, 'variable', None) if nxt is not None else None
-                if isinstance(v, torch.Tensor) and v.requires_grad and id(v) in key_of:
+                v = leaves.get(nxt)
+                if v is not None and v.requires_grad and id(v) in key_of:
                     self._foreign[id(v)] = key_of[id(v)]
         for k in self._foreign.values():
             counts[k] += 1
@@ -505,7 +531,6 @@ class GradReducer:
         if sb is not None:
             sb.expected += 1
         else:
-            self._pending_expect = getattr(self, '_pending_expect', {})
             self._pending_expect[key] = self._pending_expect.get(key, 0) + 1
 
     def acquire(self, group, numel, device, arena_key=None, arena_numel=0, layout=None, lazy_zero=False):
@@ -521,12 +546,10 @@ class GradReducer:
             if arena_key is not None and not self.reduce_scatter:
                 arena = self.arenas.get(arena_key)
                 if arena is None:
-                    pad = self.world * 8
-                    arena = self.arenas[arena_key] = _Arena(arena_numel + 4 * pad, device, self.comm_dtype)
-            sb = _SinkBucket(numel, device, self.comm_dtype, self.world, arena)
-            sb.params = tuple(group)
-            sb.layout = layout          # [(parameter, offset in the flat bucket)]: what zero.ZeroAdam shards
-            sb.expected = getattr(self, '_pending_expect', {}).pop(key, 1)
+                    # room for the padding of up to four buckets (shared parameters + three experts)
+                    arena = self.arenas[arena_key] = _Arena(arena_numel + 4 * self.world * 8, device, self.comm_dtype)
+            sb = _SinkBucket(numel, device, self.comm_dtype, self.world, arena, tuple(group), layout)
+            sb.expected = self._pending_expect.pop(key, 1)
             self.sinks[key] = sb
             self._sink_params.update(key)
         if sb.work is not None:         # previous step's reduction was never finish()ed: retire it first
@@ -570,85 +593,83 @@ class GradReducer:
                 self._launch_range(ready[i:j + 1])
             i = j + 1
 
-    def _comm_wait(self):
-        """Order the communication stream after the producers of the gradients about to be reduced."""
-        ev = getattr(self, '_ready_event', None)
-        if ev is not None:
-            from . import hip
-            hip.stream_wait_event(self.comm_stream, ev)
+    # ---- the exchange: communication stream after the producers -> 1/W (or pack) -> collective -> unpack ------------
+    @contextmanager
+    def _on_comm_stream(self, ready_event=None):
+        """Run the body on the communication stream, ordered after `ready_event` (hip.event_create) or, without one,
+        after everything enqueued so far on the current stream; timed when `timing` is on.  On the CPU: nothing."""
+        if not self.on_gpu:
+            yield
+            return
+        if ready_event is not None:
+            hip.stream_wait_event(self.comm_stream, ready_event)
         else:
             self.comm_stream.wait_stream(torch.cuda.current_stream(self.device))
-
-    def _launch_range(self, sbs):
-        """One pack / collective / unpack over the contiguous arena range of several ready buckets."""
-        a = sbs[0].arena
-        lo, hi = sbs[0].offset, sbs[-1].offset + sbs[-1].padded
-        flat, comm = a.flat[lo:hi], a.comm[lo:hi]
-        self._comm_wait()
         with torch.cuda.stream(self.comm_stream):
             t0 = self._t0()
-            if comm.data_ptr() != flat.data_ptr():
-                self._pack(flat, comm)
-            elif self.world > 1:
-                flat.mul_(1.0 / self.world)
-            work = self._c_all_reduce(comm)
-            work.wait()
-            if comm.data_ptr() != flat.data_ptr():
-                self._unpack_into(comm, flat)
+            yield
             self._t1(t0)
+
+    def _exchange(self, b, flat, comm, scaled=False):
+        """Average `flat` over the ranks through `comm` -- the storage of bucket `b`, or an arena range that starts with
+        it -- and leave the handle in b.work.  ``scaled``: `comm` already holds the gradients times 1/W."""
+        src = comm
+        if scaled:
+            pass
+        elif comm.dtype != flat.dtype:
+            self._pack(flat, comm)              # ONE pass: 1/world scaling + fp32 -> bf16 pack
+        elif self.reduce_scatter:
+            # fp32 communication + gradient partition: the reduce-scatter writes only the shard, so `flat` stays the
+            # LOCAL accumulator that the next micro-step of a gradient-accumulation window adds to -- it must never
+            # be scaled in place (it would carry g1 / W into the next pack: (g1 / W + g2) / W)
+            if b.rs_pack is None:
+                b.rs_pack = torch.empty_like(flat)
+            src = torch.mul(flat, 1.0 / self.world, out=b.rs_pack)
+        elif self.world > 1:
+            flat.mul_(1.0 / self.world)
+        if self.reduce_scatter:
+            # persistent buffers: the ZeRO-2 optimizer (zero.ZeroAdam) keeps device tables of their addresses
+            if b.shard_comm is None:
+                n = b.padded // self.world
+                b.shard_comm = torch.empty(n, dtype=comm.dtype, device=self.device)
+                b.shard32 = b.shard_comm if comm.dtype == torch.float32 else torch.empty(
+                    n, dtype=torch.float32, device=self.device)
+            b.work = self._c_reduce_scatter(b.shard_comm, src)
+        else:
+            b.work = self._c_all_reduce(comm)
+        b.has_grad = True
+        if self.on_gpu:
+            # the unpack follows its collective on the communication stream (work.wait() orders this stream after
+            # the collective, it does not block the host): it overlaps the rest of the backward pass instead of
+            # running once per bucket on the main stream at the end of the step.  On the CPU finish() unpacks.
+            b.work.wait()
+            self._unpack(b, flat, comm)
+
+    def _unpack(self, b, flat, comm):
+        if self.reduce_scatter:
+            if b.shard32 is not b.shard_comm:
+                self._unpack_into(b.shard_comm, b.shard32)
+            b.shard = b.shard32
+        elif comm.dtype != flat.dtype:
+            self._unpack_into(comm, flat)       # ONE pass: bf16 -> fp32 unpack (already averaged)
+        b.unpacked = True
+
+    def _launch_range(self, sbs):
+        """One exchange over the contiguous arena range of several ready buckets (arenas exist only without gradient
+        partition: acquire)."""
+        first, a = sbs[0], sbs[0].arena
+        lo, hi = first.offset, sbs[-1].offset + sbs[-1].padded
+        with self._on_comm_stream(self._ready_event):
+            self._exchange(first, a.flat[lo:hi], a.comm[lo:hi])
         for sb in sbs:
-            sb.work, sb.unpacked, sb.reduced, sb.has_grad = work, True, True, True
+            sb.work, sb.unpacked, sb.reduced, sb.has_grad = first.work, first.unpacked, True, True
 
     def _launch_sink(self, sb):
-        sb.reduced = sb.has_grad = True
         # everything on the communication stream (ordered after the block backward that just finished on the
         # current stream): the pack would otherwise sit in the dgrad chain's critical path 30 times per step
-        if self.on_gpu:
-            self._comm_wait()
-            ctxm = torch.cuda.stream(self.comm_stream)
-        else:
-            from contextlib import nullcontext
-            ctxm = nullcontext()
-        with ctxm:
-            t0 = self._t0()
-            src = sb.comm
-            if sb.comm is not sb.flat:
-                self._pack(sb.flat, sb.comm)        # ONE pass: 1/world scaling + fp32 -> bf16 pack
-            elif self.reduce_scatter:
-                # fp32 communication + gradient partition: the reduce-scatter writes only the shard, so `flat` stays the
-                # LOCAL accumulator that the next micro-step of a gradient-accumulation window adds to -- it must never
-                # be scaled in place (it would carry g1 / W into the next pack: (g1 / W + g2) / W)
-                if getattr(sb, 'rs_pack', None) is None:
-                    sb.rs_pack = torch.empty_like(sb.flat)
-                src = torch.mul(sb.flat, 1.0 / self.world, out=sb.rs_pack)
-            elif self.world > 1:
-                sb.flat.mul_(1.0 / self.world)
-            if self.reduce_scatter:
-                # persistent buffers: the ZeRO-2 optimizer (zero.ZeroAdam) keeps device tables of their addresses
-                n = sb.padded // self.world
-                if getattr(sb, 'shard_comm', None) is None:
-                    sb.shard_comm = torch.empty(n, dtype=sb.comm.dtype, device=self.device)
-                    sb.shard32 = sb.shard_comm if sb.comm.dtype == torch.float32 else torch.empty(
-                        n, dtype=torch.float32, device=self.device)
-                sb.work = self._c_reduce_scatter(sb.shard_comm, src)
-            else:
-                sb.work = self._c_all_reduce(sb.comm)
-            if self.on_gpu:
-                # the unpack follows its collective on the communication stream (work.wait() orders this stream
-                # after the collective, it does not block the host): it overlaps the rest of the backward pass
-                # instead of running 30 times on the main stream at the end of the step
-                sb.work.wait()
-                self._unpack_sink(sb)
-                self._t1(t0)
-
-    def _unpack_sink(self, sb):
-        if self.reduce_scatter:
-            if sb.shard32 is not sb.shard_comm:
-                self._unpack_into(sb.shard_comm, sb.shard32)
-            sb.shard = sb.shard32
-        elif sb.comm is not sb.flat:
-            self._unpack_into(sb.comm, sb.flat)  # ONE pass: bf16 -> fp32 unpack (already averaged)
-        sb.unpacked = True
+        sb.reduced = True
+        with self._on_comm_stream(self._ready_event):
+            self._exchange(sb, sb.flat, sb.comm)
 
     def _hook(self, p):
         if not self._armed:
@@ -667,17 +688,11 @@ class GradReducer:
             self._launch(b)
 
     def _launch(self, b):
-        """Pack (1/world folded in), reduce and unpack one hook bucket, all on the communication stream."""
+        """Gather one hook bucket's gradients into its wire buffer (1/world folded in) and exchange it.  Its producers
+        ran on the current stream, whatever event the engine last handed over."""
         inv = 1.0 / self.world
-        if self.on_gpu:
-            self.comm_stream.wait_stream(torch.cuda.current_stream(self.device))
-            ctxm = torch.cuda.stream(self.comm_stream)
-        else:
-            from contextlib import nullcontext
-            ctxm = nullcontext()
-        with ctxm:
-            t0 = self._t0()
-            # pack: grads of this pass, zeros for parameters this pass did not touch
+        with self._on_comm_stream():
+            # grads of this pass, zeros for parameters this pass did not touch
             b.had = []
             for p, off, u in zip(b.params, b.offsets, b.used):
                 v = b.comm[off:off + p.numel()]
@@ -691,29 +706,8 @@ class GradReducer:
                 else:
                     v.zero_()       # e.g. img_mask_token in a pass without masked patches: backward gives None
                 b.had.append(has)
-            if self.reduce_scatter:
-                n = b.padded // self.world
-                if getattr(b, 'shard_comm', None) is None:
-                    b.shard_comm = torch.empty(n, dtype=b.comm.dtype, device=self.device)
-                    b.shard32 = b.shard_comm if b.comm.dtype == torch.float32 else torch.empty(
-                        n, dtype=torch.float32, device=self.device)
-                b.work = self._c_reduce_scatter(b.shard_comm, b.comm)
-            else:
-                b.work = self._c_all_reduce(b.comm)
-            if self.on_gpu:
-                b.work.wait()           # orders the communication stream after the collective (no host block)
-                self._unpack(b)
-                self._t1(t0)
-        b.launched = b.has_grad = True
-
-    def _unpack(self, b):
-        if self.reduce_scatter:
-            if b.shard32 is not b.shard_comm:
-                self._unpack_into(b.shard_comm, b.shard32)
-            b.shard = b.shard32
-        elif b.comm is not b.flat:
-            self._unpack_into(b.comm, b.flat)        # bf16 -> fp32 unpack (already averaged)
-        b.unpacked = True
+            self._exchange(b, b.flat, b.comm, scaled=True)
+        b.launched = True
 
     def finish(self, accumulate=False):
         """Wait for every bucket and hand the averaged gradients back.  ``accumulate=True`` (a micro-step of gradient
@@ -725,7 +719,6 @@ class GradReducer:
             raise RuntimeError('GradReducer.finish() without prepare()')
         self._armed = False
         self._window_done = not accumulate
-        inv = 1.0 / self.world
         for b in self.buckets:
             if b.expected == 0:
                 continue
@@ -737,7 +730,7 @@ class GradReducer:
             # acquired in this step but never released to zero (a backward call that was expected did not run):
             # reduce what it holds now -- every rank walks its sinks in creation order, so ranks that agree on which
             # passes ran issue the same collectives
-            if sb.work is None and not sb.fresh and not getattr(sb, 'reduced', False):
+            if sb.work is None and not sb.fresh and not sb.reduced:
                 self._launch_sink(sb)
         for sb in self.sinks.values():
             if sb.work is not None:
@@ -746,15 +739,15 @@ class GradReducer:
             torch.cuda.current_stream(self.device).wait_stream(self.comm_stream)
         for sb in self.sinks.values():
             if sb.work is not None:
-                if not getattr(sb, 'unpacked', False):
-                    self._unpack_sink(sb)
+                if not sb.unpacked:
+                    self._unpack(sb, sb.flat, sb.comm)
                 sb.work, sb.unpacked = None, False
             sb.fresh, sb.expected, sb.reduced = (not accumulate), 0, False
         for b in self.buckets:
             if b.expected == 0:
                 continue
-            if not getattr(b, 'unpacked', False):
-                self._unpack(b)
+            if not b.unpacked:
+                self._unpack(b, b.flat, b.comm)
             b.unpacked = False
             if self.reduce_scatter:
                 continue

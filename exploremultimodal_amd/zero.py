@@ -125,18 +125,19 @@ class ZeroAdam:
         gradient in the current accumulation window."""
         ent = []
         for pt in self.parts:
-            shard = getattr(pt.bucket, 'shard32', None)
+            b = pt.bucket
+            shard = b.shard32
             # `shard32` is a persistent buffer: it still holds the PREVIOUS window's gradient when nothing fed the bucket in
             # this one (every pass that uses it dropped from the loss, modality absent).  torch.optim / FusedAdam skip
-            # `grad is None`; so does this: only buckets reduced in the current window (GradReducer.prepare / _launch*)
-            if shard is None or not getattr(pt.bucket, 'has_grad', False):
+            # `grad is None`; so does this: only buckets reduced in the current window (GradReducer.prepare / _exchange)
+            if shard is None or not b.has_grad:
                 continue
             # parameters of a hook bucket that received no gradient in this step (an objective skipped; unused heads)
             # are left alone, as torch.optim / FusedAdam skip `grad is None` (no moment decay, no weight decay)
-            had = getattr(pt.bucket, 'had', None)
+            # (`had` is None on the engine's sink buckets: they are fed as a whole)
             skip = set()
-            if had is not None and hasattr(pt.bucket, 'offsets'):
-                skip = {id(p) for p, h in zip(pt.bucket.params, had) if not h}
+            if b.had is not None:
+                skip = {id(p) for p, h in zip(b.params, b.had) if not h}
             for p, off, gi in pt.entries:
                 if id(p) in skip:
                     continue
@@ -253,7 +254,7 @@ class ZeroAdam:
             # an unchanged slice is a no-op in value.  (Ranks must still agree on which PASSES run -- see
             # GradReducer.agree_finite -- because the reducer issues its collectives as the buckets become ready.)
             for pt in self.parts:
-                if getattr(pt.bucket, 'shard32', None) is None:
+                if pt.bucket.shard32 is None:
                     continue
                 red.all_gather(pt.pflat, pt.pflat[pt.lo:pt.hi])
         # the parameters changed behind autograd's back: invalidate the engine's bf16 weight shadows
