@@ -136,6 +136,7 @@ _SIGS = {
     'vlmo_isda_update': [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     'vlmo_isda_aug_fwd': [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _i64, _vp],
     'vlmo_isda_aug_bwd': [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _i64, _vp],
+    'vlmo_sim_topk': [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, ctypes.c_size_t, _vp, _vp, _vp],
 }
 
 _lib = None
@@ -162,6 +163,8 @@ def lib():
         L.vlmo_isda_ws_bytes.restype = ctypes.c_int64
         L.vlmo_isda_ws_bytes.argtypes = [_i32, _i32, _i32]
         L.vlmo_gemm_tn_ws_bytes.argtypes = [_i32, _i32, _i32]
+        L.vlmo_sim_topk_ws_bytes.restype = ctypes.c_int64
+        L.vlmo_sim_topk_ws_bytes.argtypes = [_i32, _i32, _i32, _i32]
         for name, sig in _SIGS.items():
             fn = getattr(L, name)
             fn.argtypes = sig
@@ -172,7 +175,7 @@ def lib():
 
 def exported_symbols():
     return ['vlmo_last_error', 'vlmo_abi_version', 'vlmo_reduce_ws_bytes', 'vlmo_gemm_tn_ws_bytes',
-            'vlmo_isda_ws_bytes'] + list(_SIGS)
+            'vlmo_isda_ws_bytes', 'vlmo_sim_topk_ws_bytes'] + list(_SIGS)
 
 
 def _check(rc, name):
@@ -584,6 +587,26 @@ def isda_aug_bwd(G, W, k, ck, B, V, A, r, dw):
     ws = _isda_ws(dw.device, B, V, A)
     _check(lib().vlmo_isda_aug_bwd(_p(G), G.stride(0), _p(W), W.stride(0), _p(k), _p(ck), ck.stride(0), B, V, A,
                                    float(r), _p(dw), dw.stride(0), _p(ws), ws.numel() * 4, _stream()), 'vlmo_isda_aug_bwd')
+
+
+def sim_topk(q, g, k, scale=1.0, splits=0):
+    """vlmo_sim_topk: the k best rows of g fp32 [Ng, D] for every row of q fp32 [Nq, D] under scale * <q, g> -> (values
+    fp32 [Nq, k], indices int32 [Nq, k]), best first, equal scores by ascending index, -inf / -1 past Ng.  Rows may be
+    strided (stride(1) == 1).  The per-slice lists of a split gallery live in a workspace allocated for this call."""
+    for t, n in ((q, 'q'), (g, 'g')):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f'sim_topk: {n} must be a 2-D fp32 tensor with unit column stride')
+    if q.shape[1] != g.shape[1] or q.device != g.device:
+        raise ValueError('sim_topk: q and g must have the same width and device')
+    Nq, D = q.shape
+    Ng = g.shape[0]
+    val = torch.empty(Nq, k, dtype=torch.float32, device=q.device)
+    idx = torch.empty(Nq, k, dtype=torch.int32, device=q.device)
+    nbytes = lib().vlmo_sim_topk_ws_bytes(Nq, Ng, k, splits)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device) if nbytes > 0 else None
+    _check(lib().vlmo_sim_topk(_p(q), q.stride(0), _p(g), g.stride(0), Nq, Ng, D, k, float(scale), splits, _p(ws), nbytes,
+                               _p(val), _p(idx), _stream()), 'vlmo_sim_topk')
+    return val, idx
 
 
 PROFILE_TAGS = 96

@@ -22,6 +22,7 @@
 #ifndef VLMO_HIP_H
 #define VLMO_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -456,6 +457,21 @@ int vlmo_isda_aug_fwd(const float* W, int ldw, const int32_t* k, const float* ck
 int vlmo_isda_aug_bwd(const void* G, int ldg, const float* W, int ldw, const int32_t* k, const float* ck, int ldc,
                       int B, int V, int A, float r, float* dw, int lddw, float* ws, int64_t ws_bytes,
                       hipStream_t stream);
+
+/* ---- retrieval ranking (zero-shot / fine-tuned image-text retrieval on the ITC features); csrc/retrieval.hip ---- */
+
+/* For every query row q < Nq the K best gallery rows under score(q, g) = scale * sum_d Q[q, d] * G[g, d], best first, in
+ * out_val fp32 / out_idx int32, both [Nq, K] contiguous.  The order is total: higher score first, and among equal scores
+ * the lower gallery index first.  With Ng < K the tail of a row is idx = -1, val = -inf.  Q [Nq, ldq], G [Ng, ldg] fp32;
+ * fp32 MFMA operands and accumulation; the [Nq, Ng] score matrix never reaches memory.  Inputs are assumed finite.
+ * Limits: 1 <= K <= 16; 4 <= D <= 1024, D % 4 == 0; ldq, ldg >= D; scale > 0; Nq, Ng >= 1.
+ * The gallery is cut into `splits` contiguous slices (0 = chosen by the library so that a small query count still fills
+ * the chip; never more slices than 128-row steps of the gallery); with more than one slice the per-slice lists go through
+ * ws (>= vlmo_sim_topk_ws_bytes of the same Nq, Ng, K, splits; 0 bytes for one slice) and a merge kernel.  No atomics; a
+ * score is one fixed-order chain over D whatever the tile or split: the same bits from run to run and for every splits. */
+int64_t vlmo_sim_topk_ws_bytes(int Nq, int Ng, int K, int splits);
+int vlmo_sim_topk(const float* Q, int ldq, const float* G, int ldg, int Nq, int Ng, int D, int K, float scale, int splits,
+                  void* ws, size_t ws_bytes, float* out_val, int32_t* out_idx, hipStream_t stream);
 
 #ifdef __cplusplus
 }
