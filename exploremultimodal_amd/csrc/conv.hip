@@ -1,5 +1,7 @@
 // dVAE convolutions over NHWC activation matrices (vlmo_conv2d_nhwc): conv3_dx_kernel for 3x3 bottlenecks and the
 // implicit-GEMM instantiations of gemm_nt_kernel (CONV = true).
+#include <type_traits>
+
 #include "gemm_common.h"
 
 namespace {
@@ -21,10 +23,20 @@ struct Conv3Args {
     f16* out;            // [B*H*W, ldo]
     int M, H, W, Cin, Cout, ldo, relu;
 };
+// VLMO_EPI_DUAL (the DUAL instantiations): v = resid + beta * (acc + bias); out = v; out2 = relu(v)
+struct Conv3DualArgs : Conv3Args {
+    const f16* resid;    // [B*H*W, ldo] or null (= 0)
+    f16* out2;           // [B*H*W, ld2] or null
+    int ld2;
+    float beta;
+};
 
-// WM x WN waves of 64 pixels x 64 channels: <4, 1> = 256 x 64 tile (<= 64 output channels), <2, 2> = 128 x 128 tile
-template <int WM, int WN>
-__global__ __launch_bounds__(256, 2) void conv3_dx_kernel(const Conv3Args a) {
+// WM x WN waves of 64 pixels x 64 channels: <4, 1> = 256 x 64 tile (<= 64 output channels), <2, 2> = 128 x 128 tile.
+// DUAL: the DecoderBlock tail (dall_e/decoder.py:42-46, conv_4 is the block's 3x3 with n_out channels): the identity
+// path's fp16 rows are requested before the K loop (8 x 16 bytes per lane, they fly under the operand staging), put into
+// the wave's epilogue image and combined there in fp32, so the sum is rounded to fp16 once.
+template <int WM, int WN, bool DUAL>
+__global__ __launch_bounds__(256, 2) void conv3_dx_kernel(const std::conditional_t<DUAL, Conv3DualArgs, Conv3Args> a) {
     static_assert(WM * WN == 4, "four waves");
     constexpr int BM = WM * 64, BN = WN * 64, HALO = 8, AROWS = BM + 2 * HALO;
     constexpr int A_BYTES = AROWS * 64, B_BYTES = 3 * BN * 64, STAGE = A_BYTES + B_BYTES;
@@ -102,6 +114,18 @@ __global__ __launch_bounds__(256, 2) void conv3_dx_kernel(const Conv3Args a) {
 #pragma unroll
             for (int k = 0; k < 16; ++k) acc[i][j][k] = 0.f;
 
+    // lane -> (row, 8-channel piece) of the wave's 64 x 64 output block in the epilogue's store passes
+    f16x8 pre[DUAL ? 8 : 1];
+    if constexpr (DUAL) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int ch = lane + 64 * q, row = ch >> 3, c8 = (ch & 7) * 8;
+            const int m = m0 + wm * 64 + row, n = n0 + wn * 64 + c8;
+            const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+            pre[q] = (a.resid && m < a.M && n < a.Cout) ? *(const f16x8*)(a.resid + (size_t)m * a.ldo + n) : z;
+        }
+    }
+
     stage(0, 0);
     for (int s_ = 0; s_ < nsteps; ++s_) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -138,6 +162,14 @@ __global__ __launch_bounds__(256, 2) void conv3_dx_kernel(const Conv3Args a) {
     f16* ep = (f16*)(smem + wave * 8192);
     const bool relu_out = (a.relu & 1) != 0;
     const int nw0 = n0 + wn * 64;
+    if constexpr (DUAL) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int ch = lane + 64 * q;
+            *(f16x8*)(ep + (ch >> 3) * 64 + (ch & 7) * 8) = pre[q];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int n = nw0 + j * 32 + l31;
@@ -147,8 +179,13 @@ __global__ __launch_bounds__(256, 2) void conv3_dx_kernel(const Conv3Args a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float v = acc[i][j][r] + bv;
-                if (relu_out) v = fmaxf(v, 0.f);
-                ep[(i * 32 + 8 * (r >> 2) + 4 * h + (r & 3)) * 64 + j * 32 + l31] = (f16)v;
+                if constexpr (DUAL) {
+                    f16* slot = ep + (i * 32 + 8 * (r >> 2) + 4 * h + (r & 3)) * 64 + j * 32 + l31;
+                    *slot = (f16)((float)*slot + a.beta * v);
+                } else {
+                    if (relu_out) v = fmaxf(v, 0.f);
+                    ep[(i * 32 + 8 * (r >> 2) + 4 * h + (r & 3)) * 64 + j * 32 + l31] = (f16)v;
+                }
             }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -158,23 +195,34 @@ __global__ __launch_bounds__(256, 2) void conv3_dx_kernel(const Conv3Args a) {
         const int m = m0 + wm * 64 + row;
         if (m < a.M && nw0 + c8 < a.Cout) {
             const f16x8 v = *(const f16x8*)(ep + row * 64 + c8);
-            __builtin_nontemporal_store(v, (f16x8*)(a.out + (size_t)m * a.ldo + nw0 + c8));
+            if constexpr (DUAL) {
+                // the next convolution reads both maps back at once: plain stores
+                *(f16x8*)(a.out + (size_t)m * a.ldo + nw0 + c8) = v;
+                const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+                if (a.out2) *(f16x8*)(a.out2 + (size_t)m * a.ld2 + nw0 + c8) = __builtin_elementwise_max(v, z);
+            } else {
+                __builtin_nontemporal_store(v, (f16x8*)(a.out + (size_t)m * a.ldo + nw0 + c8));
+            }
         }
     }
 }
 
-template <int WM, int WN>
+template <int WM, int WN, bool DUAL>
 int launch_conv3_dx(const void* x, int B, int H, int W, int Cin, const void* w, int Cout, const void* zero_page,
                     const VlmoEpilogue* e, hipStream_t stream) {
-    Conv3Args a{(const f16*)x, (const f16*)w, (const f16*)zero_page, e->bias, (f16*)e->out, B * H * W, H, W, Cin, Cout,
-                e->ldo, e->relu};
+    std::conditional_t<DUAL, Conv3DualArgs, Conv3Args> a{};
+    static_cast<Conv3Args&>(a) = Conv3Args{(const f16*)x, (const f16*)w, (const f16*)zero_page, e->bias, (f16*)e->out,
+                                           B * H * W, H, W, Cin, Cout, e->ldo, e->relu};
+    if constexpr (DUAL) {
+        a.resid = (const f16*)(const void*)e->resid, a.out2 = (f16*)e->out2, a.ld2 = e->ld2, a.beta = e->beta;
+    }
     constexpr int BM = WM * 64, BN = WN * 64;
     constexpr int LDS = 2 * ((BM + 16) * 64 + 3 * BN * 64);
     static DeviceOnce once;
     if (once.first())
-        (void)hipFuncSetAttribute((const void*)conv3_dx_kernel<WM, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)conv3_dx_kernel<WM, WN, DUAL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     const int grid = ((a.M + BM - 1) / BM) * ((Cout + BN - 1) / BN);
-    hipLaunchKernelGGL((conv3_dx_kernel<WM, WN>), dim3(grid), dim3(256), LDS, stream, a);
+    hipLaunchKernelGGL((conv3_dx_kernel<WM, WN, DUAL>), dim3(grid), dim3(256), LDS, stream, a);
     VLMO_CHECK_LAUNCH("vlmo_conv2d_nhwc");
     return 0;
 }
@@ -204,8 +252,15 @@ extern "C" int vlmo_conv2d_nhwc(int epi, int dtype, const void* x, int B, int H,
             return launch_nt<f16, 256, 256, 2, 4, true, 64, 2, true, (1u << VLMO_EPI_BIAS)>(epi, p, stream);
     }
     if (dtype == VLMO_F16 && epi == VLMO_EPI_BIAS && kw == 3 && Cin % 32 == 0 && Cout % 8 == 0 && e->ldo % 8 == 0) {
-        if (Cout <= 64) return launch_conv3_dx<4, 1>(x, B, H, W, Cin, w, Cout, zero_page, e, stream);
-        return launch_conv3_dx<2, 2>(x, B, H, W, Cin, w, Cout, zero_page, e, stream);
+        if (Cout <= 64) return launch_conv3_dx<4, 1, false>(x, B, H, W, Cin, w, Cout, zero_page, e, stream);
+        return launch_conv3_dx<2, 2, false>(x, B, H, W, Cin, w, Cout, zero_page, e, stream);
+    }
+    // DecoderBlock tail (3x3, residual epilogue) under the same shape conditions; the residual rows and the second output
+    // move as 16-byte pieces too
+    if (dtype == VLMO_F16 && epi == VLMO_EPI_DUAL && kw == 3 && Cin % 32 == 0 && Cout % 8 == 0 && e->ldo % 8 == 0 &&
+        (!e->out2 || e->ld2 % 8 == 0)) {
+        if (Cout <= 64) return launch_conv3_dx<4, 1, true>(x, B, H, W, Cin, w, Cout, zero_page, e, stream);
+        return launch_conv3_dx<2, 2, true>(x, B, H, W, Cin, w, Cout, zero_page, e, stream);
     }
     // <= 64 output channels: a 256 x 64 tile -- with the 128-wide tile half of every MFMA and half of the weight staging
     // multiplied padding

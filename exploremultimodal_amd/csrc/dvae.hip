@@ -1,4 +1,4 @@
-// Glue kernels of the dall_e dVAE encoder (dall_e/encoder.py:74-121) around the
+// Glue kernels of the dall_e dVAE encoder (dall_e/encoder.py:74-121) and decoder (dall_e/decoder.py:75-124) around the
 // implicit-GEMM convolutions of conv.hip.  Activations are NHWC fp16 matrices
 // [B*H*W, C] (the reference runs this encoder in fp16 on GPU: dall_e/utils.py:37-42).
 #include "common.h"
@@ -189,6 +189,95 @@ __global__ __launch_bounds__(256) void ce_reduce_kernel(const float* __restrict_
     }
 }
 
+
+// ---- decoder (dall_e/decoder.py) ----------------------------------------------------------------------------------
+// input convolution on a one-hot map (decoder.py:77-78 after modeling_discrete_vae.py:241-243) = a row gather of the
+// transposed fp32 weight: out[m] = fp16(table[ids[m]] + bias).  One thread = 8 channels (two 16-byte loads of the table
+// row, one 16-byte store).  The host has checked the ids; the clamp keeps a stale id from reading outside the table.
+__global__ __launch_bounds__(256) void dvae_embed_kernel(const int64_t* __restrict__ ids, const float* __restrict__ table,
+                                                         const float* __restrict__ bias, f16* __restrict__ out, long total8,
+                                                         int vocab, int n_init) {
+    const int c8n = n_init / 8;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total8; i += (long)gridDim.x * 256) {
+        const long m = i / c8n;
+        const int c0 = (int)(i - m * c8n) * 8;
+        const long raw = (long)ids[m];
+        const long id = raw < 0 ? 0 : (raw >= vocab ? vocab - 1 : raw);
+        const float* row = table + id * n_init + c0;
+        const f32x4 a = *(const f32x4*)row, b = *(const f32x4*)(row + 4);
+        const f32x4 ba = *(const f32x4*)(bias + c0), bb = *(const f32x4*)(bias + c0 + 4);
+        f16x8 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[j] = (f16)(a[j] + ba[j]);
+            v[4 + j] = (f16)(b[j] + bb[j]);
+        }
+        *(f16x8*)(out + m * n_init + c0) = v;
+    }
+}
+
+// nn.Upsample(scale_factor=2, mode='nearest') on NHWC (decoder.py:85,95,105): one thread reads 8 channels of a source
+// pixel once and stores them to its four output pixels.
+__global__ __launch_bounds__(256) void upsample2_kernel(const f16* __restrict__ x, f16* __restrict__ out, int H, int W,
+                                                        int C, long total8) {
+    const int c8n = C / 8;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total8; i += (long)gridDim.x * 256) {
+        const int c0 = (int)(i % c8n) * 8;
+        const long m = i / c8n;                         // source pixel (b, y, x)
+        const long by = m / W;                          // b * H + y
+        const int xx = (int)(m - by * W);
+        const f16x8 v = *(const f16x8*)(x + m * C + c0);
+        f16* o = out + ((2 * by) * (2 * (long)W) + 2 * xx) * C + c0;
+        *(f16x8*)o = v;
+        *(f16x8*)(o + C) = v;
+        *(f16x8*)(o + 2 * (long)W * C) = v;
+        *(f16x8*)(o + 2 * (long)W * C + C) = v;
+    }
+}
+
+// output head (decoder.py:116-123): out[b, co, y, x] = bias[co] + sum_c relu(x[m, c]) * w[co, c] for <= 8 output channels,
+// fp32 NCHW.  Bound by the read of x: the weights sit in LDS as fp32, 8 lanes share a pixel (each 16-byte piece of the
+// row is read once, 128 contiguous bytes per pixel and pass), a wave covers 8 consecutive pixels; the 8 lanes' partial
+// sums meet in three butterfly steps and lane co of the group stores channel co.
+template <int CO>
+__global__ __launch_bounds__(256) void out_head_kernel(const f16* __restrict__ x, const f16* __restrict__ w,
+                                                       const float* __restrict__ bias, float* __restrict__ out, long M,
+                                                       int HW, int C) {
+    extern __shared__ __attribute__((aligned(16))) float wl[];      // [CO][C]
+    for (int i = threadIdx.x; i < CO * C; i += 256) wl[i] = (float)w[i];
+    __syncthreads();
+    const int sub = threadIdx.x & 7;
+    const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (long m = (long)blockIdx.x * 32 + (threadIdx.x >> 3); m < M; m += (long)gridDim.x * 32) {
+        float acc[CO];
+#pragma unroll
+        for (int co = 0; co < CO; ++co) acc[co] = 0.f;
+        const f16* row = x + m * C;
+        for (int c0 = sub * 8; c0 < C; c0 += 64) {
+            const f16x8 v = __builtin_elementwise_max(__builtin_nontemporal_load((const f16x8*)(row + c0)), z);
+#pragma unroll
+            for (int co = 0; co < CO; ++co) {
+                const f32x4 wa = *(const f32x4*)(wl + co * C + c0), wb = *(const f32x4*)(wl + co * C + c0 + 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[co] += (float)v[j] * wa[j] + (float)v[4 + j] * wb[j];
+            }
+        }
+        float mine = 0.f;
+#pragma unroll
+        for (int co = 0; co < CO; ++co) {
+            float s = acc[co];
+            s += __shfl_xor(s, 1, 64);
+            s += __shfl_xor(s, 2, 64);
+            s += __shfl_xor(s, 4, 64);
+            if (sub == co) mine = s;
+        }
+        if (sub < CO) {
+            const long b = m / HW, pix = m - b * HW;
+            out[(b * CO + sub) * HW + pix] = mine + bias[sub];
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int vlmo_ce_reduce(const float* partial, int nchunk, const int32_t* labels, int ignore_index, float* lse,
@@ -233,5 +322,55 @@ extern "C" int vlmo_argmax_reduce(const float* partial, int nchunk, int64_t* ids
     VLMO_CHECK_ARG(partial && ids && M > 0 && nchunk > 0, "vlmo_argmax_reduce: bad arguments");
     hipLaunchKernelGGL(argmax_reduce_kernel, dim3((M + 3) / 4), dim3(256), 0, stream, partial, nchunk, ids, M);
     VLMO_CHECK_LAUNCH("vlmo_argmax_reduce");
+    return 0;
+}
+
+static int elementwise_grid(long total) {
+    const long blocks = (total + 255) / 256;
+    return (int)(blocks < 65536 ? blocks : 65536);
+}
+
+extern "C" int vlmo_dvae_embed(const int64_t* ids, const float* table, const float* bias, void* out, int M, int vocab,
+                               int n_init, hipStream_t stream) {
+    VLMO_CHECK_ARG(ids && table && bias && out, "vlmo_dvae_embed: null pointer");
+    VLMO_CHECK_ARG(M > 0 && vocab > 0 && n_init > 0 && n_init % 8 == 0, "vlmo_dvae_embed: n_init must be a multiple of 8");
+    const long total8 = (long)M * (n_init / 8);
+    hipLaunchKernelGGL(dvae_embed_kernel, dim3(elementwise_grid(total8)), dim3(256), 0, stream, ids, table, bias, (f16*)out,
+                       total8, vocab, n_init);
+    VLMO_CHECK_LAUNCH("vlmo_dvae_embed");
+    return 0;
+}
+
+extern "C" int vlmo_upsample2_nhwc(const void* x, void* out, int B, int H, int W, int C, hipStream_t stream) {
+    VLMO_CHECK_ARG(x && out, "vlmo_upsample2_nhwc: null pointer");
+    VLMO_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "vlmo_upsample2_nhwc: C must be a multiple of 8");
+    const long total8 = (long)B * H * W * (C / 8);
+    hipLaunchKernelGGL(upsample2_kernel, dim3(elementwise_grid(total8)), dim3(256), 0, stream, (const f16*)x, (f16*)out, H,
+                       W, C, total8);
+    VLMO_CHECK_LAUNCH("vlmo_upsample2_nhwc");
+    return 0;
+}
+
+extern "C" int vlmo_dvae_out_head(const void* x, const void* w, const float* bias, float* out, int B, int H, int W, int C,
+                                  int Cout, hipStream_t stream) {
+    VLMO_CHECK_ARG(x && w && bias && out, "vlmo_dvae_out_head: null pointer");
+    VLMO_CHECK_ARG(B > 0 && H > 0 && W > 0 && (long)H * W < 0x7fffffffL, "vlmo_dvae_out_head: bad geometry");
+    VLMO_CHECK_ARG(Cout >= 1 && Cout <= 8, "vlmo_dvae_out_head: 1 <= Cout <= 8 (got %d)", Cout);
+    VLMO_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 1024, "vlmo_dvae_out_head: C must be a multiple of 8, at most 1024 (got %d)", C);
+    const long M = (long)B * H * W;
+    const long blocks = (M + 31) / 32;
+    const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
+    const size_t lds = (size_t)Cout * C * sizeof(float);
+#define VLMO_OUT_HEAD(CO)                                                                                              \
+    case CO:                                                                                                           \
+        hipLaunchKernelGGL(out_head_kernel<CO>, grid, dim3(256), lds, stream, (const f16*)x, (const f16*)w, bias, out, \
+                           M, H * W, C);                                                                               \
+        break;
+    switch (Cout) {
+        VLMO_OUT_HEAD(1) VLMO_OUT_HEAD(2) VLMO_OUT_HEAD(3) VLMO_OUT_HEAD(4)
+        VLMO_OUT_HEAD(5) VLMO_OUT_HEAD(6) VLMO_OUT_HEAD(7) VLMO_OUT_HEAD(8)
+    }
+#undef VLMO_OUT_HEAD
+    VLMO_CHECK_LAUNCH("vlmo_dvae_out_head");
     return 0;
 }

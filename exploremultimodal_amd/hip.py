@@ -102,6 +102,9 @@ _SIGS = {
     'vlmo_dvae_im2col': [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     'vlmo_maxpool2_nhwc': [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     'vlmo_argmax_reduce': [_vp, _i32, _vp, _i32, _vp],
+    'vlmo_dvae_embed': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
+    'vlmo_upsample2_nhwc': [_vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    'vlmo_dvae_out_head': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     'vlmo_ce_reduce': [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
     'vlmo_stack_fwd': [ctypes.POINTER(StackDesc), _vp],
     'vlmo_stack_bwd': [ctypes.POINTER(StackDesc), _vp],
@@ -140,7 +143,7 @@ _SIGS = {
 }
 
 _lib = None
-ABI_VERSION = 6      # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
+ABI_VERSION = 7      # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
 
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is missing."""
@@ -391,7 +394,7 @@ def embed_txt_bwd(dx, ids, xhat, rstd, ln_w, dword, dpos, dbtype0, dln_w, dln_b,
     _check(rc, 'vlmo_embed_txt_bwd')
 
 
-# ------------------------------------------------------------------ dVAE encoder
+# ------------------------------------------------------------------ dVAE encoder / decoder
 _ZERO = {}
 
 
@@ -423,6 +426,24 @@ def maxpool2_nhwc(x, raw, relu, B, H, W, C):
 
 def argmax_reduce(partial, nchunk, ids, M):
     _check(lib().vlmo_argmax_reduce(_p(partial), nchunk, _p(ids), M, _stream()), 'vlmo_argmax_reduce')
+
+
+def dvae_embed(ids, table, bias, out):
+    """out f16 [M, n_init] = fp16(table[ids] + bias); ids int64 [M] already checked to lie in [0, vocab)."""
+    vocab, n_init = table.shape
+    _check(lib().vlmo_dvae_embed(_p(ids), _p(table), _p(bias), _p(out), ids.numel(), vocab, n_init, _stream()),
+           'vlmo_dvae_embed')
+
+
+def upsample2_nhwc(x, out, B, H, W, C):
+    """Nearest-neighbour 2x upsampling of an NHWC map: x [B*H*W, C] -> out [B*2H*2W, C] (f16)."""
+    _check(lib().vlmo_upsample2_nhwc(_p(x), _p(out), B, H, W, C, _stream()), 'vlmo_upsample2_nhwc')
+
+
+def dvae_out_head(x, w, bias, out, B, H, W):
+    """out f32 [B, Cout, H, W] = conv1x1(relu(x)) + bias; x f16 [B*H*W, C], w f16 [Cout, C], Cout <= 8."""
+    Cout, C = w.shape
+    _check(lib().vlmo_dvae_out_head(_p(x), _p(w), _p(bias), _p(out), B, H, W, C, Cout, _stream()), 'vlmo_dvae_out_head')
 
 
 def gemm_tn_multi(problems, dtype=BF16):

@@ -82,7 +82,7 @@ typedef struct VlmoEpilogue {
 const char* vlmo_last_error(void);
 /* Version of the struct layouts and signatures below; raised whenever one of them changes
  * (exploremultimodal_amd/hip.py mirrors it as ABI_VERSION and refuses any other). */
-#define VLMO_ABI_VERSION 6
+#define VLMO_ABI_VERSION 7
 int vlmo_abi_version(void);     /* = VLMO_ABI_VERSION of the header the library was built from */
 
 /* C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue.  tile: -1 = pick by shape, 0 = 128x128x64
@@ -382,11 +382,13 @@ int vlmo_comm_all_gather(void* comm, const void* send, void* recv, int64_t send_
 int vlmo_grad_pack(const float* src, void* dst_bf16, int64_t n, float scale, hipStream_t stream);
 int vlmo_grad_unpack(const void* src_bf16, float* dst, int64_t n, hipStream_t stream);
 
-/* ---- dall_e dVAE encoder (dall_e/encoder.py:49-133), fp16 NHWC activations [B*H*W, C] ---- */
+/* ---- dall_e dVAE encoder (dall_e/encoder.py:49-133) and decoder (dall_e/decoder.py:49-136), fp16 NHWC activations
+ * [B*H*W, C] ---- */
 
 /* Conv2d, stride 1, same padding (kw-1)/2 (dall_e/utils.py:37-48) as implicit GEMM:
  * x [B*H*W, Cin], w [Cout, kw*kw*Cin] (tap-major, channel-minor), zero_page = >= 128 zero bytes.
- * Epilogues: VLMO_EPI_BIAS (relu flag), VLMO_EPI_DUAL (EncoderBlock tail, encoder.py:45-46), VLMO_EPI_F32. */
+ * Epilogues: VLMO_EPI_BIAS (relu flag), VLMO_EPI_DUAL (block tail id + post_gain * res, encoder.py:45-46 and
+ * decoder.py:45-46: resid = the identity path's rows in the activation type, [M, ldo]; out2 may be NULL), VLMO_EPI_F32. */
 int vlmo_conv2d_nhwc(int epi, int dtype, const void* x, int B, int H, int W, int Cin, int kw,
                      const void* w, int Cout, const void* zero_page, const VlmoEpilogue* e,
                      hipStream_t stream);
@@ -396,6 +398,17 @@ int vlmo_dvae_im2col(const float* x, void* out, int B, int C, int H, int W, int 
 /* MaxPool2d(2) (encoder.py:85,95,105): raw pooled map + relu of it (relu may be NULL). */
 int vlmo_maxpool2_nhwc(const void* x, void* raw, void* relu, int B, int H, int W, int C,
                        hipStream_t stream);
+/* Decoder input convolution on a one-hot map (decoder.py:77-78 after modeling_discrete_vae.py:241-243) as a row gather:
+ * out f16 [M, n_init] = fp16(table[ids[m]] + bias), table = the fp32 weight transposed to [vocab, n_init].  n_init % 8 == 0.
+ * ids must lie in [0, vocab): the caller checks them (an id outside is clamped, never dereferenced outside the table). */
+int vlmo_dvae_embed(const int64_t* ids, const float* table, const float* bias, void* out, int M, int vocab,
+                    int n_init, hipStream_t stream);
+/* nn.Upsample(scale_factor=2, mode='nearest') (decoder.py:85,95,105): x f16 [B*H*W, C] -> out f16 [B*2H*2W, C]. C % 8 == 0. */
+int vlmo_upsample2_nhwc(const void* x, void* out, int B, int H, int W, int C, hipStream_t stream);
+/* Decoder output head (decoder.py:116-123): out f32 NCHW [B, Cout, H, W] = conv1x1(relu(x)) + bias for x f16 [B*H*W, C],
+ * w f16 [Cout, C], 1 <= Cout <= 8, C % 8 == 0, C <= 1024. */
+int vlmo_dvae_out_head(const void* x, const void* w, const float* bias, float* out, int B, int H, int W, int C,
+                       int Cout, hipStream_t stream);
 /* finish of VLMO_EPI_CE: partial [M, nchunk, 4] -> lse [M], loss [M] (lse - label logit; 0 where
  * labels[m] == ignore_index; may be NULL), pred [M] (arg-max, first maximum wins; may be NULL). */
 int vlmo_ce_reduce(const float* partial, int nchunk, const int32_t* labels, int ignore_index, float* lse,
