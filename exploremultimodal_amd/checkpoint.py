@@ -4,7 +4,9 @@ the newest ``<exp_dir>/*/checkpoint-N.pth`` and loading through ``VlmoModule.loa
 layout, position-embedding interpolation) -- utils/utils.py:534-612.  Files written by either side load in the
 other: parameter names are the reference's and the optimizer state is ``torch.optim.AdamW``-shaped.
 The DeepSpeed (``.ds``) branches of the reference are not provided: sharded state is this framework's own
-``exploremultimodal_amd.dp`` reducer, which keeps ordinary replicated ``.pth`` checkpoints."""
+``exploremultimodal_amd.dp`` reducer, which keeps ordinary replicated ``.pth`` checkpoints.
+A weight average (``ema.ModelEma``) travels as the ``'model_ema'`` entry, a state dict with the keys of ``'model'``
+(utils/utils.py:506-508)."""
 import glob
 import os
 import shutil
@@ -24,11 +26,10 @@ def save_on_master(obj, path):
 
 
 def save_model(cfg, epoch, model, model_without_ddp, optimizer, lr_scheduler, loss_scaler, model_ema=None):
-    """utils/utils.py:479-520 (torch.amp branch).  Returns the file name."""
+    """utils/utils.py:479-520 (torch.amp branch).  Returns the file name.  ``model_ema``: an ``ema.ModelEma``, written
+    as ``'model_ema'``."""
     if loss_scaler is None:
         raise NotImplementedError('DeepSpeed checkpoints (.ds) are not provided; pass the loss scaler object')
-    if model_ema is not None:
-        raise NotImplementedError('EMA twins (vlmo_ema) are out of scope')
     output_dir = Path(cfg.output_dir)
     ckpt_name = f'checkpoint-{epoch}.pth'
     to_save = {
@@ -39,6 +40,8 @@ def save_model(cfg, epoch, model, model_without_ddp, optimizer, lr_scheduler, lo
         'scaler': loss_scaler.state_dict(),
         'cfg': cfg,
     }
+    if model_ema is not None:
+        to_save['model_ema'] = model_ema.module.state_dict()
     if _is_master():
         output_dir.mkdir(parents=True, exist_ok=True)
     save_on_master(to_save, output_dir / ckpt_name)
@@ -67,7 +70,13 @@ def latest_checkpoint(exp_dir, pattern='checkpoint-%d.pth'):
 def auto_load_model(cfg, model, model_without_ddp, optimizer, lr_scheduler, loss_scaler, model_ema=None, logger=None):
     """utils/utils.py:534-612 (torch.amp branch): resolve ``cfg.train.resume`` (auto-resume picks the newest
     checkpoint under ``cfg.exp_dir``), load the weights through ``load_from_ckpt`` and -- when the checkpoint was
-    written by the same ``(train.phase, tag)`` -- the optimizer / schedule / scaler state and ``start_epoch``."""
+    written by the same ``(train.phase, tag)`` -- the optimizer / schedule / scaler state and ``start_epoch``.
+
+    ``model_ema`` (an ``ema.ModelEma``) is restored in that same branch from the checkpoint's ``'model_ema'`` entry; when
+    nothing was restored (no such entry, or another ``(phase, tag)``) it becomes a copy of the weights just loaded, with a
+    warning.  (The reference calls
+    ``ModelEma._load_checkpoint`` there, a method of timm's first ``ModelEma`` that the ``ModelEmaV2`` it constructs
+    does not have; loading the state dict into ``.module`` is what that method did.)"""
     import logging
     logger = logger or logging.getLogger(__name__)
     if loss_scaler is None:
@@ -93,6 +102,7 @@ def auto_load_model(cfg, model, model_without_ddp, optimizer, lr_scheduler, loss
         logger.warning(f'Weights not initialized from pretrained model: {match.missing_keys}')
     if len(match.unexpected_keys) > 0:
         logger.warning(f'Weights from pretrained model not used: {match.unexpected_keys}')
+    ema_restored = False
     if 'cfg' in ckpt:
         ckpt_cfg = ckpt['cfg']
         if (cfg.train.phase, cfg.tag) == (ckpt_cfg.train.phase, ckpt_cfg.tag):
@@ -103,5 +113,13 @@ def auto_load_model(cfg, model, model_without_ddp, optimizer, lr_scheduler, loss
                     lr_scheduler.load_state_dict(ckpt['lr_scheduler'])
                 if 'scaler' in ckpt:
                     loss_scaler.load_state_dict(ckpt['scaler'])
+                if model_ema is not None and 'model_ema' in ckpt:
+                    model_ema.load_state_dict(ckpt['model_ema'])
+                    ema_restored = True
                 logger.info('Load states with optim & sched!')
+    if model_ema is not None and not ema_restored:
+        # no entry in the file, or another (phase, tag) (fine-tuning from a pretrained checkpoint): the average would
+        # otherwise still hold the weights the model had before this load
+        logger.warning(f'no model_ema state restored from {cfg.train.resume}: the average restarts from the loaded weights')
+        model_ema.set(model_without_ddp)
     return match

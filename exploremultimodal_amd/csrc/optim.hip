@@ -64,10 +64,47 @@ __global__ __launch_bounds__(OPT_THREADS) void mt_norm_finish_kernel(const float
     }
 }
 
-__global__ __launch_bounds__(OPT_THREADS) void mt_adam_kernel(const VlmoTensorList tl, const VlmoAdamArgs a,
-                                                             const float* __restrict__ ctl) {
+// One step of the weight average e <- e + w (p - e), w = 1 - decay.  e == p is an exact fixed point (p - e = 0), so the
+// average of a tensor that never changes never drifts, which decay * e + w * p does not give.  From w = 0.5 on the same
+// value is written from p's side, p - (1 - w) (p - e), as torch.lerp does: w = 1 then copies p exactly (w - 1 is exact
+// there).  Every kernel that averages calls this.
+__device__ __forceinline__ float ema_update(float e, float p, float w) {
+    const float d = p - e;
+    return w < 0.5f ? fmaf(w, d, e) : fmaf(w - 1.f, d, p);
+}
+
+// e[0, n) <- average toward p[0, n): 16-byte accesses when both pointers are aligned, a scalar tail, a scalar path otherwise
+__device__ __forceinline__ void ema_chunk(float* e, const float* p, int64_t n, float w) {
+    if (((((uintptr_t)e) | ((uintptr_t)p)) & 15) == 0) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = threadIdx.x; i < n4; i += OPT_THREADS) {
+            f32x4 ee = ((f32x4*)e)[i];
+            const f32x4 pp = ((const f32x4*)p)[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ee[j] = ema_update(ee[j], pp[j], w);
+            ((f32x4*)e)[i] = ee;
+        }
+        for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += OPT_THREADS) e[i] = ema_update(e[i], p[i], w);
+    } else {
+        for (int64_t i = threadIdx.x; i < n; i += OPT_THREADS) e[i] = ema_update(e[i], p[i], w);
+    }
+}
+
+// The Adam step of one chunk.  EMA: the weight average of the tensor (ema[t], or 0 for a tensor without one) takes its
+// step toward the NEW parameter value in the same pass; a skipped step still moves it, toward the unchanged parameters.
+// mt_adam_kernel is the instance without, so the two kernels share every line of the Adam update.
+template <bool EMA>
+__device__ __forceinline__ void adam_chunk(const VlmoTensorList& tl, const VlmoAdamArgs& a, const float* __restrict__ ctl,
+                                           const int64_t* __restrict__ ema, float w) {
     const float gscale = ctl ? ctl[1] : 1.f;
-    if (ctl && ctl[2] != 0.f) return;       // non-finite gradients: skip the step
+    if (ctl && ctl[2] != 0.f) {             // non-finite gradients: skip the step
+        if (EMA) {
+            const int t = tl.chunk_tensor[blockIdx.x];
+            const int64_t off = tl.chunk_start[blockIdx.x];
+            if (ema[t]) ema_chunk((float*)ema[t] + off, (const float*)tl.p[t] + off, min((int64_t)tl.chunk, tl.numel[t] - off), w);
+        }
+        return;
+    }
     const int c = blockIdx.x;
     const int t = tl.chunk_tensor[c];
     const int64_t off = tl.chunk_start[c];
@@ -76,6 +113,7 @@ __global__ __launch_bounds__(OPT_THREADS) void mt_adam_kernel(const VlmoTensorLi
     const float* g = (const float*)tl.g[t] + off;
     float* m = (float*)tl.m[t] + off;
     float* v = (float*)tl.v[t] + off;
+    float* e = EMA && ema[t] ? (float*)ema[t] + off : nullptr;
     const float lr = tl.lr[t], wd = tl.wd[t];
     const float b1 = a.beta1, b2 = a.beta2, ob1 = 1.f - a.beta1, ob2 = 1.f - a.beta2;
     auto upd = [&](float& pp, float gg, float& mm, float& vv) {
@@ -88,7 +126,7 @@ __global__ __launch_bounds__(OPT_THREADS) void mt_adam_kernel(const VlmoTensorLi
         if (a.adam_w_mode) u += wd * pp;                   // decoupled decay
         pp -= lr * u;
     };
-    const bool al = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
+    const bool al = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)e)) & 15) == 0;
     if (al) {
         const int64_t n4 = n >> 2;
         for (int64_t i = threadIdx.x; i < n4; i += OPT_THREADS) {
@@ -101,11 +139,42 @@ __global__ __launch_bounds__(OPT_THREADS) void mt_adam_kernel(const VlmoTensorLi
                 pp[j] = x, mm[j] = y, vv[j] = z;
             }
             ((f32x4*)p)[i] = pp, ((f32x4*)m)[i] = mm, ((f32x4*)v)[i] = vv;
+            if (EMA && e) {
+                f32x4 ee = ((f32x4*)e)[i];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) ee[j] = ema_update(ee[j], pp[j], w);
+                ((f32x4*)e)[i] = ee;
+            }
         }
         for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += OPT_THREADS) upd(p[i], g[i], m[i], v[i]);
+        // the scalar elements average in a loop of their own (each thread re-reads what it just wrote): appended to the
+        // update above they changed which of its multiply-adds the compiler fuses, and with that its last bit
+        if (EMA && e)
+            for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += OPT_THREADS) e[i] = ema_update(e[i], p[i], w);
     } else {
         for (int64_t i = threadIdx.x; i < n; i += OPT_THREADS) upd(p[i], g[i], m[i], v[i]);
+        if (EMA && e)
+            for (int64_t i = threadIdx.x; i < n; i += OPT_THREADS) e[i] = ema_update(e[i], p[i], w);
     }
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void mt_adam_kernel(const VlmoTensorList tl, const VlmoAdamArgs a,
+                                                             const float* __restrict__ ctl) {
+    adam_chunk<false>(tl, a, ctl, nullptr, 0.f);
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void mt_adam_ema_kernel(const VlmoTensorList tl, const VlmoAdamArgs a,
+                                                                 const float* __restrict__ ctl,
+                                                                 const int64_t* __restrict__ ema, float w) {
+    adam_chunk<true>(tl, a, ctl, ema, w);
+}
+
+// tl.p[t] = the average (written in place), tl.g[t] = the tensor it follows
+__global__ __launch_bounds__(OPT_THREADS) void mt_ema_kernel(const VlmoTensorList tl, float w) {
+    const int c = blockIdx.x;
+    const int t = tl.chunk_tensor[c];
+    const int64_t off = tl.chunk_start[c];
+    ema_chunk((float*)tl.p[t] + off, (const float*)tl.g[t] + off, min((int64_t)tl.chunk, tl.numel[t] - off), w);
 }
 
 int check_list(const VlmoTensorList* tl, const char* who) {
@@ -137,5 +206,28 @@ extern "C" int vlmo_mt_adam(const VlmoTensorList* tl, const VlmoAdamArgs* a, con
     VLMO_CHECK_ARG(tl->p && tl->m && tl->v && tl->lr && tl->wd, "vlmo_mt_adam: null table");
     hipLaunchKernelGGL(mt_adam_kernel, dim3(tl->n_chunks), dim3(OPT_THREADS), 0, stream, *tl, *a, ctl);
     VLMO_CHECK_LAUNCH("vlmo_mt_adam");
+    return 0;
+}
+
+extern "C" int vlmo_mt_ema(const VlmoTensorList* tl, float w, hipStream_t stream) {
+    if (int rc = check_list(tl, "vlmo_mt_ema")) return rc;
+    VLMO_CHECK_ARG(w >= 0.f && w <= 1.f, "vlmo_mt_ema: w = 1 - decay = %g is outside [0, 1]", (double)w);
+    if (tl->n_chunks == 0) return 0;
+    VLMO_CHECK_ARG(tl->p, "vlmo_mt_ema: null table");
+    hipLaunchKernelGGL(mt_ema_kernel, dim3(tl->n_chunks), dim3(OPT_THREADS), 0, stream, *tl, w);
+    VLMO_CHECK_LAUNCH("vlmo_mt_ema");
+    return 0;
+}
+
+extern "C" int vlmo_mt_adam_ema(const VlmoTensorList* tl, const VlmoAdamArgs* a, const float* ctl, const void* const* ema,
+                                float w, hipStream_t stream) {
+    if (int rc = check_list(tl, "vlmo_mt_adam_ema")) return rc;
+    VLMO_CHECK_ARG(a && a->beta1 >= 0.f && a->beta1 < 1.f && a->beta2 >= 0.f && a->beta2 < 1.f && a->eps >= 0.f,
+                   "vlmo_mt_adam_ema: bad hyper-parameters");
+    VLMO_CHECK_ARG(w >= 0.f && w <= 1.f, "vlmo_mt_adam_ema: w = 1 - decay = %g is outside [0, 1]", (double)w);
+    if (tl->n_chunks == 0) return 0;
+    VLMO_CHECK_ARG(tl->p && tl->m && tl->v && tl->lr && tl->wd && ema, "vlmo_mt_adam_ema: null table");
+    hipLaunchKernelGGL(mt_adam_ema_kernel, dim3(tl->n_chunks), dim3(OPT_THREADS), 0, stream, *tl, *a, ctl, (const int64_t*)ema, w);
+    VLMO_CHECK_LAUNCH("vlmo_mt_adam_ema");
     return 0;
 }

@@ -117,6 +117,8 @@ _SIGS = {
     'vlmo_gemm_nt_grouped': [_i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp],
     'vlmo_mt_grad_norm': [ctypes.c_void_p, _f32, _f32, _vp, _vp, _vp],
     'vlmo_mt_adam': [ctypes.c_void_p, ctypes.c_void_p, _vp, _vp],
+    'vlmo_mt_ema': [ctypes.c_void_p, _f32, _vp],
+    'vlmo_mt_adam_ema': [ctypes.c_void_p, ctypes.c_void_p, _vp, _vp, _f32, _vp],
     'vlmo_side_stream_create': [_i32, ctypes.POINTER(ctypes.c_uint32), _i32, ctypes.POINTER(ctypes.c_void_p)],
     'vlmo_profile_stop': [_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                           ctypes.POINTER(ctypes.c_int64)],
@@ -143,7 +145,7 @@ _SIGS = {
 }
 
 _lib = None
-ABI_VERSION = 7      # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
+ABI_VERSION = 8      # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
 
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is missing."""
@@ -652,6 +654,18 @@ def mt_grad_norm(tl, inv_scale, max_norm, partial, out):
 
 def mt_adam(tl, args, ctl=None):
     _check(lib().vlmo_mt_adam(ctypes.byref(tl), ctypes.byref(args), _p(ctl), _stream()), 'vlmo_mt_adam')
+
+
+def mt_ema(tl, w):
+    """Weight average in place: tensor tl.p[t] <- tl.p[t] + w * (tl.g[t] - tl.p[t]) for every tensor of the list."""
+    _check(lib().vlmo_mt_ema(ctypes.byref(tl), float(w), _stream()), 'vlmo_mt_ema')
+
+
+def mt_adam_ema(tl, args, ctl, ema, w):
+    """mt_adam, then the average of the new parameter values in the same pass; ema = device int64 table parallel to
+    tl.p holding the address of each tensor's average (0: none)."""
+    _check(lib().vlmo_mt_adam_ema(ctypes.byref(tl), ctypes.byref(args), _p(ctl), _p(ema), float(w), _stream()),
+           'vlmo_mt_adam_ema')
 
 
 def side_stream_create(low_priority=True, cu_mask=None):

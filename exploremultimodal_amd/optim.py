@@ -90,7 +90,13 @@ class FusedAdam(torch.optim.Optimizer):
 
     ``step(clip_grad=None, grad_scale=1.0)``: with ``clip_grad`` the gradients are scaled by
     ``min(1, clip_grad / (norm + 1e-6))`` inside the update (``.grad`` itself is left untouched) and the global
-    norm (a 0-dim device tensor, no host sync) is returned.  Parameters without ``.grad`` are skipped."""
+    norm (a 0-dim device tensor, no host sync) is returned.  Parameters without ``.grad`` are skipped.
+
+    ``step(..., ema=model_ema)`` (an ``ema.ModelEma``) also moves the weight average one step toward the model it
+    follows, with the same result as ``step()`` followed by ``model_ema.update(model)``: the tensors that step in this
+    call and have a twin in the average take ``vlmo_mt_adam_ema`` (the average of the new value in the same pass),
+    every other entry of the average -- parameters without a gradient this step, frozen ones, buffers, tensors
+    outside this optimizer -- one ``vlmo_mt_ema`` launch."""
 
     def __init__(self, params, lr=1e-3, bias_correction=True, betas=(0.9, 0.999), eps=1e-8, adam_w_mode=True,
                  weight_decay=0., amsgrad=False):
@@ -100,6 +106,7 @@ class FusedAdam(torch.optim.Optimizer):
         super().__init__(params, defaults)
         self.adam_w_mode = 1 if adam_w_mode else 0
         self._tabs = {}          # signature -> [device buffers, host staging, TensorList, turn] (a few at most)
+        self._ema_tabs = {}      # (parameter, average) addresses -> device table of vlmo_mt_adam_ema (a few at most)
         self.last_ctl = None
 
     # ---- tables ------------------------------------------------------------------------------------------
@@ -179,16 +186,52 @@ class FusedAdam(torch.optim.Optimizer):
         ev.record()
         return tl, partial, ctl
 
+    # ---- weight average ------------------------------------------------------------------------------------
+    @staticmethod
+    def _ema_split(ema, items):
+        """({id(parameter): its average} for the stepping tensors the fused kernel can serve, the other entries of the
+        average as ``ema.pairs()`` lists them)."""
+        pairs = ema.pairs()
+        by_addr = {}
+        for i, (_, e, src) in enumerate(pairs):
+            if (e.is_cuda and e.device == src.device and e.dtype == src.dtype == torch.float32 and e.is_contiguous()
+                    and src.is_contiguous() and e.numel()):
+                by_addr.setdefault((src.device, src.data_ptr(), src.numel()), i)
+        twins, fused = {}, set()
+        for _, p, _ in items:
+            i = by_addr.get((p.device, p.data_ptr(), p.numel()))
+            if i is not None and i not in fused:
+                fused.add(i)
+                twins[id(p)] = pairs[i][1]
+        return twins, [pr for i, pr in enumerate(pairs) if i not in fused]
+
+    def _ema_table(self, items, twins):
+        """Device table parallel to the parameter table of `items`: the address of each tensor's average, or 0."""
+        addr = [twins[id(p)].data_ptr() if id(p) in twins else 0 for _, p, _ in items]
+        sig = tuple((p.data_ptr(), a) for (_, p, _), a in zip(items, addr))
+        tab = self._ema_tabs.get(sig)
+        if tab is None:
+            if len(self._ema_tabs) >= 8:
+                self._ema_tabs.pop(next(iter(self._ema_tabs)))
+            tab = self._ema_tabs[sig] = torch.tensor(addr, dtype=torch.int64).to(items[0][1].device)
+        return tab
+
     # ---- step --------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def step(self, closure=None, clip_grad=None, grad_scale=1.0):
+    def step(self, closure=None, clip_grad=None, grad_scale=1.0, ema=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         items = self._collect()
         if not items:
+            if ema is not None:
+                ema.update(ema.source())
             return loss
+        ema_w = None
+        if ema is not None:
+            ema_w = 1.0 - ema.decay
+            twins, ema_rest = self._ema_split(ema, items)
         groups = {gi for gi, _, _ in items}
         ref = self.param_groups[min(groups)]
         for gi in groups:
@@ -217,7 +260,13 @@ class FusedAdam(torch.optim.Optimizer):
                 else:
                     a.inv_bc1 = a.inv_bc2 = 1.0
                 a.adam_w_mode = self.adam_w_mode
-                hip.mt_adam(tl_b, a, ctl if use_ctl else None)
+                if ema is not None and any(id(p) in twins for _, p, _ in its):
+                    hip.mt_adam_ema(tl_b, a, ctl if use_ctl else None, self._ema_table(its, twins), ema_w)
+                else:
+                    hip.mt_adam(tl_b, a, ctl if use_ctl else None)
+            if ema is not None:
+                ema.update_pairs(ema_rest, ema_w)
+                ema.touched(list(twins.values()))
         # the kernel wrote the parameters and moments behind autograd's back: bump their version counters, which is
         # what invalidates the engine's cached bf16 weight shadows (engine.ShadowCache) and any saved-tensor checks
         touched = [p for _, p, _ in items]
@@ -242,7 +291,11 @@ class NativeScalerWithGradNormCount:
     def __init__(self, reducer=None):
         self.reducer = reducer       # exploremultimodal_amd.dp.GradReducer or None
 
-    def __call__(self, loss, optimizer, clip_grad=None, parameters=None, create_graph=False, update_grad=True):
+    def __call__(self, loss, optimizer, clip_grad=None, parameters=None, create_graph=False, update_grad=True,
+                 model_ema=None):
+        """``model_ema`` (an ``ema.ModelEma``): the weight average moves once per optimizer step -- inside
+        ``FusedAdam.step``, after the step of any other optimizer -- and not at all on a micro-step
+        (``update_grad=False``)."""
         if self.reducer is not None:
             self.reducer.prepare(loss)
         from . import engine
@@ -257,11 +310,13 @@ class NativeScalerWithGradNormCount:
         if not update_grad:
             return None
         if isinstance(optimizer, FusedAdam):
-            norm = optimizer.step(clip_grad=clip_grad if clip_grad is not None else float('inf'))
+            norm = optimizer.step(clip_grad=clip_grad if clip_grad is not None else float('inf'), ema=model_ema)
         else:
             assert parameters is not None
             norm = torch.nn.utils.clip_grad_norm_(parameters, clip_grad if clip_grad is not None else float('inf'))
             optimizer.step()
+            if model_ema is not None:
+                model_ema.update(model_ema.source())
         return norm
 
     def state_dict(self):

@@ -248,6 +248,23 @@ class VLMO(nn.Module):
         for b in self.blocks:
             object.__setattr__(b, '_owner', weakref.ref(self))
 
+    def __deepcopy__(self, memo):
+        """A copy (the weight average of ema.ModelEma) gets caches of its own: the shadow cache is keyed on the identity of
+        THIS model's parameters and would only carry their bf16 copies along, and the blocks' back-reference must point
+        at the copy (a weak reference is copied as it is, so it would keep naming this model)."""
+        import copy
+        import weakref
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k not in ('_shadows', '_plans'):
+                new.__dict__[k] = copy.deepcopy(v, memo)
+        new._shadows = engine.ShadowCache()
+        new._plans = {}
+        for b in new.blocks:
+            object.__setattr__(b, '_owner', weakref.ref(new))
+        return new
+
     # ------------------------------------------------------------------ utils
     def _init_weights(self, m):
         if isinstance(m, (nn.Linear, nn.Embedding)):

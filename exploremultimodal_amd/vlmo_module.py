@@ -6,7 +6,8 @@ the classifier's last Linear becomes ``vqa_last`` and ``isda_head`` keeps the IS
 isda_head.estimator.{count, mean, cov}); training steps with answers run heads.VQAIsdaHeadFn.  ISDA
 needs train.epochs and train.cur_epoch (its ratio) and is refused with R-Drop (kl_alpha > 0), which
 fails upstream.  Each rank keeps its own estimator, as the reference's DDP with broadcast_buffers=False
-does.  The other downstream heads (nlvr2 / irtr / mpp / refcoco), EMA and the negative queue raise
+does.  The other downstream heads (nlvr2 / irtr / mpp / refcoco), the momentum twin (vlmo_ema; the plain
+weight average model_ema is ema.ModelEma) and the negative queue raise
 NotImplementedError (out of scope, off in conf/train/pretrain_mum.yaml and
 conf/train/finetune_vqa.yaml)."""
 import math
@@ -89,7 +90,9 @@ class VlmoModule(nn.Module):
 
         self.transformer_m = None
         if getattr(self.config, 'vlmo_ema', False):
-            raise NotImplementedError('vlmo_ema (momentum twin) is out of scope; config.yaml:136 default is off')
+            raise NotImplementedError('vlmo_ema (the momentum twin transformer_m / itc_head_m and the momentum ITC '
+                                      'branch) is out of scope; config.yaml:136 default is off.  The plain weight '
+                                      'average (model_ema) is exploremultimodal_amd.ema.ModelEma')
         if hasattr(config.train, 'neg_queue') and config.train.neg_queue:
             raise NotImplementedError('neg_queue is out of scope; pretrain_mum.yaml:40 default is off')
         self.q_size = 0

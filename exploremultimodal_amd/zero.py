@@ -44,7 +44,9 @@ class _Part:
 
 class ZeroAdam:
     """``opt = ZeroAdam(reducer, param_groups, betas=..., eps=..., adam_w_mode=True)``;
-    ``norm = opt.step(clip_grad=5.0)`` after ``reducer.finish()``.  ``param_groups`` as produced by
+    ``norm = opt.step(clip_grad=5.0)`` after ``reducer.finish()`` (``ema=`` an ``ema.ModelEma``: its update runs
+    after the parameter all-gather; every rank holds the same parameters then, so the averages agree without any
+    communication, for one more read of the parameters).  ``param_groups`` as produced by
     ``optim.get_parameter_groups`` (dicts with 'params', 'lr', 'weight_decay').  The partition is built at the
     first step (the engine's gradient buckets exist once a backward has run)."""
 
@@ -200,7 +202,7 @@ class ZeroAdam:
 
     # ------------------------------------------------------------------------------------------ step
     @torch.no_grad()
-    def step(self, clip_grad=None):
+    def step(self, clip_grad=None, ema=None):
         red = self.reducer
         if self.parts is None:
             self._build()
@@ -259,6 +261,8 @@ class ZeroAdam:
                 red.all_gather(pt.pflat, pt.pflat[pt.lo:pt.hi])
         # the parameters changed behind autograd's back: invalidate the engine's bf16 weight shadows
         torch.autograd.graph.increment_version([p for pt in self.parts for p, _, _ in pt.entries])
+        if ema is not None:
+            ema.update(ema.source())
         self.last_ctl = ctl
         return ctl[0] if ctl is not None else None
 

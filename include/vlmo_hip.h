@@ -82,7 +82,7 @@ typedef struct VlmoEpilogue {
 const char* vlmo_last_error(void);
 /* Version of the struct layouts and signatures below; raised whenever one of them changes
  * (exploremultimodal_amd/hip.py mirrors it as ABI_VERSION and refuses any other). */
-#define VLMO_ABI_VERSION 7
+#define VLMO_ABI_VERSION 8
 int vlmo_abi_version(void);     /* = VLMO_ABI_VERSION of the header the library was built from */
 
 /* C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue.  tile: -1 = pick by shape, 0 = 128x128x64
@@ -283,6 +283,19 @@ int vlmo_mt_grad_norm(const VlmoTensorList* tl, float inv_scale, float max_norm,
 /* One Adam step on every tensor.  ctl = the 3 floats of vlmo_mt_grad_norm (gradients are multiplied by
  * ctl[1]; the whole step is skipped when ctl[2] != 0, like GradScaler.step) or NULL. */
 int vlmo_mt_adam(const VlmoTensorList* tl, const VlmoAdamArgs* a, const float* ctl, hipStream_t stream);
+/* Weight average (the reference's model_ema, timm ModelEmaV2; conf/config.yaml:140-141), fp32:
+ *   e <- e + w (p - e),  w = 1 - decay in [0, 1],
+ * computed as fmaf(w, p - e, e), and from w = 0.5 on from p's side, fmaf(w - 1, p - e, p), as torch.lerp does.  e == p is an
+ * exact fixed point, w = 0 leaves e and w = 1 copies p bit for bit.
+ * Standalone over a list: tl->p[t] = the average (written in place), tl->g[t] = the tensor it follows; numel and the chunk
+ * tables as for vlmo_mt_adam, the other tables unused. */
+int vlmo_mt_ema(const VlmoTensorList* tl, float w, hipStream_t stream);
+/* vlmo_mt_adam with the average of the NEW parameter value folded into the same pass (8 more bytes of traffic per
+ * element instead of 12 and a launch).  ema = DEVICE table parallel to tl->p with the address of each tensor's average, or 0
+ * for a tensor without one.  Element for element the result of vlmo_mt_adam followed by vlmo_mt_ema; when ctl[2] != 0 the
+ * parameters and moments stay untouched and the averages still move toward the unchanged parameters. */
+int vlmo_mt_adam_ema(const VlmoTensorList* tl, const VlmoAdamArgs* a, const float* ctl, const void* const* ema, float w,
+                     hipStream_t stream);
 
 /* The stream vlmo_stack_bwd's deferred parameter-gradient work runs on (VlmoStackDesc.side_stream).  It has the
  * whole step of slack while the activation-gradient chain on the caller's stream is the critical
