@@ -1,0 +1,233 @@
+"""The image views of a sample from decoded pixels (data/utils/transforms.py: RandomResizedCropAndInterpolationWithTwoPic,
+then the flip, ToTensor and Normalize / map_pixels of data/base_dataset.py, which the reference runs on the CPU with PIL).
+
+One random crop box per image is resampled twice: antialiased bicubic to ``size`` for the patch embedding (``image``) and
+Lanczos to ``second_size`` for the dVAE (``image4dalle``); a second, independent box gives ``image_aug``.  The sources of
+a batch differ in size, so they travel packed in one byte buffer (``pack_images``).  A device buffer goes through
+hip.crop_resample (csrc/augment.hip: two launches per batch); a CPU buffer takes a torch restatement of the same
+definition, which is what the tests compare the kernels with.  No autograd: this is input preparation.
+
+Stated difference from PIL: values stay fp32 between the two passes and at the end and are not clamped to [0, 255]; PIL
+rounds to uint8 after each pass, so its image is this one rounded.
+"""
+import math
+
+import torch
+
+from . import hip
+from .dvae import logit_laplace_eps
+
+BICUBIC, LANCZOS = hip.FILTER_BICUBIC, hip.FILTER_LANCZOS
+_RADIUS = {BICUBIC: 2.0, LANCZOS: 3.0}
+_PAD = 16           # packed buffers are a multiple of this many bytes long (the kernel reads whole aligned dwords)
+
+
+def pack_images(images, pin_memory=False):
+    """[uint8 [H, W, 3] tensors] -> {'pixels': uint8 [nbytes], 'table': ((byte offset, H, W), ...)}: what a collate
+    function returns.  Images are laid end to end without padding between them, so an image or a row may start on any
+    byte.  The table is plain Python: it stays on the host when DataLoaderX uploads the batch.
+    The buffer is pageable unless ``pin_memory=True``: a collate function runs in the DataLoader's worker processes, where
+    a pinned allocation would open the GPU (after a fork it cannot; after a spawn every worker would), and a tensor that
+    comes back from a worker is no longer pinned anyway.  DataLoaderX pins on the consumer side before it uploads; ask for
+    a pinned buffer only in the process that owns the GPU."""
+    table, off = [], 0
+    for i, im in enumerate(images):
+        if not torch.is_tensor(im) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+            raise ValueError(f'pack_images: image {i} must be a uint8 [H, W, 3] tensor, got '
+                             f'{tuple(im.shape) if torch.is_tensor(im) else type(im).__name__}')
+        H, W = int(im.shape[0]), int(im.shape[1])
+        if H < 1 or W < 1:
+            raise ValueError(f'pack_images: image {i} is empty ({H} x {W})')
+        table.append((off, H, W))
+        off += H * W * 3
+    total = max(_PAD, (off + _PAD - 1) // _PAD * _PAD)
+    pixels = torch.zeros(total, dtype=torch.uint8, pin_memory=bool(pin_memory))
+    for (o, H, W), im in zip(table, images):
+        pixels[o:o + H * W * 3] = im.reshape(-1)
+    return {'pixels': pixels, 'table': tuple(table)}
+
+
+def unpack_image(packed, i):
+    """Image i of a packed batch as a uint8 [H, W, 3] view."""
+    o, H, W = _table(packed)[i]
+    return packed['pixels'][o:o + H * W * 3].view(H, W, 3)
+
+
+def _table(packed):
+    t = packed['table']
+    if torch.is_tensor(t):          # a tensor table works too, at the price of a device-to-host read when it was uploaded
+        t = t.tolist()
+    return [(int(o), int(H), int(W)) for o, H, W in t]
+
+
+def sample_crop_params(sizes, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), generator=None):
+    """torchvision's RandomResizedCrop.get_params for every (H, W) of ``sizes`` -> int64 [N, 4] boxes (top, left, h, w).
+    Up to 10 tries of area fraction ~ U(scale) times aspect ratio w / h log-uniform in ``ratio``, the first box that fits
+    wins and is placed uniformly; after 10 misses the largest centred box whose ratio is clamped into ``ratio``.  The same
+    seeded ``generator`` gives the same boxes."""
+    if not (0 < scale[0] <= scale[1]) or not (0 < ratio[0] <= ratio[1]):
+        raise ValueError(f'sample_crop_params: need 0 < min <= max for scale {scale} and ratio {ratio}')
+    lo, hi = math.log(ratio[0]), math.log(ratio[1])
+
+    def uniform(a, b):
+        return torch.empty(1).uniform_(a, b, generator=generator).item()
+
+    def below(n):
+        return int(torch.randint(0, n, (1,), generator=generator).item())
+
+    boxes = []
+    for H, W in sizes:
+        H, W = int(H), int(W)
+        if H < 1 or W < 1:
+            raise ValueError(f'sample_crop_params: empty image {H} x {W}')
+        box = None
+        for _ in range(10):
+            target = H * W * uniform(scale[0], scale[1])
+            aspect = math.exp(uniform(lo, hi))
+            w = int(round(math.sqrt(target * aspect)))
+            h = int(round(math.sqrt(target / aspect)))
+            if 0 < w <= W and 0 < h <= H:
+                box = (below(H - h + 1), below(W - w + 1), h, w)
+                break
+        if box is None:
+            box = fallback_box(H, W, ratio)
+        boxes.append(box)
+    return torch.tensor(boxes, dtype=torch.int64).reshape(-1, 4)
+
+
+def fallback_box(H, W, ratio):
+    """The centred box sample_crop_params falls back to: the whole image if its ratio W / H lies in ``ratio``, else the
+    largest box at the nearest allowed ratio."""
+    r = W / H
+    if r < ratio[0]:
+        w, h = W, min(H, max(1, int(round(W / ratio[0]))))
+    elif r > ratio[1]:
+        h, w = H, min(W, max(1, int(round(H * ratio[1]))))
+    else:
+        h, w = H, W
+    return ((H - h) // 2, (W - w) // 2, h, w)
+
+
+# ---------------------------------------------------------------------------------- the definition, restated in torch
+
+def filter_weight(filt, x):
+    """Bicubic: the Keys kernel with a = -0.5; Lanczos: sinc(x) sinc(x / 3) for |x| < 3.  x: fp64 tensor."""
+    x = x.abs()
+    if filt == BICUBIC:
+        near = (1.5 * x - 2.5) * x * x + 1.0
+        far = ((-0.5 * x + 2.5) * x - 4.0) * x + 2.0
+        return torch.where(x < 1.0, near, torch.where(x < 2.0, far, torch.zeros_like(x)))
+    return torch.where(x < 3.0, torch.sinc(x) * torch.sinc(x / 3.0), torch.zeros_like(x))
+
+
+def resample_matrix(n, S, filt):
+    """(fp32 [S, n], fp32 [S]): row o holds the weights of output o over the n inputs of one axis (zero outside its
+    window), and their sum, by which the pass divides its result.  Weights in fp64, rounded once, as the kernels do."""
+    scale = n / S
+    fs = max(scale, 1.0)
+    support = _RADIUS[filt] * fs
+    center = (torch.arange(S, dtype=torch.float64) + 0.5) * scale
+    k0 = (center - support + 0.5).trunc().clamp(min=0)
+    k1 = (center + support + 0.5).trunc().clamp(max=n)
+    k = torch.arange(n, dtype=torch.float64)
+    inside = (k[None, :] >= k0[:, None]) & (k[None, :] < k1[:, None])
+    w = torch.where(inside, filter_weight(filt, (k[None, :] + 0.5 - center[:, None]) / fs), torch.zeros((), dtype=torch.float64))
+    return w.float(), w.float().sum(1)
+
+
+def _crop_resample_cpu(crop, S, filt, flip, mul, add):
+    """crop uint8 [h, w, 3] -> fp32 [3, S, S]: horizontal pass, vertical pass, flip, value * mul[c] + add[c]."""
+    wh, sh = resample_matrix(crop.shape[1], S, filt)
+    wv, sv = resample_matrix(crop.shape[0], S, filt)
+    t = torch.einsum('ok,ykc->yoc', wh, crop.float()) / sh[None, :, None]        # [h, S, 3]
+    v = torch.einsum('oy,yxc->cox', wv, t) / sv[None, :, None]                   # [3, S, S]
+    if flip:
+        v = v.flip(2)
+    return v * mul[:, None, None] + add[:, None, None]
+
+
+class TwoViewCrop:
+    """``tv = TwoViewCrop(size, second_size, mean, std)``; ``tv(packed, generator=None)`` -> {'image': fp32 [N, 3, size,
+    size] (bicubic, (v / 255 - mean) / std), 'image4dalle': fp32 [N, 3, second_size, second_size] (Lanczos, map_pixels(v /
+    255))} of one random box and flip per image, plus 'image_aug' (bicubic, normalised, ``size``) from a second,
+    independent box and flip with ``aug_view=True``.  ``packed``: pack_images' result, on the host or uploaded.
+    ``tv.apply(packed, boxes, flips, aug_boxes, aug_flips)`` is the deterministic form.
+    Limits (include/vlmo_hip.h: vlmo_crop_resample): 1 <= size <= 1024, crop sides <= 8192, boxes inside their images,
+    at most 65536 views per call."""
+
+    def __init__(self, size, second_size, mean, std, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), hflip=0.5, aug_view=False):
+        for n, s in (('size', size), ('second_size', second_size)):
+            if not isinstance(s, int) or not 1 <= s <= hip.CROP_MAX_SIZE:
+                raise ValueError(f'TwoViewCrop: {n} must be an integer in [1, {hip.CROP_MAX_SIZE}], got {s!r}')
+        mean, std = [float(m) for m in mean], [float(s) for s in std]
+        if len(mean) != 3 or len(std) != 3 or min(std) <= 0:
+            raise ValueError('TwoViewCrop: mean and std must have 3 entries, std positive')
+        if not 0.0 <= hflip <= 1.0:
+            raise ValueError('TwoViewCrop: hflip is a probability')
+        self.size, self.second_size, self.mean, self.std = size, second_size, mean, std
+        self.scale, self.ratio, self.hflip, self.aug_view = scale, ratio, hflip, aug_view
+
+    def _draw(self, sizes, generator):
+        boxes = sample_crop_params(sizes, self.scale, self.ratio, generator)
+        flips = torch.rand(len(sizes), generator=generator) < self.hflip
+        return boxes, flips
+
+    def __call__(self, packed, generator=None):
+        sizes = [(H, W) for _, H, W in _table(packed)]
+        boxes, flips = self._draw(sizes, generator)
+        aug = self._draw(sizes, generator) if self.aug_view else (None, None)
+        return self.apply(packed, boxes, flips, *aug)
+
+    def _jobs(self, table, boxes, flips, S, filt, finish, what):
+        boxes = torch.as_tensor(boxes).reshape(-1, 4).tolist()
+        flips = torch.as_tensor(flips).reshape(-1).tolist()
+        if len(boxes) != len(table) or len(flips) != len(table):
+            raise ValueError(f'TwoViewCrop.apply: {what}: one box and one flip per image expected '
+                             f'({len(table)} images, {len(boxes)} boxes, {len(flips)} flips)')
+        jobs = []
+        for i, ((_, H, W), (top, left, h, w)) in enumerate(zip(table, boxes)):
+            top, left, h, w = int(top), int(left), int(h), int(w)
+            if h < 1 or w < 1 or h > hip.CROP_MAX_SIDE or w > hip.CROP_MAX_SIDE:
+                raise ValueError(f'TwoViewCrop.apply: {what} {i}: crop sides must lie in [1, {hip.CROP_MAX_SIDE}] (h={h}, w={w})')
+            if top < 0 or left < 0 or top + h > H or left + w > W:
+                raise ValueError(f'TwoViewCrop.apply: {what} {i}: box (top {top}, left {left}, h {h}, w {w}) is not inside '
+                                 f'the {H} x {W} image')
+            jobs.append((i, top, left, h, w, bool(flips[i]), S, filt, finish))
+        return jobs
+
+    def apply(self, packed, boxes, flips, aug_boxes=None, aug_flips=None):
+        pixels, table = packed['pixels'], _table(packed)
+        if pixels.dtype != torch.uint8 or pixels.dim() != 1 or not pixels.is_contiguous():
+            raise ValueError('TwoViewCrop.apply: packed["pixels"] must be a contiguous 1-D uint8 buffer (3 channels, HWC)')
+        if not table:
+            raise ValueError('TwoViewCrop.apply: empty batch')
+        for i, (o, H, W) in enumerate(table):
+            if H < 1 or W < 1 or o < 0 or o + H * W * 3 > pixels.numel():
+                raise ValueError(f'TwoViewCrop.apply: image {i} (offset {o}, {H} x {W} x 3) is not inside the packed buffer')
+        if (aug_boxes is None) != (aug_flips is None):
+            raise ValueError('TwoViewCrop.apply: aug_boxes and aug_flips go together')
+        views = [('image', self._jobs(table, boxes, flips, self.size, BICUBIC, hip.FINISH_NORMALIZE, 'box')),
+                 ('image4dalle', self._jobs(table, boxes, flips, self.second_size, LANCZOS, hip.FINISH_MAP_PIXELS, 'box'))]
+        if aug_boxes is not None:
+            views.append(('image_aug', self._jobs(table, aug_boxes, aug_flips, self.size, BICUBIC, hip.FINISH_NORMALIZE,
+                                                  'aug box')))
+        if sum(len(j) for _, j in views) > hip.CROP_MAX_JOBS:
+            raise ValueError(f'TwoViewCrop.apply: more than {hip.CROP_MAX_JOBS} views in one call: split the batch')
+        out = {name: torch.empty(len(jobs), 3, jobs[0][6], jobs[0][6], dtype=torch.float32, device=pixels.device)
+               for name, jobs in views}
+        if pixels.is_cuda:
+            if pixels.numel() % 4 or pixels.data_ptr() % 4:
+                raise ValueError('TwoViewCrop.apply: the device buffer must be 4-byte aligned and a multiple of 4 bytes '
+                                 'long (pack_images pads it)')
+            hip.crop_resample(pixels, table, [job + (out[name][q],) for name, jobs in views for q, job in enumerate(jobs)],
+                              self.mean, self.std, logit_laplace_eps)
+            return out
+        std = torch.tensor(self.std)
+        finish = {hip.FINISH_NORMALIZE: (1.0 / (255.0 * std), -torch.tensor(self.mean) / std),
+                  hip.FINISH_MAP_PIXELS: (torch.full((3,), (1 - 2 * logit_laplace_eps) / 255.0), torch.full((3,), logit_laplace_eps))}
+        for name, jobs in views:
+            for q, (i, top, left, h, w, flip, S, filt, fin) in enumerate(jobs):
+                o, H, W = table[i]
+                crop = pixels[o:o + H * W * 3].view(H, W, 3)[top:top + h, left:left + w]
+                out[name][q] = _crop_resample_cpu(crop, S, filt, flip, *finish[fin])
+        return out

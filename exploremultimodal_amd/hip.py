@@ -74,6 +74,17 @@ class ColJob(ctypes.Structure):
                 ('out', _vp * 4), ('n0', _i32), ('pad_', _i32)]
 
 
+class Image(ctypes.Structure):
+    """Mirror of VlmoImage."""
+    _fields_ = [('offset', _i64), ('H', _i32), ('W', _i32)]
+
+
+class CropJob(ctypes.Structure):
+    """Mirror of VlmoCropJob."""
+    _fields_ = [('image', _i32), ('top', _i32), ('left', _i32), ('h', _i32), ('w', _i32), ('flip', _i32), ('S', _i32),
+                ('filter', _i32), ('finish', _i32), ('pad_', _i32), ('tmp_off', _i64), ('out', _vp)]
+
+
 _SIGS = {
     'vlmo_gemm_nt': [_i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32,
                      ctypes.POINTER(Epilogue), _vp],
@@ -142,10 +153,12 @@ _SIGS = {
     'vlmo_isda_aug_fwd': [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _i64, _vp],
     'vlmo_isda_aug_bwd': [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _i64, _vp],
     'vlmo_sim_topk': [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, ctypes.c_size_t, _vp, _vp, _vp],
+    'vlmo_crop_resample': [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _f32, _vp,
+                           _i64, _vp],
 }
 
 _lib = None
-ABI_VERSION = 8      # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
+ABI_VERSION = 9      # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
 
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is missing."""
@@ -630,6 +643,63 @@ def sim_topk(q, g, k, scale=1.0, splits=0):
     _check(lib().vlmo_sim_topk(_p(q), q.stride(0), _p(g), g.stride(0), Nq, Ng, D, k, float(scale), splits, _p(ws), nbytes,
                                _p(val), _p(idx), _stream()), 'vlmo_sim_topk')
     return val, idx
+
+
+FILTER_BICUBIC, FILTER_LANCZOS = 0, 1
+FINISH_NORMALIZE, FINISH_MAP_PIXELS = 0, 1
+CROP_MAX_SIZE, CROP_MAX_SIDE, CROP_MAX_JOBS = 1024, 8192, 65536
+
+
+_IMAGE_DT = None
+
+
+def _crop_dtypes():
+    """numpy mirrors of VlmoImage / VlmoCropJob (the ctypes classes above give the sizes they must have)."""
+    global _IMAGE_DT
+    if _IMAGE_DT is None:
+        import numpy as np
+        i4, i8 = np.int32, np.int64
+        image = np.dtype([('offset', i8), ('H', i4), ('W', i4)])
+        job = np.dtype([(n, i4) for n in ('image', 'top', 'left', 'h', 'w', 'flip', 'S', 'filter', 'finish', 'pad_')]
+                       + [('tmp_off', i8), ('out', i8)])
+        assert image.itemsize == ctypes.sizeof(Image) and job.itemsize == ctypes.sizeof(CropJob)
+        _IMAGE_DT = (np, image, job)
+    return _IMAGE_DT
+
+
+def crop_resample(pixels, images, jobs, mean, std, pixel_eps):
+    """vlmo_crop_resample: pixels = device uint8 buffer of packed HWC images (4-byte aligned, length a multiple of 4);
+    images = [(offset, H, W)]; jobs = [(image, top, left, h, w, flip, S, filter, finish, out)] with out an fp32 [3, S, S]
+    contiguous device tensor that the job fills.  Two launches for the whole list; the fp32 intermediates live in a cached
+    scratch buffer.  Both tables are built as numpy records in ONE pinned staging buffer, which the entry point checks on
+    the host and one asynchronous copy on the current stream hands to the kernels."""
+    np, image_dt, job_dt = _crop_dtypes()
+    ni, nj = len(images), len(jobs)
+    for q, job in enumerate(jobs):
+        out, S = job[9], job[6]
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != 3 * S * S or out.device != pixels.device:
+            raise ValueError(f'crop_resample: job {q}: out must be a contiguous fp32 [3, {S}, {S}] tensor on the pixels\' device')
+    ibytes = ni * image_dt.itemsize                       # a multiple of 16: the job table behind it stays 8-byte aligned
+    host = torch.empty(max(1, ibytes + nj * job_dt.itemsize), dtype=torch.uint8, pin_memory=True)
+    raw = host.numpy()
+    itab, jtab = raw[:ibytes].view(image_dt), raw[ibytes:ibytes + nj * job_dt.itemsize].view(job_dt)
+    if ni:
+        itab[:] = np.array([tuple(im) for im in images], dtype=image_dt)
+    if nj:
+        sizes = np.array([j[3] * j[6] * 3 for j in jobs], dtype=np.int64)
+        run = np.concatenate([[0], np.cumsum(sizes)])
+        jtab[:] = np.array([(im, top, left, h, w, int(flip), S, filt, fin, 0, 0, out.data_ptr())
+                            for im, top, left, h, w, flip, S, filt, fin, out in jobs], dtype=job_dt)
+        jtab['tmp_off'] = run[:-1]
+        total = int(run[-1])
+    else:
+        total = 0
+    ws = _scratch('crop', pixels.device, total * 4, 1 << 24)
+    dev = host.to(pixels.device, non_blocking=True)
+    m3, s3 = (_f32 * 3)(*mean), (_f32 * 3)(*std)
+    _check(lib().vlmo_crop_resample(_p(pixels), pixels.numel(), host.data_ptr(), dev.data_ptr(), ni,
+                                    host.data_ptr() + ibytes, dev.data_ptr() + ibytes, nj, m3, s3, float(pixel_eps), _p(ws),
+                                    ws.numel() * 4, _stream()), 'vlmo_crop_resample')
 
 
 PROFILE_TAGS = 96

@@ -82,7 +82,7 @@ typedef struct VlmoEpilogue {
 const char* vlmo_last_error(void);
 /* Version of the struct layouts and signatures below; raised whenever one of them changes
  * (exploremultimodal_amd/hip.py mirrors it as ABI_VERSION and refuses any other). */
-#define VLMO_ABI_VERSION 8
+#define VLMO_ABI_VERSION 9
 int vlmo_abi_version(void);     /* = VLMO_ABI_VERSION of the header the library was built from */
 
 /* C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue.  tile: -1 = pick by shape, 0 = 128x128x64
@@ -498,6 +498,46 @@ int vlmo_isda_aug_bwd(const void* G, int ldg, const float* W, int ldw, const int
 int64_t vlmo_sim_topk_ws_bytes(int Nq, int Ng, int K, int splits);
 int vlmo_sim_topk(const float* Q, int ldq, const float* G, int ldg, int Nq, int Ng, int D, int K, float scale, int splits,
                   void* ws, size_t ws_bytes, float* out_val, int32_t* out_idx, hipStream_t stream);
+
+/* ---- input preparation: the two image views of a sample from decoded pixels; csrc/augment.hip ---- */
+
+/* One source image of the packed byte buffer: uint8 [H, W, 3] starting `offset` bytes into it (any alignment). */
+typedef struct {
+    int64_t offset;
+    int32_t H, W;
+} VlmoImage;
+
+enum { VLMO_FILTER_BICUBIC = 0, VLMO_FILTER_LANCZOS = 1 };          /* Keys a = -0.5, radius 2; Lanczos, radius 3 */
+enum { VLMO_FINISH_NORMALIZE = 0, VLMO_FINISH_MAP_PIXELS = 1 };     /* (v / 255 - mean) / std; (1 - 2 eps) v / 255 + eps */
+#define VLMO_CROP_MAX_SIZE 1024     /* output side S */
+#define VLMO_CROP_MAX_SIDE 8192     /* crop box side */
+#define VLMO_CROP_MAX_JOBS 65536    /* jobs per call */
+
+/* One output view: crop box (top, left, h, w) of image `image`, resampled to S x S with `filter`, mirrored when flip = 1,
+ * finished with `finish`, written to out fp32 [3, S, S].  tmp_off: where the job's fp32 intermediate [h, S, 3] starts in
+ * the workspace, in floats: the sum of h * S * 3 over the jobs before it. */
+typedef struct {
+    int32_t image, top, left, h, w;
+    int32_t flip, S, filter, finish, pad_;
+    int64_t tmp_off;
+    float* out;
+} VlmoCropJob;
+
+/* Every job of a batch in two launches, whatever their number (data/utils/transforms.py:8-138 + the flip, ToTensor and
+ * Normalize / map_pixels of data/base_dataset.py, which the reference runs on the CPU with PIL).  Per job: crop first
+ * (pixels outside the box do not exist for the filter), then a separable resampling, horizontal pass then vertical, with
+ * PIL's windows: per axis of input length n, scale = n / S, fs = max(scale, 1), support = R * fs, output o has centre
+ * (o + 0.5) * scale and taps k in [max(0, int(centre - support + 0.5)), min(n, int(centre + support + 0.5))) with weight
+ * f((k + 0.5 - centre) / fs) divided by the sum of the output's weights.  Weights are computed on the device (fp64, rounded
+ * to fp32); values stay fp32 between the passes and at the end, unclamped (PIL rounds to uint8 after each pass).
+ * src: device bytes, 4-byte aligned, src_bytes a multiple of 4 (pad the tail).  images / jobs: HOST tables, checked here;
+ * images_dev / jobs_dev: the same tables in device memory, read by the kernels.  mean, std: 3 host floats each.
+ * pixel_eps: the eps of VLMO_FINISH_MAP_PIXELS.  ws: device workspace of at least 4 * sum(h * S * 3) bytes.
+ * Limits: 3 channels; 1 <= S <= VLMO_CROP_MAX_SIZE; 1 <= h, w <= VLMO_CROP_MAX_SIDE; the box inside its image; 1 <= n_jobs
+ * <= VLMO_CROP_MAX_JOBS.  No atomics, fixed summation order: the same bits from run to run and for any order of the jobs. */
+int vlmo_crop_resample(const uint8_t* src, int64_t src_bytes, const VlmoImage* images, const VlmoImage* images_dev,
+                       int n_images, const VlmoCropJob* jobs, const VlmoCropJob* jobs_dev, int n_jobs, const float* mean,
+                       const float* std, float pixel_eps, float* ws, int64_t ws_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }
