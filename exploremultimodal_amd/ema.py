@@ -19,32 +19,14 @@ import weakref
 
 import torch
 
-from . import hip
-from .optim import CHUNK
+from . import hip, mt
 
 
 def tensor_list(dev, eps):
-    """(VlmoTensorList, the device buffers behind it) of one ``vlmo_mt_ema`` launch over ``eps = [(average, source)]``,
-    contiguous fp32 tensors on ``dev``: p = the averages, g = their sources, cut into chunks of ``optim.CHUNK``."""
-    nt = len(eps)
-    chunk_tensor, chunk_start = [], []
-    for t, (e, _) in enumerate(eps):
-        for off in range(0, e.numel(), CHUNK):
-            chunk_tensor.append(t)
-            chunk_start.append(off)
-    nc = len(chunk_tensor)
-    host_i = torch.empty(3 * nt + nc, dtype=torch.int64)      # [average | source | numel | chunk_start]
-    for t, (e, p) in enumerate(eps):
-        host_i[t], host_i[nt + t], host_i[2 * nt + t] = e.data_ptr(), p.data_ptr(), e.numel()
-    host_i[3 * nt:] = torch.tensor(chunk_start, dtype=torch.int64)
-    dev_i = host_i.to(dev)
-    dev_c = torch.tensor(chunk_tensor, dtype=torch.int32).to(dev)
-    tl = hip.TensorList()
-    base = dev_i.data_ptr()
-    tl.p, tl.g, tl.numel, tl.chunk_start = base, base + 8 * nt, base + 16 * nt, base + 24 * nt
-    tl.chunk_tensor = dev_c.data_ptr()
-    tl.n_chunks, tl.chunk = nc, CHUNK
-    return tl, (dev_i, dev_c)
+    """(VlmoTensorList, the ``mt.Table`` that owns its device buffers) of one ``vlmo_mt_ema`` launch over ``eps = [(average, source)]``,
+    contiguous fp32 tensors on ``dev``: p = the averages, g = their sources, cut into chunks of ``mt.CHUNK``."""
+    tab = mt.Table(dev, [e.data_ptr() for e, _ in eps], [p.data_ptr() for _, p in eps], [e.numel() for e, _ in eps])
+    return tab.tl, tab
 
 
 def _state_slots(module):
@@ -175,12 +157,7 @@ class ModelEma:
         """The launch tables of `eps`.  The addresses are fixed between steps, so they are uploaded once per set of tensors
         (as FusedAdam._tables caches its own)."""
         sig = (dev, tuple((e.data_ptr(), p.data_ptr(), e.numel()) for e, p in eps))
-        tab = self._tabs.get(sig)
-        if tab is None:
-            if len(self._tabs) >= 8:        # the set changes only with which parameters stepped: keep a few
-                self._tabs.pop(next(iter(self._tabs)))
-            tab = self._tabs[sig] = tensor_list(dev, eps)
-        return tab[0]
+        return mt.recent(self._tabs, sig, lambda: tensor_list(dev, eps))[0]
 
     # ---- state -----------------------------------------------------------------------------------------------
     def state_dict(self):

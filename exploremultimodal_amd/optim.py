@@ -22,11 +22,11 @@ import math
 
 import torch
 
-from . import hip
+from . import hip, mt
+from .mt import CHUNK  # noqa: F401  (optim.CHUNK stays importable)
 
 HEAD_NAMES = ('mlm_head', 'itc_head', 'itm_head', 'mim_head', 'vqa_classifier', 'vqa_last', 'nlvr2_classifier',
               'snli_classifier')
-CHUNK = 1 << 16        # elements per workgroup of the multi-tensor kernels
 
 
 def get_parameter_groups(model, base_lr, lr_mult_head, lr_mult_fusion, weight_decay=1e-5, skip_list=(), logger=None):
@@ -105,7 +105,7 @@ class FusedAdam(torch.optim.Optimizer):
         defaults = dict(lr=lr, bias_correction=bias_correction, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self.adam_w_mode = 1 if adam_w_mode else 0
-        self._tabs = {}          # signature -> [device buffers, host staging, TensorList, turn] (a few at most)
+        self._tabs = {}          # signature -> [mt.Table, host staging, turn] (a few at most)
         self._ema_tabs = {}      # (parameter, average) addresses -> device table of vlmo_mt_adam_ema (a few at most)
         self.last_ctl = None
 
@@ -137,54 +137,31 @@ class FusedAdam(torch.optim.Optimizer):
         dev = items[0][1].device
         sig = (dev, tuple((id(p), p.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr()) for _, p, st in items))
         nt = len(items)
-        tab = self._tabs.get(sig)
-        if tab is None:
-            chunk_tensor, chunk_start = [], []
-            for t, (_, p, _) in enumerate(items):
-                for off in range(0, p.numel(), CHUNK):
-                    chunk_tensor.append(t)
-                    chunk_start.append(off)
-            nc = len(chunk_tensor)
-            # device tables: int64 [p | g | m | v | numel | chunk_start], float32 [lr | wd], int32 chunk_tensor
-            const_i = torch.empty(5 * nt + nc, dtype=torch.int64)
-            for t, (_, p, st) in enumerate(items):
-                const_i[t] = p.data_ptr()
-                const_i[2 * nt + t] = st['exp_avg'].data_ptr()
-                const_i[3 * nt + t] = st['exp_avg_sq'].data_ptr()
-                const_i[4 * nt + t] = p.numel()
-            const_i[5 * nt:] = torch.tensor(chunk_start, dtype=torch.int64)
-            dev_i = const_i.to(dev)
-            dev_f = torch.empty(2 * nt, dtype=torch.float32, device=dev)
-            dev_c = torch.tensor(chunk_tensor, dtype=torch.int32).to(dev)
-            partial = torch.empty(max(nc, 1), dtype=torch.float32, device=dev)
-            ctl = torch.zeros(4, dtype=torch.float32, device=dev)
-            tl = hip.TensorList()
-            base = dev_i.data_ptr()
-            tl.p, tl.g, tl.m, tl.v = base, base + 8 * nt, base + 16 * nt, base + 24 * nt
-            tl.numel, tl.chunk_start = base + 32 * nt, base + 40 * nt
-            tl.lr, tl.wd = dev_f.data_ptr(), dev_f.data_ptr() + 4 * nt
-            tl.chunk_tensor = dev_c.data_ptr()
-            tl.n_chunks, tl.chunk = nc, CHUNK
+
+        def make():
+            # the gradient addresses (NULL here), lr and wd are uploaded below, every step
+            table = mt.Table(dev, [p.data_ptr() for _, p, _ in items], [0] * nt, [p.numel() for _, p, _ in items],
+                             m=[st['exp_avg'].data_ptr() for _, _, st in items],
+                             v=[st['exp_avg_sq'].data_ptr() for _, _, st in items])
             # per-step host staging (gradient addresses, lr, wd): pinned, rotated, each guarded by an event so a
             # host running steps ahead of the GPU never overwrites a buffer whose upload has not happened yet
             stage = [(torch.empty(nt, dtype=torch.int64).pin_memory(), torch.empty(2 * nt, dtype=torch.float32).pin_memory(),
                       torch.cuda.Event()) for _ in range(4)]
-            if len(self._tabs) >= 8:        # parameter sets change rarely (frozen / unused parameters): keep a few
-                self._tabs.pop(next(iter(self._tabs)))
-            tab = self._tabs[sig] = [(dev_i, dev_f, dev_c, partial, ctl), stage, tl, 0]
-        (dev_i, dev_f, _, partial, ctl), stage, tl, turn = tab
+            return [table, stage, 0]
+        tab = mt.recent(self._tabs, sig, make)
+        table, stage, turn = tab
         host_g, host_f, ev = stage[turn % len(stage)]
-        tab[3] = turn + 1
+        tab[2] = turn + 1
         ev.synchronize()
         for t, (gi, p, _) in enumerate(items):
             host_g[t] = p.grad.data_ptr()
             g = self.param_groups[gi]
             host_f[t] = g['lr']
             host_f[nt + t] = g['weight_decay']
-        dev_i[nt:2 * nt].copy_(host_g, non_blocking=True)
-        dev_f.copy_(host_f, non_blocking=True)
+        table.g.copy_(host_g, non_blocking=True)
+        table.dev_f.copy_(host_f, non_blocking=True)
         ev.record()
-        return tl, partial, ctl
+        return table.tl, table.partial, table.ctl
 
     # ---- weight average ------------------------------------------------------------------------------------
     @staticmethod
@@ -209,12 +186,7 @@ class FusedAdam(torch.optim.Optimizer):
         """Device table parallel to the parameter table of `items`: the address of each tensor's average, or 0."""
         addr = [twins[id(p)].data_ptr() if id(p) in twins else 0 for _, p, _ in items]
         sig = tuple((p.data_ptr(), a) for (_, p, _), a in zip(items, addr))
-        tab = self._ema_tabs.get(sig)
-        if tab is None:
-            if len(self._ema_tabs) >= 8:
-                self._ema_tabs.pop(next(iter(self._ema_tabs)))
-            tab = self._ema_tabs[sig] = torch.tensor(addr, dtype=torch.int64).to(items[0][1].device)
-        return tab
+        return mt.recent(self._ema_tabs, sig, lambda: torch.tensor(addr, dtype=torch.int64).to(items[0][1].device))
 
     # ---- step --------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -249,17 +221,9 @@ class FusedAdam(torch.optim.Optimizer):
             use_ctl = clip_grad is not None or grad_scale != 1.0
             if use_ctl:      # the global norm covers every parameter of this step, whatever its counter
                 hip.mt_grad_norm(tl, 1.0 / grad_scale, clip_grad if clip_grad is not None else 0.0, partial, ctl)
-            b1, b2 = ref['betas']
             for step0, its in by_step.items():
-                step = step0 + 1
                 tl_b = tl if len(by_step) == 1 else self._tables(its)[0]
-                a = hip.AdamArgs()
-                a.beta1, a.beta2, a.eps = b1, b2, ref['eps']
-                if ref['bias_correction']:
-                    a.inv_bc1, a.inv_bc2 = 1.0 / (1.0 - b1 ** step), 1.0 / (1.0 - b2 ** step)
-                else:
-                    a.inv_bc1 = a.inv_bc2 = 1.0
-                a.adam_w_mode = self.adam_w_mode
+                a = mt.adam_args(ref['betas'], ref['eps'], ref['bias_correction'], step0 + 1, self.adam_w_mode)
                 if ema is not None and any(id(p) in twins for _, p, _ in its):
                     hip.mt_adam_ema(tl_b, a, ctl if use_ctl else None, self._ema_table(its, twins), ema_w)
                 else:

@@ -20,8 +20,7 @@ same factor as ``torch.nn.utils.clip_grad_norm_`` would on the full averaged gra
 import torch
 import torch.distributed as dist
 
-from . import hip
-from .optim import CHUNK
+from . import hip, mt
 
 
 class _Part:
@@ -66,7 +65,7 @@ class ZeroAdam:
         self.adam_w_mode, self.bias_correction = adam_w_mode, bias_correction
         self.step_count = 0
         self.parts = None
-        self._tab = None
+        self._tabs = {}             # addresses of the stepping entries -> mt.Table (a few at most)
         self.last_ctl = None
         self._pending_state = None
         self._pstep = {}            # id(parameter) -> optimizer steps taken (torch.optim.AdamW keeps one per parameter)
@@ -97,7 +96,7 @@ class ZeroAdam:
                 parts.append(_Part(b, ents, red.world, red.rank, dev))
         torch.autograd.graph.increment_version([p for pt in parts for p, _, _ in pt.entries])
         self.parts = parts
-        self._tab = None
+        self._tabs = {}
         if self._pending_state is not None:
             self._apply_state(self._pending_state)
             self._pending_state = None
@@ -151,54 +150,21 @@ class ZeroAdam:
         return ent
 
     def _table(self, ent):
-        """Device tables of the multi-tensor kernels for the entries `ent` (cached by their addresses)."""
-        dev = self.reducer.device
-        sig = tuple(e[:5] for e in ent)
-        if self._tab is None:
-            self._tab = {}
-        tab = self._tab.get(sig)
-        if tab is not None:
-            return tab
-        if len(self._tab) > 8:          # the sets of parameters stepping together change rarely
-            self._tab.clear()
-        nt = len(ent)
-        chunk_tensor, chunk_start = [], []
-        for t, e in enumerate(ent):
-            for o in range(0, e[4], CHUNK):
-                chunk_tensor.append(t)
-                chunk_start.append(o)
-        nc = len(chunk_tensor)
-        host_i = torch.empty(5 * nt + nc, dtype=torch.int64)
-        for t, e in enumerate(ent):
-            host_i[t], host_i[nt + t], host_i[2 * nt + t], host_i[3 * nt + t], host_i[4 * nt + t] = e[:5]
-        if nc:
-            host_i[5 * nt:] = torch.tensor(chunk_start, dtype=torch.int64)
-        tab = {'sig': sig, 'ent': ent, 'nt': nt}
-        tab['dev_i'] = host_i.to(dev)
-        tab['dev_f'] = torch.empty(max(2 * nt, 1), dtype=torch.float32, device=dev)
-        tab['dev_c'] = torch.tensor(chunk_tensor, dtype=torch.int32).to(dev)
-        tab['partial'] = torch.empty(max(nc, 1), dtype=torch.float32, device=dev)
-        tab['ctl'] = torch.zeros(4, dtype=torch.float32, device=dev)
-        if dev.type == 'cuda':
-            tl = hip.TensorList()
-            base = tab['dev_i'].data_ptr()
-            tl.p, tl.g, tl.m, tl.v = base, base + 8 * nt, base + 16 * nt, base + 24 * nt
-            tl.numel, tl.chunk_start = base + 32 * nt, base + 40 * nt
-            tl.lr, tl.wd = tab['dev_f'].data_ptr(), tab['dev_f'].data_ptr() + 4 * nt
-            tl.chunk_tensor = tab['dev_c'].data_ptr()
-            tl.n_chunks, tl.chunk = nc, CHUNK
-            tab['tl'] = tl
-        self._tab[sig] = tab
-        return tab
+        """Device tables of the multi-tensor kernels for the entries `ent` (cached by their addresses); `tab.ent` keeps
+        them: step() reads the group index and the parameter of each entry."""
+        def make():
+            p, g, m, v, numel = ([e[k] for e in ent] for k in range(5))
+            return mt.Table(self.reducer.device, p, g, numel, m=m, v=v, ent=ent)
+        return mt.recent(self._tabs, tuple(e[:5] for e in ent), make)
 
     # ------------------------------------------------------------------------------------------ kernels
     def _local_sqnorm(self, tab):
         """sum of squares of this rank's gradient slices -> 0-dim device tensor."""
-        hip.mt_grad_norm(tab['tl'], 1.0, 0.0, tab['partial'], tab['ctl'])
-        return tab['ctl'][0] * tab['ctl'][0]
+        hip.mt_grad_norm(tab.tl, 1.0, 0.0, tab.partial, tab.ctl)
+        return tab.ctl[0] * tab.ctl[0]
 
     def _apply(self, tab, args, ctl):
-        hip.mt_adam(tab['tl'], args, ctl)
+        hip.mt_adam(tab.tl, args, ctl)
 
     # ------------------------------------------------------------------------------------------ step
     @torch.no_grad()
@@ -220,7 +186,7 @@ class ZeroAdam:
             norm = sq.sqrt()
             bad = ~torch.isfinite(norm)
             coef = torch.clamp(clip_grad / (norm + 1e-6), max=1.0) if clip_grad > 0 else torch.ones_like(norm)
-            ctl = tab['ctl']
+            ctl = tab.ctl
             ctl[0:1] = norm
             ctl[1:2] = torch.where(bad, torch.zeros_like(coef), coef)
             ctl[2:3] = bad.to(torch.float32)
@@ -230,22 +196,14 @@ class ZeroAdam:
         by_step = {}
         for e in ent:
             by_step.setdefault(self._pstep.get(id(e[6]), 0), []).append(e)
-        b1, b2 = self.betas
         for step0, es in sorted(by_step.items()):
             tb = tab if len(by_step) == 1 else self._table(es)
-            n_ = tb['nt']
+            n_ = tb.nt
             if n_:
                 lrwd = torch.tensor([self.param_groups[e[5]]['lr'] for e in es] +
                                     [self.param_groups[e[5]]['weight_decay'] for e in es], dtype=torch.float32)
-                tb['dev_f'][:2 * n_].copy_(lrwd, non_blocking=True)
-            a = hip.AdamArgs()
-            a.beta1, a.beta2, a.eps = b1, b2, self.eps
-            if self.bias_correction:
-                a.inv_bc1, a.inv_bc2 = 1.0 / (1.0 - b1 ** (step0 + 1)), 1.0 / (1.0 - b2 ** (step0 + 1))
-            else:
-                a.inv_bc1 = a.inv_bc2 = 1.0
-            a.adam_w_mode = 1 if self.adam_w_mode else 0
-            self._apply(tb, a, ctl)
+                tb.dev_f[:2 * n_].copy_(lrwd, non_blocking=True)
+            self._apply(tb, mt.adam_args(self.betas, self.eps, self.bias_correction, step0 + 1, self.adam_w_mode), ctl)
         for pid in {id(e[6]) for e in ent}:
             self._pstep[pid] = self._pstep.get(pid, 0) + 1
         # every rank's updated slice -> every rank's full flat parameters (in place: the slice is the rank's

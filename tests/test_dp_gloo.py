@@ -376,7 +376,7 @@ def _zero_worker(rank, world, port, q):
             def _views(self, tab):
                 import ctypes
                 out = []
-                for (pp, gp, mp_, vp, n, gi, _p) in tab['ent']:
+                for (pp, gp, mp_, vp, n, gi, _p) in tab.ent:
                     mk = lambda a: torch.frombuffer((ctypes.c_float * n).from_address(a), dtype=torch.float32)
                     out.append((mk(pp), mk(gp), mk(mp_), mk(vp), gi))
                 return out
