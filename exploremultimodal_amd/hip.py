@@ -79,6 +79,11 @@ class Image(ctypes.Structure):
     _fields_ = [('offset', _i64), ('H', _i32), ('W', _i32)]
 
 
+class AugSlot(ctypes.Structure):
+    """Mirror of VlmoAugSlot."""
+    _fields_ = [('op', _i32), ('pad_', _i32), ('a', ctypes.c_double), ('b', ctypes.c_double)]
+
+
 class CropJob(ctypes.Structure):
     """Mirror of VlmoCropJob."""
     _fields_ = [('image', _i32), ('top', _i32), ('left', _i32), ('h', _i32), ('w', _i32), ('flip', _i32), ('S', _i32),
@@ -155,10 +160,11 @@ _SIGS = {
     'vlmo_sim_topk': [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, ctypes.c_size_t, _vp, _vp, _vp],
     'vlmo_crop_resample': [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _f32, _vp,
                            _i64, _vp],
+    'vlmo_randaug': [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _vp],
 }
 
 _lib = None
-ABI_VERSION = 9      # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
+ABI_VERSION = 10     # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
 
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is missing."""
@@ -183,6 +189,8 @@ def lib():
         L.vlmo_gemm_tn_ws_bytes.argtypes = [_i32, _i32, _i32]
         L.vlmo_sim_topk_ws_bytes.restype = ctypes.c_int64
         L.vlmo_sim_topk_ws_bytes.argtypes = [_i32, _i32, _i32, _i32]
+        L.vlmo_randaug_ws_bytes.restype = ctypes.c_int64
+        L.vlmo_randaug_ws_bytes.argtypes = [_i32]
         for name, sig in _SIGS.items():
             fn = getattr(L, name)
             fn.argtypes = sig
@@ -193,7 +201,7 @@ def lib():
 
 def exported_symbols():
     return ['vlmo_last_error', 'vlmo_abi_version', 'vlmo_reduce_ws_bytes', 'vlmo_gemm_tn_ws_bytes',
-            'vlmo_isda_ws_bytes', 'vlmo_sim_topk_ws_bytes'] + list(_SIGS)
+            'vlmo_isda_ws_bytes', 'vlmo_sim_topk_ws_bytes', 'vlmo_randaug_ws_bytes'] + list(_SIGS)
 
 
 def _check(rc, name):
@@ -662,8 +670,10 @@ def _crop_dtypes():
         image = np.dtype([('offset', i8), ('H', i4), ('W', i4)])
         job = np.dtype([(n, i4) for n in ('image', 'top', 'left', 'h', 'w', 'flip', 'S', 'filter', 'finish', 'pad_')]
                        + [('tmp_off', i8), ('out', i8)])
+        slot = np.dtype([('op', i4), ('pad_', i4), ('a', np.float64), ('b', np.float64)])
         assert image.itemsize == ctypes.sizeof(Image) and job.itemsize == ctypes.sizeof(CropJob)
-        _IMAGE_DT = (np, image, job)
+        assert slot.itemsize == ctypes.sizeof(AugSlot)
+        _IMAGE_DT = (np, image, job, slot)
     return _IMAGE_DT
 
 
@@ -673,7 +683,7 @@ def crop_resample(pixels, images, jobs, mean, std, pixel_eps):
     contiguous device tensor that the job fills.  Two launches for the whole list; the fp32 intermediates live in a cached
     scratch buffer.  Both tables are built as numpy records in ONE pinned staging buffer, which the entry point checks on
     the host and one asynchronous copy on the current stream hands to the kernels."""
-    np, image_dt, job_dt = _crop_dtypes()
+    np, image_dt, job_dt, _ = _crop_dtypes()
     ni, nj = len(images), len(jobs)
     for q, job in enumerate(jobs):
         out, S = job[9], job[6]
@@ -700,6 +710,50 @@ def crop_resample(pixels, images, jobs, mean, std, pixel_eps):
     _check(lib().vlmo_crop_resample(_p(pixels), pixels.numel(), host.data_ptr(), dev.data_ptr(), ni,
                                     host.data_ptr() + ibytes, dev.data_ptr() + ibytes, nj, m3, s3, float(pixel_eps), _p(ws),
                                     ws.numel() * 4, _stream()), 'vlmo_crop_resample')
+
+
+(AUG_SKIP, AUG_IDENTITY, AUG_AUTOCONTRAST, AUG_EQUALIZE, AUG_BRIGHTNESS, AUG_SHARPNESS, AUG_SHEAR_X, AUG_SHEAR_Y,
+ AUG_TRANSLATE_X, AUG_TRANSLATE_Y, AUG_ROTATE, AUG_SOLARIZE, AUG_POSTERIZE, AUG_CONTRAST) = range(-1, 13)
+AUG_MAX_SLOTS, AUG_MAX_IMAGES, AUG_MAX_SHIFT = 4, 65536, 1000000
+
+
+def randaug(pixels, images, ops, a, b, fill=128, out=None, scratch=None, ws=None):
+    """vlmo_randaug: pixels = device uint8 buffer of packed HWC images (4-byte aligned, length a multiple of 4); images =
+    [(offset, H, W)]; ops int [N, n], a and b float64 [N, n] (array-likes on the host): operation AUG_* and its arguments
+    for slot s of image i.  Returns a new buffer of the same length with every image's slots applied in order; bytes
+    outside the images are not written.  out, scratch (for n > 1) and ws default to fresh / cached buffers.  Both tables
+    go through ONE pinned staging buffer, checked on the host by the entry point and copied once on the current stream;
+    nothing is read back."""
+    np, image_dt, _, slot_dt = _crop_dtypes()
+    ops = np.asarray(ops, dtype=np.int64)
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    ni = len(images)
+    if ops.ndim != 2 or ops.shape[0] != ni or a.shape != ops.shape or b.shape != ops.shape:
+        raise ValueError(f'randaug: ops, a and b must be [{ni}, n] (got {ops.shape}, {a.shape}, {b.shape})')
+    n = ops.shape[1]
+    if out is None:
+        out = torch.empty_like(pixels)
+    if scratch is None and n > 1:
+        scratch = torch.empty_like(pixels)
+    for t, name in ((pixels, 'pixels'), (out, 'out'), (scratch, 'scratch')):
+        if t is not None and (t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous() or t.device != pixels.device
+                              or t.numel() != pixels.numel()):
+            raise ValueError(f'randaug: {name} must be a contiguous 1-D uint8 buffer of pixels\' length and device')
+    ibytes = ni * image_dt.itemsize                       # a multiple of 16: the slot table behind it stays 8-byte aligned
+    host = torch.empty(max(1, ibytes + ni * n * slot_dt.itemsize), dtype=torch.uint8, pin_memory=True)
+    raw = host.numpy()
+    if ni:
+        raw[:ibytes].view(image_dt)[:] = np.array([tuple(im) for im in images], dtype=image_dt)
+    stab = raw[ibytes:ibytes + ni * n * slot_dt.itemsize].view(slot_dt)
+    stab['op'], stab['pad_'], stab['a'], stab['b'] = ops.reshape(-1), 0, a.reshape(-1), b.reshape(-1)
+    need = lib().vlmo_randaug_ws_bytes(ni)
+    if ws is None:
+        ws = _scratch('randaug', pixels.device, need, 1 << 20)
+    dev = host.to(pixels.device, non_blocking=True)
+    _check(lib().vlmo_randaug(_p(pixels), _p(out), _p(scratch), pixels.numel(), host.data_ptr(), dev.data_ptr(), ni,
+                              host.data_ptr() + ibytes, dev.data_ptr() + ibytes, n, int(fill), _p(ws),
+                              ws.numel() * ws.element_size(), _stream()), 'vlmo_randaug')
+    return out
 
 
 PROFILE_TAGS = 96

@@ -82,7 +82,7 @@ typedef struct VlmoEpilogue {
 const char* vlmo_last_error(void);
 /* Version of the struct layouts and signatures below; raised whenever one of them changes
  * (exploremultimodal_amd/hip.py mirrors it as ABI_VERSION and refuses any other). */
-#define VLMO_ABI_VERSION 9
+#define VLMO_ABI_VERSION 10
 int vlmo_abi_version(void);     /* = VLMO_ABI_VERSION of the header the library was built from */
 
 /* C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue.  tile: -1 = pick by shape, 0 = 128x128x64
@@ -538,6 +538,53 @@ typedef struct {
 int vlmo_crop_resample(const uint8_t* src, int64_t src_bytes, const VlmoImage* images, const VlmoImage* images_dev,
                        int n_images, const VlmoCropJob* jobs, const VlmoCropJob* jobs_dev, int n_jobs, const float* mean,
                        const float* std, float pixel_eps, float* ws, int64_t ws_bytes, hipStream_t stream);
+
+/* ---- RandAugment on the packed sources, in front of the crop (data/utils/randaugment.py); csrc/randaug.hip ---- */
+
+enum {
+    VLMO_AUG_SKIP = -1,         /* the slot was not kept: a copy */
+    VLMO_AUG_IDENTITY = 0,
+    VLMO_AUG_AUTOCONTRAST = 1,  /* table ops: 1, 2, 3 and 10 .. 12 */
+    VLMO_AUG_EQUALIZE = 2,
+    VLMO_AUG_BRIGHTNESS = 3,    /* a = factor */
+    VLMO_AUG_SHARPNESS = 4,     /* a = factor */
+    VLMO_AUG_SHEAR_X = 5,       /* a = shear factor */
+    VLMO_AUG_SHEAR_Y = 6,
+    VLMO_AUG_TRANSLATE_X = 7,   /* a = offset in pixels */
+    VLMO_AUG_TRANSLATE_Y = 8,
+    VLMO_AUG_ROTATE = 9,        /* a = cos, b = sin of the counter-clockwise angle */
+    VLMO_AUG_SOLARIZE = 10,     /* a = threshold */
+    VLMO_AUG_POSTERIZE = 11,    /* a = bits kept, an integer in [0, 8] */
+    VLMO_AUG_CONTRAST = 12      /* a = factor */
+};
+#define VLMO_AUG_MAX_SLOTS 4        /* operations per image */
+#define VLMO_AUG_MAX_IMAGES 65536   /* images per call */
+#define VLMO_AUG_MAX_SHIFT 1000000  /* |shear factor|, |translate offset| */
+
+/* One operation of one image; unused arguments are 0. */
+typedef struct {
+    int32_t op, pad_;
+    double a, b;
+} VlmoAugSlot;
+
+/* Bytes of the workspace of vlmo_randaug for n_images: 32-bit histograms and byte tables, [n_images][3][256] each. */
+int64_t vlmo_randaug_ws_bytes(int n_images);
+/* Applies slots[i * n_slots + s], s = 0 .. n_slots - 1 in order, to image i of the packed buffer src; every operation keeps
+ * H x W, so the result has src's layout.  The result is in `out` after the call; `scratch` (NULL allowed for n_slots = 1)
+ * takes the intermediate batches, because a warp and the 3 x 3 filter cannot run in place; src is only read.  The three
+ * buffers are nbytes long each, 4-byte aligned, nbytes a multiple of 4, and do not overlap; only the bytes of the images
+ * are written.  DESIGN.md 4i defines every operation: table look-ups (tables built on the device from 32-bit integer
+ * histograms; fp64, Brightness fp32, no fused multiply-add), PIL's Sharpness (borders copied, result clamped), affine warps
+ * with fp64 bilinear sampling where a tap outside the image reads `fill`.
+ * images / slots: HOST tables, checked here; images_dev / slots_dev: the same tables in device memory.  ws: device
+ * workspace, 16-byte aligned, at least vlmo_randaug_ws_bytes(n_images) bytes.
+ * Launches per call depend on n_slots alone (at most a memset and three kernels per slot); no device-to-host read.
+ * Limits: 3 channels; 1 <= H, W <= VLMO_CROP_MAX_SIDE; images do not overlap; 1 <= n_images <= VLMO_AUG_MAX_IMAGES;
+ * 1 <= n_slots <= VLMO_AUG_MAX_SLOTS; 0 <= fill <= 255; arguments finite.  Integer histogram sums and no arithmetic that
+ * depends on the position of an image in the table: the same bits from run to run and for any order of the images. */
+int vlmo_randaug(const uint8_t* src, uint8_t* out, uint8_t* scratch, int64_t nbytes, const VlmoImage* images,
+                 const VlmoImage* images_dev, int n_images, const VlmoAugSlot* slots, const VlmoAugSlot* slots_dev,
+                 int n_slots, int fill, void* ws, int64_t ws_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }
