@@ -64,6 +64,23 @@ def _table(packed):
     return [(int(o), int(H), int(W)) for o, H, W in t]
 
 
+def _checked_pack(packed, who):
+    """(pixels, table) of a packed batch, after the refusals that every consumer makes in the name ``who``: a contiguous 1-D
+    uint8 buffer, at least one image, every image inside the buffer, a device buffer as the kernels need it."""
+    pixels, table = packed['pixels'], _table(packed)
+    if pixels.dtype != torch.uint8 or pixels.dim() != 1 or not pixels.is_contiguous():
+        raise ValueError(f'{who}: packed["pixels"] must be a contiguous 1-D uint8 buffer (3 channels, HWC)')
+    if not table:
+        raise ValueError(f'{who}: empty batch')
+    for i, (o, H, W) in enumerate(table):
+        if H < 1 or W < 1 or o < 0 or o + H * W * 3 > pixels.numel():
+            raise ValueError(f'{who}: image {i} (offset {o}, {H} x {W} x 3) is not inside the packed buffer')
+    if pixels.is_cuda and (pixels.numel() % 4 or pixels.data_ptr() % 4):
+        raise ValueError(f'{who}: the device buffer must be 4-byte aligned and a multiple of 4 bytes long (pack_images '
+                         'pads it)')
+    return pixels, table
+
+
 def sample_crop_params(sizes, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), generator=None):
     """torchvision's RandomResizedCrop.get_params for every (H, W) of ``sizes`` -> int64 [N, 4] boxes (top, left, h, w).
     Up to 10 tries of area fraction ~ U(scale) times aspect ratio w / h log-uniform in ``ratio``, the first box that fits
@@ -200,14 +217,7 @@ class TwoViewCrop:
         return jobs
 
     def apply(self, packed, boxes, flips, aug_boxes=None, aug_flips=None):
-        pixels, table = packed['pixels'], _table(packed)
-        if pixels.dtype != torch.uint8 or pixels.dim() != 1 or not pixels.is_contiguous():
-            raise ValueError('TwoViewCrop.apply: packed["pixels"] must be a contiguous 1-D uint8 buffer (3 channels, HWC)')
-        if not table:
-            raise ValueError('TwoViewCrop.apply: empty batch')
-        for i, (o, H, W) in enumerate(table):
-            if H < 1 or W < 1 or o < 0 or o + H * W * 3 > pixels.numel():
-                raise ValueError(f'TwoViewCrop.apply: image {i} (offset {o}, {H} x {W} x 3) is not inside the packed buffer')
+        pixels, table = _checked_pack(packed, 'TwoViewCrop.apply')
         if (aug_boxes is None) != (aug_flips is None):
             raise ValueError('TwoViewCrop.apply: aug_boxes and aug_flips go together')
         views = [('image', self._jobs(table, boxes, flips, self.size, BICUBIC, hip.FINISH_NORMALIZE, 'box')),
@@ -220,9 +230,6 @@ class TwoViewCrop:
         out = {name: torch.empty(len(jobs), 3, jobs[0][6], jobs[0][6], dtype=torch.float32, device=pixels.device)
                for name, jobs in views}
         if pixels.is_cuda:
-            if pixels.numel() % 4 or pixels.data_ptr() % 4:
-                raise ValueError('TwoViewCrop.apply: the device buffer must be 4-byte aligned and a multiple of 4 bytes '
-                                 'long (pack_images pads it)')
             hip.crop_resample(pixels, table, [job + (out[name][q],) for name, jobs in views for q, job in enumerate(jobs)],
                               self.mean, self.std, logit_laplace_eps)
             return out
@@ -454,16 +461,10 @@ class RandAugment:
         return ops_l, args_l
 
     def apply(self, packed, plan):
-        pixels, table = packed['pixels'], _table(packed)
-        if pixels.dtype != torch.uint8 or pixels.dim() != 1 or not pixels.is_contiguous():
-            raise ValueError('RandAugment.apply: packed["pixels"] must be a contiguous 1-D uint8 buffer (3 channels, HWC)')
-        if not table:
-            raise ValueError('RandAugment.apply: empty batch')
+        pixels, table = _checked_pack(packed, 'RandAugment.apply')
         if len(table) > hip.AUG_MAX_IMAGES:
             raise ValueError(f'RandAugment.apply: more than {hip.AUG_MAX_IMAGES} images in one call: split the batch')
-        for i, (o, H, W) in enumerate(table):
-            if H < 1 or W < 1 or o < 0 or o + H * W * 3 > pixels.numel():
-                raise ValueError(f'RandAugment.apply: image {i} (offset {o}, {H} x {W} x 3) is not inside the packed buffer')
+        for i, (_, H, W) in enumerate(table):
             if H > hip.CROP_MAX_SIDE or W > hip.CROP_MAX_SIDE:
                 raise ValueError(f'RandAugment.apply: image {i}: sides must be <= {hip.CROP_MAX_SIDE} ({H} x {W})')
         spans = sorted((o, o + H * W * 3) for o, H, W in table)
@@ -472,9 +473,6 @@ class RandAugment:
         ops, args = self._check_plan(plan, table)
         covered = spans[0][0] == 0 and all(a[1] == b[0] for a, b in zip(spans, spans[1:]))
         if pixels.is_cuda:
-            if pixels.numel() % 4 or pixels.data_ptr() % 4:
-                raise ValueError('RandAugment.apply: the device buffer must be 4-byte aligned and a multiple of 4 bytes '
-                                 'long (pack_images pads it)')
             # the entry point writes the images' bytes only: the padding behind them (and gaps, if any) is zeroed here
             out = torch.empty_like(pixels)
             (out[spans[-1][1]:] if covered else out).zero_()

@@ -3,10 +3,9 @@
 // uint8 HWC source, resample it to S x S with PIL's antialiased bicubic or Lanczos windows, flip, normalise.  Entry point
 // vlmo_crop_resample, two launches for all jobs of a batch (DESIGN.md 4h has the specification):
 //   crop_h_kernel   horizontal pass: a workgroup owns 32 output columns x 32 crop rows of one job.  The source columns
-//                   its windows cover are walked in chunks of 128: the chunk's bytes go to LDS as whole aligned dwords (a
-//                   row or an image may start on any byte; the buffer itself is 4-byte aligned and padded, so the dword
-//                   that holds a row's first or last byte is always inside it), the chunk's weights are computed once per
-//                   output column into LDS, and a thread (one output column, four rows) sums its own taps only.
+//                   its windows cover are walked in chunks of 128: the chunk's bytes go to LDS as whole aligned dwords
+//                   (packed_image.h has the rule that allows it), the chunk's weights are computed once per output
+//                   column into LDS, and a thread (one output column, four rows) sums its own taps only.
 //                   Writes the fp32 intermediate [h, S, 3] of the job.
 //   crop_v_kernel   vertical pass: a workgroup owns 64 output columns x 16 output rows (4 per wave); the weights of the 16
 //                   rows are computed once into LDS (chunks of 128 taps), a lane reads the three channels of its column
@@ -15,15 +14,14 @@
 // 5e-4 pixels) and rounded once to fp32; the sums run in fp32 in ascending tap order, and a pixel's sum is divided by the
 // sum of its weights at the end.  Nothing is accumulated with atomics and no thread's arithmetic depends on the job's
 // position in the table: the same bits from run to run and for every job order.
-#include "common.h"
-#include "vlmo_hip.h"
+#include "packed_image.h"
 
 namespace {
 
 constexpr int HX = 32;         // output columns per workgroup, horizontal pass
 constexpr int HY = 32;         // crop rows per workgroup (4 per thread)
 constexpr int HC = 128;        // source columns per chunk
-constexpr int HPITCH = HC * 3 + 8;     // bytes of a staged row: 384 + up to 3 leading bytes of its first dword, dword pitch
+constexpr int HPITCH = packed::row_pitch(HC * 3);       // bytes of a staged row
 constexpr int WPITCH = HC + 1;         // floats per weight row: rows on different banks
 constexpr int VX = 64, VY = 16, VC = 128;
 
@@ -104,16 +102,9 @@ __global__ __launch_bounds__(256) void crop_h_kernel(const uint8_t* __restrict__
     for (int cc = c_lo; cc < c_hi; cc += HC) {
         const int nc = min(HC, c_hi - cc);
         fill_weights<HC>(s_w, WPITCH, ax, x0, nx, cc, s_k0, s_k1);
-        // rows y0 .. y0 + ny - 1, source columns cc .. cc + nc - 1, as the aligned dwords that hold them
-        const int ndw = (nc * 3 + 3 + 3) / 4;       // enough for any start phase; never past the padded buffer (see entry)
-        for (int i = tid; i < ny * ndw; i += 256) {
-            const int r = i / ndw, d = i - r * ndw;
-            const size_t first = origin + (size_t)r * row_bytes + (size_t)cc * 3;
-            const size_t a0 = first & ~(size_t)3;
-            const size_t last = first + (size_t)nc * 3;                 // one past the row's last byte of this chunk
-            if (a0 + 4 * (size_t)d < last)
-                *(uint32_t*)(s_src + r * HPITCH + 4 * d) = *(const uint32_t*)(src + a0 + 4 * (size_t)d);
-        }
+        // rows y0 .. y0 + ny - 1, source columns cc .. cc + nc - 1
+        const size_t first0 = origin + (size_t)cc * 3;
+        packed::stage_rows(s_src, HPITCH, src, first0, row_bytes, ny, nc * 3);
         __syncthreads();
         if (xl < nx) {
             const int ka = max(k0, cc), kb = min(k1, cc + nc);
@@ -121,8 +112,7 @@ __global__ __launch_bounds__(256) void crop_h_kernel(const uint8_t* __restrict__
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int r = min(rl + 8 * i, ny - 1);                  // rows past the tile repeat its last row, unused
-                const size_t first = origin + (size_t)r * row_bytes + (size_t)cc * 3;
-                p[i] = s_src + r * HPITCH + (int)(first & 3);
+                p[i] = packed::staged_row(s_src, r, HPITCH, first0 + (size_t)r * row_bytes);
             }
             for (int k = ka; k < kb; ++k) {
                 const float wv = s_w[xl * WPITCH + (k - cc)];
@@ -222,20 +212,12 @@ extern "C" int vlmo_crop_resample(const uint8_t* src, int64_t src_bytes, const V
                                   const float* mean, const float* std, float pixel_eps, float* ws, int64_t ws_bytes,
                                   hipStream_t stream) {
     VLMO_CHECK_ARG(src && images && images_dev && jobs && jobs_dev && mean && std && ws, "vlmo_crop_resample: null pointer");
-    VLMO_CHECK_ARG((uintptr_t)src % 4 == 0 && src_bytes > 0 && src_bytes % 4 == 0,
-                   "vlmo_crop_resample: the packed buffer must be 4-byte aligned and a multiple of 4 bytes long (%lld bytes)",
-                   (long long)src_bytes);
+    // the crop limits the sides of its boxes, not of the images
+    if (packed::check_packed("vlmo_crop_resample", "packed buffer", (uintptr_t)src, src_bytes, images, n_images, 0)) return -1;
     VLMO_CHECK_ARG(n_images >= 1, "vlmo_crop_resample: no images");
     VLMO_CHECK_ARG(n_jobs >= 1 && n_jobs <= VLMO_CROP_MAX_JOBS, "vlmo_crop_resample: need 1 <= jobs <= %d per call (got %d)",
                    VLMO_CROP_MAX_JOBS, n_jobs);
     VLMO_CHECK_ARG(pixel_eps >= 0.f && pixel_eps < 0.5f, "vlmo_crop_resample: pixel_eps %g outside [0, 0.5)", (double)pixel_eps);
-    for (int i = 0; i < n_images; ++i) {
-        const VlmoImage& I = images[i];
-        VLMO_CHECK_ARG(I.H >= 1 && I.W >= 1 && I.offset >= 0 && I.offset <= src_bytes &&
-                           (int64_t)I.H * I.W * 3 <= src_bytes - I.offset,
-                       "vlmo_crop_resample: image %d (offset %lld, %d x %d x 3) is not inside the %lld-byte buffer", i,
-                       (long long)I.offset, I.H, I.W, (long long)src_bytes);
-    }
     int64_t run = 0;
     int max_s = 0, max_h = 0;
     for (int j = 0; j < n_jobs; ++j) {

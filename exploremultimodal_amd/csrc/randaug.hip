@@ -10,8 +10,7 @@
 //   apply_kernel    one launch over all images; a workgroup reads its image's op and does a table look-up, a warp or a copy
 //                   over 8 KB of the image taken as aligned dwords (a dword that lies wholly in the image is stored whole,
 //                   the up to three bytes at either end one by one), or a 64 x 32 sharpen tile staged in LDS with its halo.
-// A packed image or row starts on any byte; the buffers are 4-byte aligned and a multiple of 4 bytes long, so the aligned
-// dword that holds any byte of an image is inside the buffer.
+// packed_image.h has the rule that lets a kernel take an image or a row that starts on any byte as aligned dwords.
 // Arithmetic: tables in fp64 (Brightness in fp32), the sharpen blend in fp32, warp coordinates, weights and sums in fp64,
 // every multiply and add rounded on its own: the Makefile builds this file with -ffp-contract=off (FLAGS_randaug), because
 // a fused multiply-add decides differently which side of an integer a value lands on.  A pragma here would not do: with
@@ -21,15 +20,14 @@
 #include <cmath>
 #include <vector>
 
-#include "common.h"
-#include "vlmo_hip.h"
+#include "packed_image.h"
 
 namespace {
 
 constexpr int HIST_BYTES = 32768;      // bytes of an image per hist_kernel workgroup
 constexpr int LIN_BYTES = 8192;        // bytes of an image per apply_kernel workgroup (table, warp, copy)
 constexpr int TW = 64, TH = 32;        // sharpen tile, pixels
-constexpr int SPITCH = (TW + 2) * 3 + 10;      // staged row: 198 bytes + up to 3 of the first dword's phase, dword pitch
+constexpr int SPITCH = packed::row_pitch((TW + 2) * 3);        // bytes of a staged row: the tile and its halo
 
 __host__ __device__ inline bool needs_stats(int op) {
     return op == VLMO_AUG_AUTOCONTRAST || op == VLMO_AUG_EQUALIZE || op == VLMO_AUG_CONTRAST;
@@ -54,9 +52,8 @@ __global__ __launch_bounds__(256) void hist_kernel(const uint8_t* __restrict__ s
     __shared__ uint32_t s_h[4][768];
     const int img = blockIdx.x;
     if (!needs_stats(slots[(size_t)img * n_slots + slot].op)) return;
-    const VlmoImage I = images[img];
-    const size_t begin = (size_t)I.offset, end = begin + (size_t)I.H * I.W * 3;
-    const size_t a0 = (begin & ~(size_t)3) + (size_t)blockIdx.y * HIST_BYTES;
+    const packed::Span sp(images[img]);
+    const size_t begin = sp.begin, end = sp.end, a0 = sp.slice(blockIdx.y, HIST_BYTES);
     if (a0 >= end) return;
     const int tid = threadIdx.x, wave = tid >> 6;
     for (int i = tid; i < 4 * 768; i += 256) (&s_h[0][0])[i] = 0;
@@ -67,8 +64,7 @@ __global__ __launch_bounds__(256) void hist_kernel(const uint8_t* __restrict__ s
         const size_t a = a0 + (size_t)i * 1024 + (size_t)tid * 4;
         if (a < end) {                              // a + 3 < buffer size: the buffer is a multiple of 4 bytes long
             const uint32_t v = *(const uint32_t*)(src + a);
-            // channel of byte a + j: (a + j - begin) mod 3; a + 3 >= begin here (a >= begin & ~3)
-            uint32_t c = (uint32_t)((a + 3 - begin) % 3);       // channel of byte a + 3 when inside; walk backwards
+            uint32_t c = sp.channel(a);                 // also the channel of byte a + 3; walk backwards from there
 #pragma unroll
             for (int j = 3; j >= 0; --j) {
                 if (a + j >= begin && a + j < end) atomicAdd(&h[c * 256 + ((v >> (8 * j)) & 0xFF)], 1u);
@@ -248,22 +244,6 @@ struct Taps {
     }
 };
 
-// dword d (counted from the aligned dword that holds byte `first`) of the bytes [first, first + n) of dst, taken from the LDS
-// bytes s[0 .. n): stored whole where all four bytes are ours, else byte by byte
-__device__ __forceinline__ void store_row_dword(uint8_t* dst, size_t first, int n, const uint8_t* s, int d) {
-    const size_t a0 = first & ~(size_t)3;
-    const int b = 4 * d - (int)(first - a0);         // index in s of the dword's first byte
-    if (b >= n) return;
-    if (b >= 0 && b + 4 <= n) {
-        *(uint32_t*)(dst + a0 + 4 * (size_t)d) = (uint32_t)s[b] | ((uint32_t)s[b + 1] << 8) | ((uint32_t)s[b + 2] << 16) |
-                                                  ((uint32_t)s[b + 3] << 24);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (b + j >= 0 && b + j < n) dst[a0 + 4 * (size_t)d + j] = s[b + j];
-    }
-}
-
 __global__ __launch_bounds__(256) void apply_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                     const VlmoImage* __restrict__ images, const VlmoAugSlot* __restrict__ slots,
                                                     int n_slots, int slot, const uint8_t* __restrict__ tables, int fill) {
@@ -273,7 +253,8 @@ __global__ __launch_bounds__(256) void apply_kernel(const uint8_t* __restrict__ 
     const VlmoAugSlot S = slots[(size_t)img * n_slots + slot];
     const VlmoImage I = images[img];
     const int H = I.H, W = I.W;
-    const size_t begin = (size_t)I.offset, end = begin + (size_t)H * W * 3;
+    const packed::Span sp(I);
+    const size_t begin = sp.begin, end = sp.end;
 
     if (is_sharpen(S, H, W)) {
         const int tiles_x = (W + TW - 1) / TW;
@@ -283,14 +264,8 @@ __global__ __launch_bounds__(256) void apply_kernel(const uint8_t* __restrict__ 
         const int tw = min(TW, W - x0), th = min(TH, H - y0);
         // staged window: columns cl .. cr, rows rt .. rb (inclusive), clipped to the image
         const int cl = max(x0 - 1, 0), cr = min(x0 + tw, W - 1), rt = max(y0 - 1, 0), rb = min(y0 + th, H - 1);
-        const int nb = (cr - cl + 1) * 3, ndw = (nb + 3 + 3) / 4;
-        for (int i = tid; i < (rb - rt + 1) * ndw; i += 256) {
-            const int r = i / ndw, d = i - r * ndw;
-            const size_t first = begin + ((size_t)(rt + r) * W + cl) * 3;
-            const size_t a0 = first & ~(size_t)3;
-            if (a0 + 4 * (size_t)d < first + nb)
-                *(uint32_t*)(s_in + r * SPITCH + 4 * d) = *(const uint32_t*)(src + a0 + 4 * (size_t)d);
-        }
+        const size_t row_bytes = (size_t)W * 3, first0 = begin + (size_t)rt * row_bytes + (size_t)cl * 3;
+        packed::stage_rows(s_in, SPITCH, src, first0, row_bytes, rb - rt + 1, (cr - cl + 1) * 3);
         __syncthreads();
         const float f = (float)S.a;
         for (int i = tid; i < th * TW; i += 256) {
@@ -298,17 +273,16 @@ __global__ __launch_bounds__(256) void apply_kernel(const uint8_t* __restrict__ 
             if (lx >= tw) continue;
             const int x = x0 + lx, y = y0 + ly;
             // byte of pixel (y, x), channel 0, in the staged window
-            const size_t first = begin + ((size_t)y * W + cl) * 3;
-            const uint8_t* c = s_in + (y - rt) * SPITCH + (int)(first & 3) + (x - cl) * 3;
+            const size_t first = first0 + (size_t)(y - rt) * row_bytes;
+            const uint8_t* c = packed::staged_row(s_in, y - rt, SPITCH, first) + (x - cl) * 3;
             uint8_t* o = s_out + (ly * TW + lx) * 3;
             if (x == 0 || y == 0 || x == W - 1 || y == H - 1) {
                 o[0] = c[0], o[1] = c[1], o[2] = c[2];
                 continue;
             }
             // the rows above and below start at their own phase
-            const size_t fu = begin + ((size_t)(y - 1) * W + cl) * 3, fd = begin + ((size_t)(y + 1) * W + cl) * 3;
-            const uint8_t* u = s_in + (y - 1 - rt) * SPITCH + (int)(fu & 3) + (x - cl) * 3;
-            const uint8_t* d = s_in + (y + 1 - rt) * SPITCH + (int)(fd & 3) + (x - cl) * 3;
+            const uint8_t* u = packed::staged_row(s_in, y - 1 - rt, SPITCH, first - row_bytes) + (x - cl) * 3;
+            const uint8_t* d = packed::staged_row(s_in, y + 1 - rt, SPITCH, first + row_bytes) + (x - cl) * 3;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const int px = c[k];
@@ -324,12 +298,12 @@ __global__ __launch_bounds__(256) void apply_kernel(const uint8_t* __restrict__ 
         const int odw = (tw * 3 + 3 + 3) / 4;
         for (int i = tid; i < th * odw; i += 256) {
             const int r = i / odw;
-            store_row_dword(dst, begin + ((size_t)(y0 + r) * W + x0) * 3, tw * 3, s_out + r * TW * 3, i - r * odw);
+            packed::store_row_dword(dst, begin + ((size_t)(y0 + r) * W + x0) * 3, tw * 3, s_out + r * TW * 3, i - r * odw);
         }
         return;
     }
 
-    const size_t a0 = (begin & ~(size_t)3) + (size_t)blockIdx.y * LIN_BYTES;
+    const size_t a0 = sp.slice(blockIdx.y, LIN_BYTES);
     if (a0 >= end) return;
     const bool table = is_table(S.op), warp = is_warp(S.op);
     uint8_t* s_tab = s_in;                           // 768 bytes of the sharpen window's LDS
@@ -350,7 +324,7 @@ __global__ __launch_bounds__(256) void apply_kernel(const uint8_t* __restrict__ 
         const long long rel = (long long)a - (long long)begin;
         uint32_t out = v;
         if (table) {
-            int c = (int)((rel + 3) % 3);            // rel + 3 >= 0; channel of byte j is (c + j) mod 3
+            int c = (int)sp.channel(a);              // channel of byte j is (c + j) mod 3
             out = 0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -398,10 +372,6 @@ extern "C" int vlmo_randaug(const uint8_t* src, uint8_t* out, uint8_t* scratch, 
                    VLMO_AUG_MAX_SLOTS, n_slots);
     VLMO_CHECK_ARG(src && out && images && images_dev && slots && slots_dev && ws && (scratch || n_slots == 1),
                    "vlmo_randaug: null pointer");
-    VLMO_CHECK_ARG(nbytes > 0 && nbytes % 4 == 0 && (uintptr_t)src % 4 == 0 && (uintptr_t)out % 4 == 0 &&
-                       (uintptr_t)scratch % 4 == 0,
-                   "vlmo_randaug: the three buffers must be 4-byte aligned and a multiple of 4 bytes long (%lld bytes)",
-                   (long long)nbytes);
     {
         const uintptr_t p[3] = {(uintptr_t)src, (uintptr_t)out, (uintptr_t)scratch};
         for (int i = 0; i < 3; ++i)
@@ -411,20 +381,15 @@ extern "C" int vlmo_randaug(const uint8_t* src, uint8_t* out, uint8_t* scratch, 
     }
     VLMO_CHECK_ARG(n_images >= 1 && n_images <= VLMO_AUG_MAX_IMAGES, "vlmo_randaug: need 1 <= images <= %d per call (got %d)",
                    VLMO_AUG_MAX_IMAGES, n_images);
+    if (packed::check_packed("vlmo_randaug", "three buffers", (uintptr_t)src | (uintptr_t)out | (uintptr_t)scratch, nbytes,
+                             images, n_images, VLMO_CROP_MAX_SIDE))
+        return -1;
     VLMO_CHECK_ARG(fill >= 0 && fill <= 255, "vlmo_randaug: fill %d outside [0, 255]", fill);
     VLMO_CHECK_ARG((uintptr_t)ws % 16 == 0 && ws_bytes >= vlmo_randaug_ws_bytes(n_images),
                    "vlmo_randaug: workspace too small or not 16-byte aligned (need %lld bytes, got %lld)",
                    (long long)vlmo_randaug_ws_bytes(n_images), (long long)ws_bytes);
     std::vector<int> order(n_images);
-    for (int i = 0; i < n_images; ++i) {
-        const VlmoImage& I = images[i];
-        VLMO_CHECK_ARG(I.H >= 1 && I.W >= 1 && I.H <= VLMO_CROP_MAX_SIDE && I.W <= VLMO_CROP_MAX_SIDE,
-                       "vlmo_randaug: image %d: sides must lie in [1, %d] (%d x %d)", i, VLMO_CROP_MAX_SIDE, I.H, I.W);
-        VLMO_CHECK_ARG(I.offset >= 0 && I.offset <= nbytes && (int64_t)I.H * I.W * 3 <= nbytes - I.offset,
-                       "vlmo_randaug: image %d (offset %lld, %d x %d x 3) is not inside the %lld-byte buffer", i,
-                       (long long)I.offset, I.H, I.W, (long long)nbytes);
-        order[i] = i;
-    }
+    for (int i = 0; i < n_images; ++i) order[i] = i;
     // every slot rewrites every image in place of the batch: two images that share bytes would race
     std::sort(order.begin(), order.end(), [&](int a, int b) { return images[a].offset < images[b].offset; });
     for (int i = 1; i < n_images; ++i) {

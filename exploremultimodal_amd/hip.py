@@ -9,6 +9,7 @@ but the first call raises.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -658,58 +659,61 @@ FINISH_NORMALIZE, FINISH_MAP_PIXELS = 0, 1
 CROP_MAX_SIZE, CROP_MAX_SIDE, CROP_MAX_JOBS = 1024, 8192, 65536
 
 
-_IMAGE_DT = None
+# VlmoImage, VlmoCropJob and VlmoAugSlot as numpy dtypes, made from the ctypes mirrors above: the sizes and offsets of
+# include/vlmo_hip.h
+_IMAGE_DT, _JOB_DT, _SLOT_DT = np.dtype(Image), np.dtype(CropJob), np.dtype(AugSlot)
 
 
-def _crop_dtypes():
-    """numpy mirrors of VlmoImage / VlmoCropJob (the ctypes classes above give the sizes they must have)."""
-    global _IMAGE_DT
-    if _IMAGE_DT is None:
-        import numpy as np
-        i4, i8 = np.int32, np.int64
-        image = np.dtype([('offset', i8), ('H', i4), ('W', i4)])
-        job = np.dtype([(n, i4) for n in ('image', 'top', 'left', 'h', 'w', 'flip', 'S', 'filter', 'finish', 'pad_')]
-                       + [('tmp_off', i8), ('out', i8)])
-        slot = np.dtype([('op', i4), ('pad_', i4), ('a', np.float64), ('b', np.float64)])
-        assert image.itemsize == ctypes.sizeof(Image) and job.itemsize == ctypes.sizeof(CropJob)
-        assert slot.itemsize == ctypes.sizeof(AugSlot)
-        _IMAGE_DT = (np, image, job, slot)
-    return _IMAGE_DT
+def image_records(images):
+    """[(offset, H, W)] -> VlmoImage records (numpy, on the host)."""
+    return np.array([tuple(im) for im in images], dtype=_IMAGE_DT).reshape(-1)
+
+
+def crop_job_records(jobs):
+    """[(image, top, left, h, w, flip, S, filter, finish, out)] -> (VlmoCropJob records, floats of the intermediate): a
+    job's tmp_off is the running sum of the h * S * 3 floats of the jobs in front of it."""
+    rec = np.array([(im, top, left, h, w, int(flip), S, filt, fin, 0, 0, out.data_ptr())
+                    for im, top, left, h, w, flip, S, filt, fin, out in jobs], dtype=_JOB_DT).reshape(-1)
+    run = np.cumsum(rec['h'].astype(np.int64) * rec['S'] * 3)
+    rec['tmp_off'][1:] = run[:-1]
+    return rec, int(run[-1]) if len(run) else 0
+
+
+def aug_slot_records(ops, a, b):
+    """ops int, a and b float64 arrays [N, n] -> the N * n VlmoAugSlot records, image by image."""
+    rec = np.zeros(ops.size, dtype=_SLOT_DT)
+    rec['op'], rec['a'], rec['b'] = ops.reshape(-1), a.reshape(-1), b.reshape(-1)
+    return rec
+
+
+def _stage_tables(device, itab, second):
+    """The image records and a call's second table in ONE pinned staging buffer, which one asynchronous copy on the current
+    stream uploads.  The image table comes first: its records are 16 bytes, so the table behind it stays 8-byte aligned.
+    -> ((images, images_dev, second, second_dev): the addresses an entry point takes, to check the host copy and hand the
+    device copy to its kernels; the two buffers, for the caller to hold until the entry point has returned)."""
+    ibytes, sbytes = itab.nbytes, second.nbytes
+    host = torch.empty(max(1, ibytes + sbytes), dtype=torch.uint8, pin_memory=True)
+    raw = host.numpy()
+    raw[:ibytes], raw[ibytes:ibytes + sbytes] = itab.view('u1'), second.view('u1')
+    dev = host.to(device, non_blocking=True)
+    return (host.data_ptr(), dev.data_ptr(), host.data_ptr() + ibytes, dev.data_ptr() + ibytes), (host, dev)
 
 
 def crop_resample(pixels, images, jobs, mean, std, pixel_eps):
     """vlmo_crop_resample: pixels = device uint8 buffer of packed HWC images (4-byte aligned, length a multiple of 4);
     images = [(offset, H, W)]; jobs = [(image, top, left, h, w, flip, S, filter, finish, out)] with out an fp32 [3, S, S]
     contiguous device tensor that the job fills.  Two launches for the whole list; the fp32 intermediates live in a cached
-    scratch buffer.  Both tables are built as numpy records in ONE pinned staging buffer, which the entry point checks on
-    the host and one asynchronous copy on the current stream hands to the kernels."""
-    np, image_dt, job_dt, _ = _crop_dtypes()
-    ni, nj = len(images), len(jobs)
+    scratch buffer.  The tables travel as _stage_tables describes."""
     for q, job in enumerate(jobs):
         out, S = job[9], job[6]
         if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != 3 * S * S or out.device != pixels.device:
             raise ValueError(f'crop_resample: job {q}: out must be a contiguous fp32 [3, {S}, {S}] tensor on the pixels\' device')
-    ibytes = ni * image_dt.itemsize                       # a multiple of 16: the job table behind it stays 8-byte aligned
-    host = torch.empty(max(1, ibytes + nj * job_dt.itemsize), dtype=torch.uint8, pin_memory=True)
-    raw = host.numpy()
-    itab, jtab = raw[:ibytes].view(image_dt), raw[ibytes:ibytes + nj * job_dt.itemsize].view(job_dt)
-    if ni:
-        itab[:] = np.array([tuple(im) for im in images], dtype=image_dt)
-    if nj:
-        sizes = np.array([j[3] * j[6] * 3 for j in jobs], dtype=np.int64)
-        run = np.concatenate([[0], np.cumsum(sizes)])
-        jtab[:] = np.array([(im, top, left, h, w, int(flip), S, filt, fin, 0, 0, out.data_ptr())
-                            for im, top, left, h, w, flip, S, filt, fin, out in jobs], dtype=job_dt)
-        jtab['tmp_off'] = run[:-1]
-        total = int(run[-1])
-    else:
-        total = 0
+    itab, (jtab, total) = image_records(images), crop_job_records(jobs)
     ws = _scratch('crop', pixels.device, total * 4, 1 << 24)
-    dev = host.to(pixels.device, non_blocking=True)
+    (ih, idev, jh, jdev), keep = _stage_tables(pixels.device, itab, jtab)
     m3, s3 = (_f32 * 3)(*mean), (_f32 * 3)(*std)
-    _check(lib().vlmo_crop_resample(_p(pixels), pixels.numel(), host.data_ptr(), dev.data_ptr(), ni,
-                                    host.data_ptr() + ibytes, dev.data_ptr() + ibytes, nj, m3, s3, float(pixel_eps), _p(ws),
-                                    ws.numel() * 4, _stream()), 'vlmo_crop_resample')
+    _check(lib().vlmo_crop_resample(_p(pixels), pixels.numel(), ih, idev, len(itab), jh, jdev, len(jtab), m3, s3,
+                                    float(pixel_eps), _p(ws), ws.numel() * 4, _stream()), 'vlmo_crop_resample')
 
 
 (AUG_SKIP, AUG_IDENTITY, AUG_AUTOCONTRAST, AUG_EQUALIZE, AUG_BRIGHTNESS, AUG_SHARPNESS, AUG_SHEAR_X, AUG_SHEAR_Y,
@@ -721,10 +725,8 @@ def randaug(pixels, images, ops, a, b, fill=128, out=None, scratch=None, ws=None
     """vlmo_randaug: pixels = device uint8 buffer of packed HWC images (4-byte aligned, length a multiple of 4); images =
     [(offset, H, W)]; ops int [N, n], a and b float64 [N, n] (array-likes on the host): operation AUG_* and its arguments
     for slot s of image i.  Returns a new buffer of the same length with every image's slots applied in order; bytes
-    outside the images are not written.  out, scratch (for n > 1) and ws default to fresh / cached buffers.  Both tables
-    go through ONE pinned staging buffer, checked on the host by the entry point and copied once on the current stream;
-    nothing is read back."""
-    np, image_dt, _, slot_dt = _crop_dtypes()
+    outside the images are not written.  out, scratch (for n > 1) and ws default to fresh / cached buffers.  The tables
+    travel as _stage_tables describes; nothing is read back."""
     ops = np.asarray(ops, dtype=np.int64)
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     ni = len(images)
@@ -739,19 +741,10 @@ def randaug(pixels, images, ops, a, b, fill=128, out=None, scratch=None, ws=None
         if t is not None and (t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous() or t.device != pixels.device
                               or t.numel() != pixels.numel()):
             raise ValueError(f'randaug: {name} must be a contiguous 1-D uint8 buffer of pixels\' length and device')
-    ibytes = ni * image_dt.itemsize                       # a multiple of 16: the slot table behind it stays 8-byte aligned
-    host = torch.empty(max(1, ibytes + ni * n * slot_dt.itemsize), dtype=torch.uint8, pin_memory=True)
-    raw = host.numpy()
-    if ni:
-        raw[:ibytes].view(image_dt)[:] = np.array([tuple(im) for im in images], dtype=image_dt)
-    stab = raw[ibytes:ibytes + ni * n * slot_dt.itemsize].view(slot_dt)
-    stab['op'], stab['pad_'], stab['a'], stab['b'] = ops.reshape(-1), 0, a.reshape(-1), b.reshape(-1)
-    need = lib().vlmo_randaug_ws_bytes(ni)
     if ws is None:
-        ws = _scratch('randaug', pixels.device, need, 1 << 20)
-    dev = host.to(pixels.device, non_blocking=True)
-    _check(lib().vlmo_randaug(_p(pixels), _p(out), _p(scratch), pixels.numel(), host.data_ptr(), dev.data_ptr(), ni,
-                              host.data_ptr() + ibytes, dev.data_ptr() + ibytes, n, int(fill), _p(ws),
+        ws = _scratch('randaug', pixels.device, lib().vlmo_randaug_ws_bytes(ni), 1 << 20)
+    (ih, idev, sh, sdev), keep = _stage_tables(pixels.device, image_records(images), aug_slot_records(ops, a, b))
+    _check(lib().vlmo_randaug(_p(pixels), _p(out), _p(scratch), pixels.numel(), ih, idev, ni, sh, sdev, n, int(fill), _p(ws),
                               ws.numel() * ws.element_size(), _stream()), 'vlmo_randaug')
     return out
 
