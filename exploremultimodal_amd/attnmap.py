@@ -1,0 +1,138 @@
+"""Attention maps: the soft-max probabilities the blocks compute, materialised for inspection.
+
+The reference's ``Attention.forward`` / ``Block.forward`` return ``(x, attn)`` with ``attn`` the [B, heads, N, N]
+soft-max matrix (vlmo.py:88-98, 187-197).  The fused attention kernels of this engine never form it; this module does, on
+request, with one HIP kernel (``vlmo_attn_probs``) next to the training path: nothing here changes what a forward or a
+backward pass computes.
+
+Definition (one sequence, one head; q, k the engine's bf16 rows, fp32 accumulation):
+
+    P = softmax(q k^T * scale + keymask(-inf), dim=-1)
+
+with these zero rules:
+  * a masked key is exactly 0;
+  * a padded QUERY position is a row like any other (only keys are masked, as in the reference);
+  * key columns and query rows past a sequence's own length (a sequence shorter than ``seq_len``) are 0;
+  * a row whose keys are ALL masked is 0 -- the reference's soft-max gives NaN there.
+
+The maps are PRE-dropout (the reference returns the post-dropout tensor in training mode; the model-level entry points
+refuse training mode) and carry no autograd graph.
+
+Memory: 4 * seq_len^2 bytes per sequence and head -- 209 MB per layer for VLMo-Base at 64 pairs (261 tokens), 4 * 965^2 *
+heads * B bytes at 480 px.  ``queries=(q0, nq)`` (a window of query rows) and ``head_mean=True`` (the mean over heads)
+exist to cut that down.
+"""
+import torch
+
+from . import engine, hip
+
+HEAD_DIM = 64
+MAX_LEN = 1024
+
+
+def _resolve(qkv, seg, num_seq, seq_len, heads, keymask, scale, queries):
+    """Validate the arguments of attention_probs / attention_probs_reference -> (scale, q0, nq)."""
+    if heads < 1 or num_seq < 1:
+        raise ValueError(f'need heads >= 1 and num_seq >= 1 (heads={heads}, num_seq={num_seq})')
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * HEAD_DIM * heads:
+        raise ValueError(f'qkv must be [M, {3 * HEAD_DIM * heads}] (q | k | v, head_dim {HEAD_DIM}), got {tuple(qkv.shape)}')
+    if not 1 <= seq_len <= MAX_LEN:
+        raise ValueError(f'seq_len must be in [1, {MAX_LEN}], got {seq_len}')
+    if seg.dim() != 2 or seg.shape[1] != 4 or seg.shape[0] < num_seq:
+        raise ValueError(f'seg must be [>= {num_seq}, 4] (rowA, lenA, rowB, lenB), got {tuple(seg.shape)}')
+    if keymask is not None and (keymask.dim() != 1 or keymask.shape[0] != qkv.shape[0]):
+        raise ValueError(f'keymask must be [{qkv.shape[0]}], got {tuple(keymask.shape)}')
+    q0, nq = (0, seq_len) if queries is None else (int(queries[0]), int(queries[1]))
+    if q0 < 0 or nq < 1 or q0 + nq > seq_len:
+        raise ValueError(f'queries=({q0}, {nq}) is not a window of [0, {seq_len})')
+    return (HEAD_DIM ** -0.5 if scale is None else float(scale)), q0, nq
+
+
+def attention_probs_reference(qkv, seg, num_seq, seq_len, heads, keymask=None, scale=None, queries=None,
+                              head_mean=False, dtype=torch.float32):
+    """The definition above in plain torch (any device), computed in ``dtype`` (float32 or float64) from the values of
+    ``qkv`` as they are.  Returns [num_seq, 1 if head_mean else heads, nq, seq_len]."""
+    scale, q0, nq = _resolve(qkv, seg, num_seq, seq_len, heads, keymask, scale, queries)
+    d = HEAD_DIM * heads
+    out = torch.zeros((num_seq, heads, nq, seq_len), dtype=dtype, device=qkv.device)
+    for s, (row_a, len_a, row_b, len_b) in enumerate(seg[:num_seq].tolist()):
+        len_a = min(max(len_a, 0), seq_len)
+        len_b = min(max(len_b, 0), seq_len - len_a)
+        n = len_a + len_b
+        rows = torch.cat([torch.arange(row_a, row_a + len_a), torch.arange(row_b, row_b + len_b)]).to(qkv.device)
+        hi = min(q0 + nq, n)
+        if hi <= q0:
+            continue
+        x = qkv[rows].to(dtype)
+        q = x[q0:hi, :d].reshape(hi - q0, heads, HEAD_DIM).transpose(0, 1)
+        k = x[:, d:2 * d].reshape(n, heads, HEAD_DIM).transpose(0, 1)
+        scores = (q @ k.transpose(-2, -1)) * scale
+        if keymask is not None:
+            valid = keymask[rows] != 0
+            if not bool(valid.any()):
+                continue                        # every key masked: zeros (the reference has NaN)
+            scores = scores.masked_fill(~valid[None, None, :], float('-inf'))
+        out[s, :, :hi - q0, :n] = scores.softmax(dim=-1)
+    return out.mean(dim=1, keepdim=True) if head_mean else out
+
+
+def attention_probs(qkv, seg, num_seq, seq_len, heads, keymask=None, scale=None, queries=None, head_mean=False):
+    """P of every sequence of ``seg`` over the packed rows of ``qkv`` [M, 3 * 64 * heads] -> fp32
+    [num_seq, 1 if head_mean else heads, nq, seq_len].
+
+    seg int32 [num_seq, 4] = (rowA, lenA, rowB, lenB): sequence s = rows [rowA, rowA + lenA) ++ [rowB, rowB + lenB), as
+    for the fused attention; seq_len >= every sequence's length, <= 1024.  keymask int32 [M] (0 = masked key) or None.
+    queries = (q0, nq): only query rows [q0, q0 + nq); default all.  scale defaults to 64 ** -0.5.
+    Device tensors (bf16 qkv) take the HIP kernel; CPU tensors take attention_probs_reference in fp32."""
+    scale, q0, nq = _resolve(qkv, seg, num_seq, seq_len, heads, keymask, scale, queries)
+    if not qkv.is_cuda:
+        return attention_probs_reference(qkv, seg, num_seq, seq_len, heads, keymask, scale, (q0, nq), head_mean)
+    if qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
+        raise ValueError('device qkv must be a contiguous bf16 matrix (the engine\'s qkv rows)')
+    seg = seg.to(device=qkv.device, dtype=torch.int32).contiguous()
+    if keymask is not None:
+        keymask = keymask.to(device=qkv.device, dtype=torch.int32).contiguous()
+    probs = torch.empty((num_seq, 1 if head_mean else heads, nq, seq_len), dtype=torch.float32, device=qkv.device)
+    hip.attn_probs(qkv, seg, num_seq, keymask, probs, heads, HEAD_DIM * heads, seq_len, q0, nq, head_mean, scale)
+    return probs
+
+
+# ---- model plumbing: the qkv rows of a block, by the launches the stack itself uses -----------------------------------
+
+@torch.no_grad()
+def block_qkv(block, x, shadows):
+    """bf16 qkv [M, 3d] of ``block`` for the packed fp32 activations x [M, d] that enter it: norm1 to bf16 (vlmo_ln_fwd),
+    then the qkv GEMM with the bias q_bias | 0 | v_bias in its epilogue (vlmo_gemm_nt) -- what vlmo_stack_fwd runs."""
+    M, d = x.shape
+    a = block.attn
+    qb, vb = (a.q_bias, a.v_bias) if a.q_bias is not None else (a._zero_bias, a._zero_bias)
+    y1 = torch.empty((M, d), dtype=torch.bfloat16, device=x.device)
+    mean, rstd = torch.empty(M, device=x.device), torch.empty(M, device=x.device)
+    hip.ln_fwd(x, block.norm1.weight.detach(), block.norm1.bias.detach(), y1, mean, rstd, None, M, d, block.norm1.eps)
+    qkv = torch.empty((M, 3 * d), dtype=torch.bfloat16, device=x.device)
+    hip.gemm_nt(hip.EPI_BIAS, y1, shadows.get(a.qkv.weight, need_t=False)[0], M, 3 * d, d, qkv,
+                tile=engine.DEFAULT_TILE, bias=shadows.qkv_bias(qb, vb))
+    return qkv
+
+
+def plan_kinds(plan, fused):
+    """The sequence kinds of a block call under ``plan``: [(name or None, seg, seq_len)].  Below the fusion layer of an
+    image-text pass the reference calls the block once per modality (vlmo.py:402-404): two kinds, 'txt' and 'img'."""
+    if plan.T and plan.P:
+        if fused:
+            return [(None, plan.seg_vl, plan.T + plan.P)]
+        return [('txt', plan.seg_txt, plan.T), ('img', plan.seg_img, plan.P)]
+    return [(None, plan.seg_txt, plan.T)] if plan.T else [(None, plan.seg_img, plan.P)]
+
+
+@torch.no_grad()
+def block_maps(block, x, plan, fused, shadows, queries=None, head_mean=False):
+    """The attention map(s) of one block call on packed activations x: a tensor [B, heads | 1, nq, N], or
+    {'txt': ..., 'img': ...} when the call has two kinds of sequence."""
+    kinds = plan_kinds(plan, fused)
+    if queries is not None and len(kinds) > 1:
+        raise ValueError('queries needs a single kind of sequence; this layer attends text and image separately')
+    qkv = block_qkv(block, x, shadows)
+    maps = {name: attention_probs(qkv, seg, plan.B, n, block.num_heads, plan.keymask, block.attn.scale, queries, head_mean)
+            for name, seg, n in kinds}
+    return maps[None] if len(kinds) == 1 else maps

@@ -14,6 +14,7 @@
 // tokens, attn_dkdv_long_kernel + attn_dq_long_kernel for 289 - 1024; K / V
 // (or Q / dO) pass through a two-slot LDS ring instead of staying resident.
 // The launch's max_len picks the kernels; nothing else does.
+// attn_probs_kernel (vlmo_attn_probs) writes the probabilities themselves to HBM for inspection, beside this path.
 //
 // Orientation: scores are computed TRANSPOSED, S^T[key][query] = K . Q^T, so a
 // lane owns one query column (softmax reductions are in-register + one
@@ -1488,6 +1489,157 @@ __global__ __launch_bounds__(512) void attn_dkdv_long_kernel(const AttnArgs a) {
     }
 }
 
+// ------------------------------------------------------------------ attention maps (vlmo_attn_probs)
+// P = softmax(q k^T * scale + keymask) written to HBM as fp32 [num_seq, heads | 1, nq, seq_len]: the one tensor the
+// kernels above exist to avoid, for looking at a trained model.  The kernel is bound by its OUTPUT (4 seq_len^2 bytes per
+// sequence and head against 64 multiply-adds per element), so it is laid out for the stores:
+//   * S = Q . K^T with the KEY on the lane (Q is the row operand, as in attn_bwd1_kernel): accumulator register i of a
+//     lane holds query row 8 (i >> 2) + 4 h + (i & 3), key lane & 31.  One store instruction therefore writes two runs of
+//     32 consecutive keys (128 B each) of two output rows.  The forward's transposed tile would scatter 4-byte pieces
+//     over 32 rows.  Rows are only 4-byte aligned (seq_len = 261: 1044 B), so the stores are dwords.
+//   * two sweeps over the keys instead of an nq x seq_len strip: the first keeps a running (maximum, sum) per lane and
+//     register and folds the 32 lanes of a half-wave at the end; the second recomputes S (the same MFMAs, bit for bit)
+//     and stores exp2(S c - m) / l.
+//   * K of one head stays resident for every length: 1024 tokens x 128 B = 128 KB + 8 KB of key bias and row table of
+//     the 160 KB LDS.  One workgroup = one (sequence, head) and a run of query tiles, one tile per wave and round.
+//   * head_mean: the workgroup walks the heads in order, restaging K; a lane owns the same output elements for every
+//     head, so the mean is a read-add-write of its own stores: no atomics, no workspace, a fixed order of additions.
+// Zero rules: masked keys, keys and query rows past the sequence's own length, and rows whose keys are all masked
+// (the reference has NaN there) are written as 0.  Lengths in seg are clamped to seq_len: nothing outside probs is written.
+struct ProbsArgs {
+    const bf16* qkv;
+    const int32_t* seg;
+    const int32_t* keymask;
+    float* probs;
+    int heads, d, seq_len, q0, nq, head_mean, tiles_per_block;
+    float scale_log2e;
+};
+#define ATT_PW 8
+#define ATT_LDS_PROBS (ATT_LMAX * 128 + ATT_LMAX * 8)
+
+__global__ __launch_bounds__(64 * ATT_PW) void attn_probs_kernel(const ProbsArgs a, const int NPAD) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* Kimg = smem;
+    float* kbias = (float*)(smem + NPAD * 128);
+    int* rowidx = (int*)(kbias + NPAD);
+
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int hout = a.head_mean ? 1 : a.heads;
+    const int sidx = blockIdx.x / hout, hd0 = blockIdx.x % hout;
+    const int nh = a.head_mean ? a.heads : 1;
+    const int ld = 3 * a.d;
+    const int rowA = a.seg[4 * sidx + 0], rowB = a.seg[4 * sidx + 2];
+    const int lenA = min(max(a.seg[4 * sidx + 1], 0), a.seq_len);
+    const int N = lenA + min(max(a.seg[4 * sidx + 3], 0), a.seq_len - lenA);
+    for (int i = threadIdx.x; i < NPAD; i += blockDim.x) {
+        const int tok = max(min(i, N - 1), 0);
+        const int row = N == 0 ? 0 : (tok < lenA ? rowA + tok : rowB + (tok - lenA));
+        rowidx[i] = row;
+        kbias[i] = (i < N && (!a.keymask || a.keymask[row] != 0)) ? 0.f : -INFINITY;
+    }
+    __syncthreads();
+
+    const int l31 = lane & 31, h = lane >> 5;
+    const int nkt = (N + 31) >> 5;                  // key tiles that hold keys of this sequence
+    const int nkt_out = NPAD >> 5;                  // key tiles of the output rows
+    const int ntq = (a.nq + 31) >> 5;
+    const int t_begin = blockIdx.y * a.tiles_per_block, t_end = min(ntq, t_begin + a.tiles_per_block);
+    const float c2 = a.scale_log2e;
+    const float inv_heads = 1.f / (float)nh;
+    float* out = a.probs + (size_t)blockIdx.x * a.nq * a.seq_len;
+
+    for (int hi = 0; hi < nh; ++hi) {
+        const int hd = hd0 + hi;
+        if (hi) __syncthreads();                    // every wave is done with the previous head's K image
+        stage_image<ATT_PW>(a.qkv, ld, a.d + hd * 64, rowidx, Kimg, nkt * 4, w, lane);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+
+        for (int qt = t_begin + w; qt < t_end; qt += ATT_PW) {
+            const int ql = qt * 32;                 // first row of the tile inside the query window
+            const bf16* qp = a.qkv + (size_t)rowidx[min(a.q0 + ql + l31, NPAD - 1)] * ld + hd * 64 + 8 * h;
+            bf16x8 qf[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qp + 16 * s);
+
+            // sweep 1: running maximum and sum of every row over the keys this lane sees
+            f32x16 m, l = zero16();
+#pragma unroll
+            for (int i = 0; i < 16; ++i) m[i] = -INFINITY;
+            for (int kt = 0; kt < nkt; ++kt) {
+                f32x16 S = zero16();
+#pragma unroll
+                for (int s = 0; s < 4; ++s) S = Elem<bf16>::mfma(qf[s], row_frag(Kimg, kt * 32, s, lane), S);
+                const float kb = kbias[kt * 32 + l31];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float t = S[i] * c2 + kb;
+                    const float mn = fmaxf(m[i], t);
+                    const float ms = mn == -INFINITY ? 0.f : mn;
+                    l[i] = l[i] * __builtin_amdgcn_exp2f(m[i] - ms) + __builtin_amdgcn_exp2f(t - ms);
+                    m[i] = mn;
+                }
+            }
+            // the 32 lanes of a half-wave hold the same 16 rows: fold them (fixed order)
+#pragma unroll
+            for (int off = 16; off > 0; off >>= 1)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float mo = __shfl_xor(m[i], off, 64), lo = __shfl_xor(l[i], off, 64);
+                    const float mn = fmaxf(m[i], mo);
+                    const float ms = mn == -INFINITY ? 0.f : mn;
+                    l[i] = l[i] * __builtin_amdgcn_exp2f(m[i] - ms) + lo * __builtin_amdgcn_exp2f(mo - ms);
+                    m[i] = mn;
+                }
+            // l becomes the factor of the row (0: the row is written as zeros), m its finite reference
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int qi = a.q0 + ql + 8 * (i >> 2) + 4 * h + (i & 3);
+                const bool zero = qi >= N || m[i] == -INFINITY;
+                l[i] = zero ? 0.f : inv_heads / l[i];
+                m[i] = zero ? 0.f : m[i];
+            }
+
+            // sweep 2: the same scores again, normalised and stored
+            const int rows_left = a.nq - ql - 4 * h;        // row 8 (i >> 2) + (i & 3) of this half is inside the window
+            for (int kt = 0; kt < nkt_out; ++kt) {
+                const int key = kt * 32 + l31;
+                const bool has_keys = kt < nkt;             // wave-uniform
+                f32x16 S = zero16();
+                float kb = 0.f;
+                if (has_keys) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) S = Elem<bf16>::mfma(qf[s], row_frag(Kimg, kt * 32, s, lane), S);
+                    kb = kbias[key];
+                }
+                if (key < a.seq_len) {
+                    float* op = out + (size_t)(ql + 4 * h) * a.seq_len + key;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int r = 8 * (i >> 2) + (i & 3);
+                        if (r < rows_left) {
+                            float v = 0.f;
+                            if (has_keys && l[i] != 0.f) v = __builtin_amdgcn_exp2f(S[i] * c2 + kb - m[i]) * l[i];
+                            float* p = op + (size_t)r * a.seq_len;
+                            *p = hi ? *p + v : v;
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+int launch_probs(const ProbsArgs& a, int gx, int gy, hipStream_t st) {
+    static DeviceOnce once;
+    if (once.first())
+        (void)hipFuncSetAttribute((const void*)attn_probs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_PROBS);
+    const int npad = (a.seq_len + 31) / 32 * 32;
+    hipLaunchKernelGGL(attn_probs_kernel, dim3(gx, gy), dim3(64 * ATT_PW), npad * 136, st, a, npad);
+    return 0;
+}
+
 int launch_fwd_long(const AttnArgs& a, int nblocks, hipStream_t st) {
     static DeviceOnce once;
     if (once.first())
@@ -1642,5 +1794,35 @@ extern "C" int vlmo_attn_bwd(const void* qkv, const void* ctx, const void* dctx,
     if (nt > 8) launch_bwd(a, nt, nb, stream);      // 257 .. 288: one tile more than the single-pass kernel's eight owners
     else launch_bwd1(a, nt, nb, stream);
     VLMO_CHECK_LAUNCH("vlmo_attn_bwd");
+    return 0;
+}
+
+extern "C" int vlmo_attn_probs(const void* qkv, const int32_t* seg, int num_seq, const int32_t* keymask, float* probs,
+                               int heads, int d, int seq_len, int q0, int nq, int head_mean, float scale,
+                               hipStream_t stream) {
+    if (int rc = check_common("vlmo_attn_probs", qkv, seg, num_seq, heads, d, seq_len, ATT_LMAX)) return rc;
+    VLMO_CHECK_ARG(probs, "vlmo_attn_probs: null probs");
+    VLMO_CHECK_ARG(q0 >= 0 && nq >= 1 && q0 <= seq_len - nq, "vlmo_attn_probs: query rows [%d, %d + %d) outside [0, %d)", q0,
+                   q0, nq, seq_len);
+    ProbsArgs a{};
+    a.qkv = (const bf16*)qkv;
+    a.seg = seg;
+    a.keymask = keymask;
+    a.probs = probs;
+    a.heads = heads;
+    a.d = d;
+    a.seq_len = seq_len;
+    a.q0 = q0;
+    a.nq = nq;
+    a.head_mean = head_mean != 0;
+    a.scale_log2e = scale * LOG2E;
+    // one query tile per wave and round; the query tiles of a (sequence, head) are split over workgroups only while
+    // that adds workgroups the chip has room for (each one stages the head's K again)
+    const int gx = num_seq * (a.head_mean ? 1 : heads);
+    const int rounds = ((nq + 31) / 32 + ATT_PW - 1) / ATT_PW;
+    const int gy = std::min(rounds, std::max(1, (768 + gx - 1) / gx));
+    a.tiles_per_block = ATT_PW * ((rounds + gy - 1) / gy);
+    launch_probs(a, gx, (rounds * ATT_PW + a.tiles_per_block - 1) / a.tiles_per_block, stream);
+    VLMO_CHECK_LAUNCH("vlmo_attn_probs");
     return 0;
 }

@@ -103,6 +103,7 @@ _SIGS = {
                       _u64, _i32, _vp],
     'vlmo_attn_bwd': [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _f32,
                       _u32, _f32, _u64, _i32, _vp],
+    'vlmo_attn_probs': [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
     'vlmo_resid_bwd': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _f32, _u64, _vp, _i64, _vp],
     'vlmo_colsum': [_i32, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _vp],
     'vlmo_cast_weight': [_i32, _vp, _i32, _i32, _vp, _vp, _vp],
@@ -165,7 +166,7 @@ _SIGS = {
 }
 
 _lib = None
-ABI_VERSION = 10     # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
+ABI_VERSION = 11     # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
 
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is missing."""
@@ -343,6 +344,13 @@ def attn_bwd(qkv, ctx, dctx, lse, seg, nseq, keymask, dqkv, heads, d, max_len, s
                              _p(keymask), _p(dqkv), _p(qv_colsum), heads, d, max_len, scale, drop[0], drop[1],
                              _seed64(seed), mask_seq0, _stream())
     _check(rc, 'vlmo_attn_bwd')
+
+
+def attn_probs(qkv, seg, nseq, keymask, probs, heads, d, seq_len, q0, nq, head_mean, scale):
+    """probs fp32 [nseq, 1 if head_mean else heads, nq, seq_len] = softmax(q k^T * scale + keymask), rows [q0, q0 + nq)."""
+    rc = lib().vlmo_attn_probs(_p(qkv), _p(seg), nseq, _p(keymask), _p(probs), heads, d, seq_len, q0, nq,
+                               int(bool(head_mean)), scale, _stream())
+    _check(rc, 'vlmo_attn_probs')
 
 
 def resid_bwd(dx, zd, gamma, row_scale, dz, dgamma, dbias, M, d, drop=(0, 1.0), seed=0, row_index=None):

@@ -9,8 +9,10 @@ reference load unchanged.
 
 Documented deviations:
   * ``Attention`` / ``Block`` return ``None`` for the attention-probability
-    tensor (vlmo.py:98): every caller in the reference drops it and the fused
-    kernel never materialises [B,h,N,N];
+    tensor (vlmo.py:98) by default: every caller in the reference drops it and
+    the fused kernel never materialises [B,h,N,N].  ``Block.forward(...,
+    return_attn=True)`` and ``VLMO.attention_maps`` compute it on request
+    (attnmap.py: pre-dropout, fp32, no autograd graph);
   * inputs must live on a gfx950 device; there is no CPU path.
 """
 import math
@@ -20,7 +22,7 @@ from types import SimpleNamespace
 import torch
 import torch.nn as nn
 
-from . import engine, hip
+from . import attnmap, engine, hip
 
 
 def trunc_normal_(tensor, mean=0., std=1., a=-2., b=2.):
@@ -172,15 +174,20 @@ class Block(nn.Module):
         meta, params = self.meta(x, plan, routes, ranges, fused, shadows, seed, drop_scales)
         return engine.StackFn.apply(x, [meta], *params)
 
-    def forward(self, x, mask=None, route='vl'):
-        """Reference signature (vlmo.py:187): x [B, N, d] -> (x, attn=None)."""
+    def forward(self, x, mask=None, route='vl', return_attn=False):
+        """Reference signature (vlmo.py:187): x [B, N, d] -> (x, attn).  attn is None unless ``return_attn``: then the
+        fp32 [B, heads, N, N] soft-max probabilities of THIS call, computed from x with the LayerNorm and qkv GEMM the
+        stack runs (attnmap.py).  They are pre-dropout (the reference returns the post-dropout tensor in training
+        mode), carry no autograd graph, and a row whose keys are all masked is 0 where the reference has NaN."""
         owner = getattr(self, '_owner', None)
         shadows = owner()._shadows if owner is not None else engine.ShadowCache()
         B, N, d = x.shape
         plan = engine.Plan(B, 0, N, x.device, None, mask)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.training else 0
-        out = self.run(x.reshape(B * N, d).float().contiguous(), plan, [route], [(0, B * N)], False, shadows, seed)
-        return out.view(B, N, d), None
+        xp = x.reshape(B * N, d).float().contiguous()
+        attn = attnmap.block_maps(self, xp.detach(), plan, False, shadows) if return_attn else None
+        out = self.run(xp, plan, [route], [(0, B * N)], False, shadows, seed)
+        return out.view(B, N, d), attn
 
 
 _CONSTS = {}
@@ -445,6 +452,49 @@ class VLMO(nn.Module):
                                           self.norm.eps)
         co_attn_masks = torch.cat([txt_attn_masks, img_attn_masks], dim=1)
         return out, co_attn_masks
+
+    @torch.no_grad()
+    def attention_maps(self, img=None, txt=None, img_attn_masks=None, txt_attn_masks=None, layers=None,
+                       fusion_layer=None, bool_masked_pos=None, img_token_type_idx=1, queries=None, head_mean=False):
+        """The attention maps of a forward_features pass -> {layer: map}, fp32.
+
+        Single-modality passes give one [B, heads, N, N] tensor per layer.  In an image-text pass a layer below the
+        fusion layer gives {'txt': [B, heads, T, T], 'img': [B, heads, P, P]} (the reference calls the block once per
+        modality there, vlmo.py:402-404); a fused layer gives [B, heads, T + P, T + P] with the TEXT tokens first
+        (vlmo.py:406).  layers: the block indices wanted (default all).  queries=(q0, nq) keeps query rows
+        [q0, q0 + nq) only and is accepted when every requested layer has a single kind of sequence; head_mean=True
+        gives the mean over heads ([B, 1, ...]).  Zero rules and memory: attnmap.py.
+
+        Eval mode only (RuntimeError otherwise): in training mode the reference's attn is post-dropout and hidden
+        dropout / drop-path would change the activations the maps are computed from.  Runs under no_grad."""
+        if self.training:
+            raise RuntimeError('attention_maps needs eval mode: the maps are pre-dropout and are computed from the '
+                               'activations of a deterministic pass (call model.eval() first)')
+        dev = self._check_inputs(img, txt, img_attn_masks, txt_attn_masks)
+        L = len(self.blocks)
+        layers = list(range(L)) if layers is None else sorted(set(int(i) for i in layers))
+        if any(i < 0 or i >= L for i in layers):
+            raise ValueError(f'layers must be block indices in [0, {L}), got {layers}')
+        P = self.patch_embed.num_patches + 1
+        if txt is None:
+            plan, mode, fl = engine.Plan(img.shape[0], 0, P, dev, None, img_attn_masks), 'v', 0
+        elif img is None:
+            plan, mode, fl = engine.Plan(txt.shape[0], txt.shape[1], 0, dev, txt_attn_masks, None), 'l', 0
+        else:
+            fl = fusion_layer or self.fusion_layer
+            assert 0 <= fl <= self.bert_config.num_hidden_layers
+            plan, mode = engine.Plan(txt.shape[0], txt.shape[1], P, dev, txt_attn_masks, img_attn_masks), 'vl'
+        if queries is not None and mode == 'vl' and any(i < fl for i in layers):
+            raise ValueError(f'queries needs a single kind of sequence in every requested layer; layers below the fusion '
+                             f'layer {fl} attend text and image separately')
+        x = self._embed(plan, img, txt, bool_masked_pos, img_token_type_idx, 0)
+        maps, done = {}, 0
+        for i in layers:
+            x = self._run_blocks(x, plan, mode, fl, range(done, i), 0)
+            done = i
+            fused = self._routes(i, mode, fl, plan)[2]
+            maps[i] = attnmap.block_maps(self.blocks[i], x, plan, fused, self._shadows, queries, head_mean)
+        return maps
 
     def forward(self, img=None, txt=None, img_attn_masks=None, txt_attn_masks=None, fusion_layer=None,
                 img_token_type_idx=1):

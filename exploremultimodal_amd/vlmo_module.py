@@ -216,6 +216,22 @@ class VlmoModule(nn.Module):
                 'img_masks': img_attn_masks, 'img_bool_masked_pos': bool_masked_pos, 'txt_labels': txt_labels,
                 'txt_ids': txt_ids, 'txt_masks': txt_attn_masks}
 
+    def attention_maps(self, batch, infer_mode='img-txt', layers=None, queries=None, head_mean=False):
+        """The attention maps of the backbone pass ``infer(batch, infer_mode)`` runs -> {layer: map} (VLMO.attention_maps:
+        shapes, zero rules, eval mode only).  Masks and inputs are picked exactly as infer picks them."""
+        assert infer_mode in ['img_only', 'txt_only', 'img-txt']
+        transformer = self.transformer
+        img, img_attn_masks, txt_ids, txt_attn_masks = None, None, None, None
+        if 'img' in infer_mode:
+            img = batch['image_0'] if 'image_0' in batch else batch['image']
+            img_attn_masks = torch.ones([img.size(0), transformer.patch_embed.num_patches + 1], dtype=torch.int64,
+                                        device=img.device)
+        if 'txt' in infer_mode:
+            txt_ids, txt_attn_masks = batch['text_ids'], batch['text_mask']
+        return transformer.attention_maps(img=img, txt=txt_ids, img_attn_masks=img_attn_masks,
+                                          txt_attn_masks=txt_attn_masks, layers=layers, queries=queries,
+                                          head_mean=head_mean)
+
     # ------------------------------------------------- merged backbone passes
     @staticmethod
     def _split_infer(out, sizes):

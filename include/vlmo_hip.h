@@ -82,7 +82,7 @@ typedef struct VlmoEpilogue {
 const char* vlmo_last_error(void);
 /* Version of the struct layouts and signatures below; raised whenever one of them changes
  * (exploremultimodal_amd/hip.py mirrors it as ABI_VERSION and refuses any other). */
-#define VLMO_ABI_VERSION 10
+#define VLMO_ABI_VERSION 11
 int vlmo_abi_version(void);     /* = VLMO_ABI_VERSION of the header the library was built from */
 
 /* C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue.  tile: -1 = pick by shape, 0 = 128x128x64
@@ -186,6 +186,20 @@ int vlmo_attn_bwd(const void* qkv, const void* ctx, const void* dctx, const floa
                   int lse_stride, const int32_t* seg, int num_seq, const int32_t* keymask,
                   void* dqkv, float* qv_colsum, int heads, int d, int max_len, float scale,
                   uint32_t drop_thresh, float inv_keep, uint64_t seed, int mask_seq0, hipStream_t stream);
+
+/* Attention maps: P = softmax((q k^T) * scale + keymask(-inf)) over packed rows (vlmo.py:88-92), written to HBM -- the
+ * tensor the reference's Attention / Block return as `attn` and the fused kernels above never form.  Read-only
+ * diagnostics: pre-dropout, no backward.
+ * qkv, seg, keymask: exactly as vlmo_attn_fwd.  probs fp32, contiguous [num_seq, head_mean ? 1 : heads, nq, seq_len]:
+ * query rows [q0, q0 + nq) of every sequence against all keys.  seq_len = key dimension of the output, >= every
+ * sequence's length (longer ones are clamped to it), <= 1024.
+ * A masked key gets exactly 0; a padded QUERY position is a row like any other (only keys are masked); key columns and
+ * query rows past a sequence's own length are 0; a row whose keys are all masked is 0 (the reference has NaN there).
+ * head_mean: the arithmetic mean over the heads, summed in head order by one workgroup (no atomics, no workspace):
+ * two runs are bitwise equal.  Refused (negative status): d / heads != 64, seq_len outside [1, 1024], q0 < 0, nq < 1,
+ * q0 + nq > seq_len, num_seq < 1, null qkv / seg / probs. */
+int vlmo_attn_probs(const void* qkv, const int32_t* seg, int num_seq, const int32_t* keymask, float* probs,
+                    int heads, int d, int seq_len, int q0, int nq, int head_mean, float scale, hipStream_t stream);
 
 /* Residual-branch backward (vlmo.py:194-196): dz = dx * gamma * row_scale * dropmask/(1-p);
  * dgamma += sum_m dx * row_scale * zd;  dbias += sum_m dz. */
