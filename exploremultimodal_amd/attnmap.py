@@ -21,6 +21,17 @@ refuse training mode) and carry no autograd graph.
 Memory: 4 * seq_len^2 bytes per sequence and head -- 209 MB per layer for VLMo-Base at 64 pairs (261 tokens), 4 * 965^2 *
 heads * B bytes at 480 px.  ``queries=(q0, nq)`` (a window of query rows) and ``head_mean=True`` (the mean over heads)
 exist to cut that down.
+
+Gradient-weighted maps (Grad-CAM on ``attn``, ``vlmo_attn_gradcam``).  With P taken as a free variable of ctx = P v, the
+gradient of a score with respect to it is, per head,
+
+    G[i, j] = sum_c dctx[row_i, 64 h + c] * v[row_j, 64 h + c]          (bf16 products, fp32 accumulation)
+
+with dctx the bf16 [M, d] gradient of the attention context on the packed rows (head-major like ctx) -- what the
+reference obtains with a hook and ``retain_grad()`` on the ``attn`` tensor.  kind 'grad' gives G, 'attn_grad' P * G,
+'cam' (the default) P * max(G, 0).  The zero rules above hold for every kind, 'grad' included; ``head_mean`` is the mean
+over heads of the per-head output (of the products, not the product of the means).  Shapes, windows and memory are those
+of the maps.
 """
 import torch
 
@@ -48,11 +59,20 @@ def _resolve(qkv, seg, num_seq, seq_len, heads, keymask, scale, queries):
     return (HEAD_DIM ** -0.5 if scale is None else float(scale)), q0, nq
 
 
-def attention_probs_reference(qkv, seg, num_seq, seq_len, heads, keymask=None, scale=None, queries=None,
-                              head_mean=False, dtype=torch.float32):
-    """The definition above in plain torch (any device), computed in ``dtype`` (float32 or float64) from the values of
-    ``qkv`` as they are.  Returns [num_seq, 1 if head_mean else heads, nq, seq_len]."""
-    scale, q0, nq = _resolve(qkv, seg, num_seq, seq_len, heads, keymask, scale, queries)
+KINDS = ('cam', 'attn_grad', 'grad')
+
+
+def _resolve_gradcam(qkv, dctx, heads, kind):
+    """The arguments attention_gradcam / attention_gradcam_reference have on top of _resolve's."""
+    if kind not in KINDS:
+        raise ValueError(f'kind must be one of {KINDS}, got {kind!r}')
+    if dctx.dim() != 2 or tuple(dctx.shape) != (qkv.shape[0], HEAD_DIM * heads):
+        raise ValueError(f'dctx must be [{qkv.shape[0]}, {HEAD_DIM * heads}] (the rows of qkv, head-major), '
+                         f'got {tuple(dctx.shape)}')
+
+
+def _restate(qkv, dctx, seg, num_seq, seq_len, heads, keymask, scale, q0, nq, head_mean, kind, dtype):
+    """The definitions of the module docstring in plain torch: P when ``kind`` is None, else the gradient-weighted map."""
     d = HEAD_DIM * heads
     out = torch.zeros((num_seq, heads, nq, seq_len), dtype=dtype, device=qkv.device)
     for s, (row_a, len_a, row_b, len_b) in enumerate(seg[:num_seq].tolist()):
@@ -67,13 +87,39 @@ def attention_probs_reference(qkv, seg, num_seq, seq_len, heads, keymask=None, s
         q = x[q0:hi, :d].reshape(hi - q0, heads, HEAD_DIM).transpose(0, 1)
         k = x[:, d:2 * d].reshape(n, heads, HEAD_DIM).transpose(0, 1)
         scores = (q @ k.transpose(-2, -1)) * scale
+        valid = None
         if keymask is not None:
             valid = keymask[rows] != 0
             if not bool(valid.any()):
                 continue                        # every key masked: zeros (the reference has NaN)
             scores = scores.masked_fill(~valid[None, None, :], float('-inf'))
-        out[s, :, :hi - q0, :n] = scores.softmax(dim=-1)
+        val = scores.softmax(dim=-1)
+        if kind is not None:
+            v = x[:, 2 * d:].reshape(n, heads, HEAD_DIM).transpose(0, 1)
+            g = dctx[rows[q0:hi]].to(dtype).reshape(hi - q0, heads, HEAD_DIM).transpose(0, 1)
+            G = g @ v.transpose(-2, -1)
+            if valid is not None:
+                G = G.masked_fill(~valid[None, None, :], 0.0)
+            val = G if kind == 'grad' else val * (G.clamp_min(0.0) if kind == 'cam' else G)
+        out[s, :, :hi - q0, :n] = val
     return out.mean(dim=1, keepdim=True) if head_mean else out
+
+
+def attention_probs_reference(qkv, seg, num_seq, seq_len, heads, keymask=None, scale=None, queries=None,
+                              head_mean=False, dtype=torch.float32):
+    """The definition above in plain torch (any device), computed in ``dtype`` (float32 or float64) from the values of
+    ``qkv`` as they are.  Returns [num_seq, 1 if head_mean else heads, nq, seq_len]."""
+    scale, q0, nq = _resolve(qkv, seg, num_seq, seq_len, heads, keymask, scale, queries)
+    return _restate(qkv, None, seg, num_seq, seq_len, heads, keymask, scale, q0, nq, head_mean, None, dtype)
+
+
+def attention_gradcam_reference(qkv, dctx, seg, num_seq, seq_len, heads, keymask=None, scale=None, queries=None,
+                                head_mean=False, kind='cam', dtype=torch.float32):
+    """The gradient-weighted map of the module docstring in plain torch (any device), computed in ``dtype`` (float32 or
+    float64) from the values of ``qkv`` and ``dctx`` as they are -> [num_seq, 1 if head_mean else heads, nq, seq_len]."""
+    scale, q0, nq = _resolve(qkv, seg, num_seq, seq_len, heads, keymask, scale, queries)
+    _resolve_gradcam(qkv, dctx, heads, kind)
+    return _restate(qkv, dctx, seg, num_seq, seq_len, heads, keymask, scale, q0, nq, head_mean, kind, dtype)
 
 
 def attention_probs(qkv, seg, num_seq, seq_len, heads, keymask=None, scale=None, queries=None, head_mean=False):
@@ -95,6 +141,38 @@ def attention_probs(qkv, seg, num_seq, seq_len, heads, keymask=None, scale=None,
     probs = torch.empty((num_seq, 1 if head_mean else heads, nq, seq_len), dtype=torch.float32, device=qkv.device)
     hip.attn_probs(qkv, seg, num_seq, keymask, probs, heads, HEAD_DIM * heads, seq_len, q0, nq, head_mean, scale)
     return probs
+
+
+def attention_gradcam(qkv, dctx, seg, num_seq, seq_len, heads, keymask=None, scale=None, queries=None, head_mean=False,
+                      kind='cam'):
+    """The gradient-weighted map of every sequence of ``seg``: 'cam' P * max(G, 0), 'attn_grad' P * G or 'grad' G with
+    G = dctx v^T per head -> fp32 [num_seq, 1 if head_mean else heads, nq, seq_len].  dctx [M, 64 * heads]: the gradient
+    of the attention context on the rows of ``qkv``; everything else as attention_probs.
+    Device tensors (contiguous bf16 qkv and dctx) take the HIP kernel; CPU tensors take attention_gradcam_reference."""
+    scale, q0, nq = _resolve(qkv, seg, num_seq, seq_len, heads, keymask, scale, queries)
+    _resolve_gradcam(qkv, dctx, heads, kind)
+    if not qkv.is_cuda:
+        return attention_gradcam_reference(qkv, dctx, seg, num_seq, seq_len, heads, keymask, scale, (q0, nq), head_mean,
+                                           kind)
+    if qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
+        raise ValueError('device qkv must be a contiguous bf16 matrix (the engine\'s qkv rows)')
+    if dctx.device != qkv.device or dctx.dtype != torch.bfloat16 or not dctx.is_contiguous():
+        raise ValueError('device dctx must be a contiguous bf16 matrix on the device of qkv (the engine\'s dctx rows)')
+    seg = seg.to(device=qkv.device, dtype=torch.int32).contiguous()
+    if keymask is not None:
+        keymask = keymask.to(device=qkv.device, dtype=torch.int32).contiguous()
+    out = torch.empty((num_seq, 1 if head_mean else heads, nq, seq_len), dtype=torch.float32, device=qkv.device)
+    hip.attn_gradcam(qkv, dctx, seg, num_seq, keymask, out, heads, HEAD_DIM * heads, seq_len, q0, nq, kind, head_mean, scale)
+    return out
+
+
+def text_to_image_heatmaps(cam, T, grid):
+    """Text-token rows against image-patch columns of a FUSED-layer map [B, heads | 1, nq, T + 1 + grid^2] (text first,
+    then the image CLS, then the patches row by row) -> [B, heads | 1, T, grid, grid]: one heat map over the image per
+    text token.  The map must hold the query rows [0, T) first (the full map, or queries=(0, T))."""
+    if cam.dim() != 4 or cam.shape[2] < T or cam.shape[3] != T + 1 + grid * grid:
+        raise ValueError(f'need a fused-layer map [B, heads | 1, >= {T}, {T + 1 + grid * grid}], got {tuple(cam.shape)}')
+    return cam[:, :, :T, T + 1:].reshape(cam.shape[0], cam.shape[1], T, grid, grid)
 
 
 # ---- model plumbing: the qkv rows of a block, by the launches the stack itself uses -----------------------------------
@@ -136,3 +214,15 @@ def block_maps(block, x, plan, fused, shadows, queries=None, head_mean=False):
     maps = {name: attention_probs(qkv, seg, plan.B, n, block.num_heads, plan.keymask, block.attn.scale, queries, head_mean)
             for name, seg, n in kinds}
     return maps[None] if len(kinds) == 1 else maps
+
+
+def gradcam_capture(block, store, key, queries=None, head_mean=False, kind='cam'):
+    """The engine.BlockMeta.capture callback of one block call: launches vlmo_attn_gradcam on the block's saved qkv rows
+    and its dctx, straight from the engine's buffers on the backward's stream, and files the map(s) as store[key] -- a
+    tensor [B, heads | 1, nq, N], or {'txt': ..., 'img': ...} when the call has two kinds of sequence."""
+    def capture(qkv, dctx, plan, fused):
+        kinds = plan_kinds(plan, fused)
+        maps = {name: attention_gradcam(qkv, dctx, seg, plan.B, n, block.num_heads, plan.keymask, block.attn.scale,
+                                        queries, head_mean, kind) for name, seg, n in kinds}
+        store[key] = maps[None] if len(kinds) == 1 else maps
+    return capture

@@ -14,7 +14,8 @@
 // tokens, attn_dkdv_long_kernel + attn_dq_long_kernel for 289 - 1024; K / V
 // (or Q / dO) pass through a two-slot LDS ring instead of staying resident.
 // The launch's max_len picks the kernels; nothing else does.
-// attn_probs_kernel (vlmo_attn_probs) writes the probabilities themselves to HBM for inspection, beside this path.
+// attn_probs_kernel (vlmo_attn_probs) writes the probabilities themselves to HBM for inspection, beside this path;
+// attn_gradcam_kernel (vlmo_attn_gradcam) their gradient-weighted form.
 //
 // Orientation: scores are computed TRANSPOSED, S^T[key][query] = K . Q^T, so a
 // lane owns one query column (softmax reductions are in-register + one
@@ -1640,6 +1641,189 @@ int launch_probs(const ProbsArgs& a, int gx, int gy, hipStream_t st) {
     return 0;
 }
 
+// ------------------------------------------------------------------ gradient-weighted maps (vlmo_attn_gradcam)
+// Grad-CAM on the attention maps: with P taken as a free variable, d score / d P[i, j] = G[i, j] = dctx[i, :] . v[j, :]
+// per head (ctx = P v).  The kernel is attn_probs_kernel with one more MFMA chain in the second sweep: the dctx rows of
+// the query tile are a second row operand held in registers beside q, and V is a second key-row image beside K, so G
+// lands in the accumulator layout of S (query row on the register, key on the lane) and the combination
+//   kind GRAD: G      ATTN_GRAD: P * G      CAM: P * max(G, 0)
+// is stored exactly as the maps are (128-byte key runs, read-add-write head mean in head order).
+//   * VRES (seq_len <= 512): K and V of the head both resident, 2 x 64 KB + the 4 KB of key bias and row table.
+//   * longer (513 - 1024): K alone takes 128 KB, so the V operand of a key tile (4 x 16 B per lane, the bytes row_frag
+//     would read from an image) is streamed from global memory into registers, one tile ahead: the loads of tile kt + 1
+//     are issued before the stores of tile kt.  A wave reads 4 KB of V (L2 hits: the head's V is 128 KB) per 4 KB tile
+//     it stores, and the stores go to HBM.
+// The zero rules of the maps hold for every kind: G is written only where the definition of P has a non-zero.
+struct GradcamArgs {
+    const bf16* qkv;
+    const bf16* dctx;
+    const int32_t* seg;
+    const int32_t* keymask;
+    float* out;
+    int heads, d, seq_len, q0, nq, head_mean, tiles_per_block, kind;
+    float scale_log2e;
+};
+#define ATT_LDS_GRADCAM (512 * 256 + 512 * 8)   // VRES at 512 tokens; the long form needs ATT_LDS_PROBS
+
+template <bool VRES>
+__global__ __launch_bounds__(64 * ATT_PW) void attn_gradcam_kernel(const GradcamArgs a, const int NPAD) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* Kimg = smem;
+    char* Vimg = smem + NPAD * 128;                 // VRES only
+    float* kbias = (float*)(smem + (VRES ? 2 : 1) * NPAD * 128);
+    int* rowidx = (int*)(kbias + NPAD);
+
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int hout = a.head_mean ? 1 : a.heads;
+    const int sidx = blockIdx.x / hout, hd0 = blockIdx.x % hout;
+    const int nh = a.head_mean ? a.heads : 1;
+    const int ld = 3 * a.d;
+    const int rowA = a.seg[4 * sidx + 0], rowB = a.seg[4 * sidx + 2];
+    const int lenA = min(max(a.seg[4 * sidx + 1], 0), a.seq_len);
+    const int N = lenA + min(max(a.seg[4 * sidx + 3], 0), a.seq_len - lenA);
+    for (int i = threadIdx.x; i < NPAD; i += blockDim.x) {
+        const int tok = max(min(i, N - 1), 0);
+        const int row = N == 0 ? 0 : (tok < lenA ? rowA + tok : rowB + (tok - lenA));
+        rowidx[i] = row;
+        kbias[i] = (i < N && (!a.keymask || a.keymask[row] != 0)) ? 0.f : -INFINITY;
+    }
+    __syncthreads();
+
+    const int l31 = lane & 31, h = lane >> 5;
+    const int nkt = (N + 31) >> 5;                  // key tiles that hold keys of this sequence
+    const int nkt_out = NPAD >> 5;                  // key tiles of the output rows
+    const int ntq = (a.nq + 31) >> 5;
+    const int t_begin = blockIdx.y * a.tiles_per_block, t_end = min(ntq, t_begin + a.tiles_per_block);
+    const float c2 = a.scale_log2e;
+    const float inv_heads = 1.f / (float)nh;
+    const int kind = a.kind;
+    float* out = a.out + (size_t)blockIdx.x * a.nq * a.seq_len;
+
+    for (int hi = 0; hi < nh; ++hi) {
+        const int hd = hd0 + hi;
+        if (hi) __syncthreads();                    // every wave is done with the previous head's images
+        stage_image<ATT_PW>(a.qkv, ld, a.d + hd * 64, rowidx, Kimg, nkt * 4, w, lane);
+        if (VRES) stage_image<ATT_PW>(a.qkv, ld, 2 * a.d + hd * 64, rowidx, Vimg, nkt * 4, w, lane);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        // the V operand of key tile kt: row_frag of the image, or the same 16 bytes per lane and k-step from global memory
+        auto v_frags = [&](int kt, bf16x8* vf) {
+            if (VRES) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) vf[s] = row_frag(Vimg, kt * 32, s, lane);
+            } else {
+                const bf16* vp = a.qkv + (size_t)rowidx[kt * 32 + l31] * ld + 2 * a.d + hd * 64 + 8 * h;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) vf[s] = *(const bf16x8*)(vp + 16 * s);
+            }
+        };
+
+        for (int qt = t_begin + w; qt < t_end; qt += ATT_PW) {
+            const int ql = qt * 32;                 // first row of the tile inside the query window
+            const size_t qrow = (size_t)rowidx[min(a.q0 + ql + l31, NPAD - 1)];
+            const bf16* qp = a.qkv + qrow * ld + hd * 64 + 8 * h;
+            const bf16* dp = a.dctx + qrow * a.d + hd * 64 + 8 * h;
+            bf16x8 qf[4], df[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                qf[s] = *(const bf16x8*)(qp + 16 * s);
+                df[s] = *(const bf16x8*)(dp + 16 * s);
+            }
+
+            // sweep 1: running maximum and sum of every row over the keys this lane sees (as attn_probs_kernel)
+            f32x16 m, l = zero16();
+#pragma unroll
+            for (int i = 0; i < 16; ++i) m[i] = -INFINITY;
+            for (int kt = 0; kt < nkt; ++kt) {
+                f32x16 S = zero16();
+#pragma unroll
+                for (int s = 0; s < 4; ++s) S = Elem<bf16>::mfma(qf[s], row_frag(Kimg, kt * 32, s, lane), S);
+                const float kb = kbias[kt * 32 + l31];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float t = S[i] * c2 + kb;
+                    const float mn = fmaxf(m[i], t);
+                    const float ms = mn == -INFINITY ? 0.f : mn;
+                    l[i] = l[i] * __builtin_amdgcn_exp2f(m[i] - ms) + __builtin_amdgcn_exp2f(t - ms);
+                    m[i] = mn;
+                }
+            }
+#pragma unroll
+            for (int off = 16; off > 0; off >>= 1)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float mo = __shfl_xor(m[i], off, 64), lo = __shfl_xor(l[i], off, 64);
+                    const float mn = fmaxf(m[i], mo);
+                    const float ms = mn == -INFINITY ? 0.f : mn;
+                    l[i] = l[i] * __builtin_amdgcn_exp2f(m[i] - ms) + lo * __builtin_amdgcn_exp2f(mo - ms);
+                    m[i] = mn;
+                }
+            // l becomes the factor of the row (0: the row is written as zeros, for every kind), m its finite reference
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int qi = a.q0 + ql + 8 * (i >> 2) + 4 * h + (i & 3);
+                const bool zero = qi >= N || m[i] == -INFINITY;
+                l[i] = zero ? 0.f : inv_heads / l[i];
+                m[i] = zero ? 0.f : m[i];
+            }
+
+            // sweep 2: the scores again and G = dctx . v^T beside them, combined and stored
+            const int rows_left = a.nq - ql - 4 * h;        // row 8 (i >> 2) + (i & 3) of this half is inside the window
+            bf16x8 vf[4];
+            if (!VRES && nkt > 0) v_frags(0, vf);
+            for (int kt = 0; kt < nkt_out; ++kt) {
+                const int key = kt * 32 + l31;
+                const bool has_keys = kt < nkt;             // wave-uniform
+                f32x16 S = zero16(), G = zero16();
+                float kb = -INFINITY;
+                if (has_keys) {
+                    if (VRES) v_frags(kt, vf);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) S = Elem<bf16>::mfma(qf[s], row_frag(Kimg, kt * 32, s, lane), S);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) G = Elem<bf16>::mfma(df[s], vf[s], G);
+                    kb = kbias[key];
+                    if (!VRES && kt + 1 < nkt) v_frags(kt + 1, vf);     // in flight during this tile's stores
+                }
+                if (key < a.seq_len) {
+                    float* op = out + (size_t)(ql + 4 * h) * a.seq_len + key;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int r = 8 * (i >> 2) + (i & 3);
+                        if (r < rows_left) {
+                            float v = 0.f;
+                            if (kb == 0.f && l[i] != 0.f) {     // a key the definition gives a non-zero P, in a live row
+                                const float g = kind == VLMO_GRADCAM_CAM ? fmaxf(G[i], 0.f) : G[i];
+                                v = kind == VLMO_GRADCAM_GRAD ? g * inv_heads
+                                                              : __builtin_amdgcn_exp2f(S[i] * c2 - m[i]) * l[i] * g;
+                            }
+                            float* p = op + (size_t)r * a.seq_len;
+                            *p = hi ? *p + v : v;
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+int launch_gradcam(const GradcamArgs& a, int gx, int gy, hipStream_t st) {
+    static DeviceOnce once;
+    if (once.first()) {
+        (void)hipFuncSetAttribute((const void*)attn_gradcam_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  ATT_LDS_GRADCAM);
+        (void)hipFuncSetAttribute((const void*)attn_gradcam_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  ATT_LDS_PROBS);
+    }
+    const int npad = (a.seq_len + 31) / 32 * 32;
+    if (a.seq_len <= 512)
+        hipLaunchKernelGGL(attn_gradcam_kernel<true>, dim3(gx, gy), dim3(64 * ATT_PW), npad * 264, st, a, npad);
+    else
+        hipLaunchKernelGGL(attn_gradcam_kernel<false>, dim3(gx, gy), dim3(64 * ATT_PW), npad * 136, st, a, npad);
+    return 0;
+}
+
 int launch_fwd_long(const AttnArgs& a, int nblocks, hipStream_t st) {
     static DeviceOnce once;
     if (once.first())
@@ -1824,5 +2008,39 @@ extern "C" int vlmo_attn_probs(const void* qkv, const int32_t* seg, int num_seq,
     a.tiles_per_block = ATT_PW * ((rounds + gy - 1) / gy);
     launch_probs(a, gx, (rounds * ATT_PW + a.tiles_per_block - 1) / a.tiles_per_block, stream);
     VLMO_CHECK_LAUNCH("vlmo_attn_probs");
+    return 0;
+}
+
+extern "C" int vlmo_attn_gradcam(const void* qkv, const void* dctx, const int32_t* seg, int num_seq, const int32_t* keymask,
+                                 float* out, int heads, int d, int seq_len, int q0, int nq, int kind, int head_mean,
+                                 float scale, hipStream_t stream) {
+    if (int rc = check_common("vlmo_attn_gradcam", qkv, seg, num_seq, heads, d, seq_len, ATT_LMAX)) return rc;
+    VLMO_CHECK_ARG(dctx && out, "vlmo_attn_gradcam: null dctx or out");
+    VLMO_CHECK_ARG(q0 >= 0 && nq >= 1 && q0 <= seq_len - nq, "vlmo_attn_gradcam: query rows [%d, %d + %d) outside [0, %d)",
+                   q0, q0, nq, seq_len);
+    VLMO_CHECK_ARG(kind == VLMO_GRADCAM_CAM || kind == VLMO_GRADCAM_ATTN_GRAD || kind == VLMO_GRADCAM_GRAD,
+                   "vlmo_attn_gradcam: unknown kind %d", kind);
+    GradcamArgs a{};
+    a.qkv = (const bf16*)qkv;
+    a.dctx = (const bf16*)dctx;
+    a.seg = seg;
+    a.keymask = keymask;
+    a.out = out;
+    a.heads = heads;
+    a.d = d;
+    a.seq_len = seq_len;
+    a.q0 = q0;
+    a.nq = nq;
+    a.kind = kind;
+    a.head_mean = head_mean != 0;
+    a.scale_log2e = scale * LOG2E;
+    // the split of vlmo_attn_probs: one query tile per wave and round, more workgroups per (sequence, head) only while
+    // the chip has room for them
+    const int gx = num_seq * (a.head_mean ? 1 : heads);
+    const int rounds = ((nq + 31) / 32 + ATT_PW - 1) / ATT_PW;
+    const int gy = std::min(rounds, std::max(1, (768 + gx - 1) / gx));
+    a.tiles_per_block = ATT_PW * ((rounds + gy - 1) / gy);
+    launch_gradcam(a, gx, (rounds * ATT_PW + a.tiles_per_block - 1) / a.tiles_per_block, stream);
+    VLMO_CHECK_LAUNCH("vlmo_attn_gradcam");
     return 0;
 }

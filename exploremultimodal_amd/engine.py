@@ -196,6 +196,9 @@ class BlockMeta:
         self.seed = seed
         self.shadows = None
         self.tile = DEFAULT_TILE
+        # opt-in: capture(qkv, dctx, plan, fused), run by StackFn.backward after vlmo_stack_bwd on the same stream with
+        # views of this block's saved bf16 qkv rows [M, 3d] and of its bf16 dctx [M, d] (see _run_captures)
+        self.capture = None
 
 
 _SIDE = {}
@@ -769,6 +772,27 @@ def _hand_to_sink(sink, groups, spans, grads_all, evs):
         sink.release_all([g.params for g in groups[i]], ready_event=evs[i] if evs is not None else None)
 
 
+def _run_captures(metas, SB, sc, M, d):
+    """BlockMeta.capture of the blocks that asked for one, after vlmo_stack_bwd: views (no copy) of the block's saved qkv
+    rows in the forward slab SB and of its dctx in the rotating temporaries.  Nothing in a block's backward writes
+    dy2 = dctx after the attention backward has read it (block.hip: the fc2 backward writes dy2, the LayerNorm backward
+    reads it, the proj backward overwrites it with dctx), so the set of the k-th processed block holds its dctx until
+    block k + nsets takes the set: a captured block must be among the last nsets processed -- a one-block StackFn always
+    is, which is how VLMO.attention_gradcam runs the layers it is asked for."""
+    nb, md = len(metas), M * d
+    for k in range(nb):
+        i = nb - 1 - k
+        if metas[i].capture is None:
+            continue
+        if k + sc.nsets < nb:
+            raise RuntimeError(f'the backward temporaries of block {i} of this {nb}-block stack were reused before its '
+                               f'capture could run ({sc.nsets} sets rotate): run a captured block as a one-block StackFn')
+        qkv = SB[(i * 16 + 1) * md:(i * 16 + 4) * md].view(M, 3 * d)
+        st_ = k % sc.nsets
+        dctx = sc.tb[(st_ * 11 + 5) * md:(st_ * 11 + 6) * md].view(M, d)
+        metas[i].capture(qkv, dctx, metas[i].plan, metas[i].fused)
+
+
 class StackFn(torch.autograd.Function):
     """All Blocks of one backbone pass (the loops at vlmo.py:402-411) as ONE native call per direction
     (vlmo_stack_fwd / vlmo_stack_bwd).  metas: one BlockMeta per block, in forward order; params: the blocks'
@@ -887,6 +911,8 @@ class StackFn(torch.autograd.Function):
             arr = (ctypes.c_void_p * nb)(*evs)
             S.grad_ready = ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p))
         hip.stack_bwd(S)
+        if any(mt.capture is not None for mt in metas):
+            _run_captures(metas, ctx.keep[0], sc, M, d)
         ctx.descs = ctx.keep = None
         if sink is not None:
             _hand_to_sink(sink, groups, spans, grads_all, evs)

@@ -104,6 +104,7 @@ _SIGS = {
     'vlmo_attn_bwd': [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _f32,
                       _u32, _f32, _u64, _i32, _vp],
     'vlmo_attn_probs': [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
+    'vlmo_attn_gradcam': [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
     'vlmo_resid_bwd': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _u32, _f32, _u64, _vp, _i64, _vp],
     'vlmo_colsum': [_i32, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _vp],
     'vlmo_cast_weight': [_i32, _vp, _i32, _i32, _vp, _vp, _vp],
@@ -166,7 +167,7 @@ _SIGS = {
 }
 
 _lib = None
-ABI_VERSION = 11     # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
+ABI_VERSION = 12     # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
 
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is missing."""
@@ -351,6 +352,17 @@ def attn_probs(qkv, seg, nseq, keymask, probs, heads, d, seq_len, q0, nq, head_m
     rc = lib().vlmo_attn_probs(_p(qkv), _p(seg), nseq, _p(keymask), _p(probs), heads, d, seq_len, q0, nq,
                                int(bool(head_mean)), scale, _stream())
     _check(rc, 'vlmo_attn_probs')
+
+
+GRADCAM_KINDS = {'cam': 0, 'attn_grad': 1, 'grad': 2}      # VLMO_GRADCAM_* of the header
+
+
+def attn_gradcam(qkv, dctx, seg, nseq, keymask, out, heads, d, seq_len, q0, nq, kind, head_mean, scale):
+    """out fp32 [nseq, 1 if head_mean else heads, nq, seq_len]: P * max(G, 0) ('cam'), P * G ('attn_grad') or G ('grad')
+    with P of attn_probs and G = dctx v^T per head; kind is a key of GRADCAM_KINDS or its number."""
+    rc = lib().vlmo_attn_gradcam(_p(qkv), _p(dctx), _p(seg), nseq, _p(keymask), _p(out), heads, d, seq_len, q0, nq,
+                                 GRADCAM_KINDS.get(kind, kind), int(bool(head_mean)), scale, _stream())
+    _check(rc, 'vlmo_attn_gradcam')
 
 
 def resid_bwd(dx, zd, gamma, row_scale, dz, dgamma, dbias, M, d, drop=(0, 1.0), seed=0, row_index=None):

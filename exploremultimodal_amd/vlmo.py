@@ -345,7 +345,8 @@ class VLMO(nn.Module):
         ``torch.autograd.graph.increment_version``)."""
         self._shadows.clear()
 
-    def _run_blocks(self, x, plan, mode, fusion_layer, layers, seed):
+    def _run_blocks(self, x, plan, mode, fusion_layer, layers, seed, capture=None):
+        """capture: {layer: engine.BlockMeta.capture callback} for the backward of these blocks (attention_gradcam)."""
         layers = list(layers)
         todo = [(i,) + tuple(self._routes(i, mode, fusion_layer, plan)) for i in layers]
         # drop-path draws of ALL blocks in three tiny kernels instead of three per block (each one is a launch
@@ -361,12 +362,14 @@ class VLMO(nn.Module):
             # fused / single-stream blocks: both streams of a sample share the draw of the stream that exists
             u = torch.where(sd.unsqueeze(-1) > 0, u[:, :, first:first + 1].expand_as(u), u)
             scales = (u < kd).to(torch.float32) / kd
-        if engine.USE_STACK and todo:
+        if (engine.USE_STACK or capture) and todo:
             # the whole stack in ONE native call per direction (engine.StackFn)
             metas, params = [], []
             for n, (i, routes, ranges, fused) in enumerate(todo):
                 mt, ps = self.blocks[i].meta(x, plan, routes, ranges, fused, self._shadows, seed + 1000 * (i + 1),
                                              drop_scales=scales[n] if scales is not None else None)
+                if capture:
+                    mt.capture = capture.get(i)
                 metas.append(mt)
                 params += ps
             return engine.StackFn.apply(x, metas, *params)
@@ -470,6 +473,18 @@ class VLMO(nn.Module):
         if self.training:
             raise RuntimeError('attention_maps needs eval mode: the maps are pre-dropout and are computed from the '
                                'activations of a deterministic pass (call model.eval() first)')
+        plan, mode, fl, layers = self._map_plan(img, txt, img_attn_masks, txt_attn_masks, layers, fusion_layer, queries)
+        x = self._embed(plan, img, txt, bool_masked_pos, img_token_type_idx, 0)
+        maps, done = {}, 0
+        for i in layers:
+            x = self._run_blocks(x, plan, mode, fl, range(done, i), 0)
+            done = i
+            fused = self._routes(i, mode, fl, plan)[2]
+            maps[i] = attnmap.block_maps(self.blocks[i], x, plan, fused, self._shadows, queries, head_mean)
+        return maps
+
+    def _map_plan(self, img, txt, img_attn_masks, txt_attn_masks, layers, fusion_layer, queries):
+        """What attention_maps and attention_gradcam share: the checked inputs -> (plan, mode, fusion layer, sorted layers)."""
         dev = self._check_inputs(img, txt, img_attn_masks, txt_attn_masks)
         L = len(self.blocks)
         layers = list(range(L)) if layers is None else sorted(set(int(i) for i in layers))
@@ -487,14 +502,56 @@ class VLMO(nn.Module):
         if queries is not None and mode == 'vl' and any(i < fl for i in layers):
             raise ValueError(f'queries needs a single kind of sequence in every requested layer; layers below the fusion '
                              f'layer {fl} attend text and image separately')
-        x = self._embed(plan, img, txt, bool_masked_pos, img_token_type_idx, 0)
-        maps, done = {}, 0
-        for i in layers:
-            x = self._run_blocks(x, plan, mode, fl, range(done, i), 0)
-            done = i
-            fused = self._routes(i, mode, fl, plan)[2]
-            maps[i] = attnmap.block_maps(self.blocks[i], x, plan, fused, self._shadows, queries, head_mean)
-        return maps
+        return plan, mode, fl, layers
+
+    def attention_gradcam(self, score_fn, img=None, txt=None, img_attn_masks=None, txt_attn_masks=None, layers=None,
+                          fusion_layer=None, img_token_type_idx=1, queries=None, head_mean=False, kind='cam'):
+        """Gradient-weighted attention maps (Grad-CAM on ``attn``) of a forward_features pass -> {layer: map}, fp32.
+
+        score_fn(x, mask) gets what forward_features returns and gives a scalar tensor with a graph; with P the attention
+        map of a layer and G = d score / d P, kind 'cam' gives P * max(G, 0), 'attn_grad' P * G, 'grad' G (attnmap.py).
+        Shapes, ``layers``, ``queries`` and ``head_mean`` as attention_maps: per-modality dicts below the fusion layer of
+        an image-text pass, [B, heads | 1, nq, T + P] with the text first at a fused layer.
+
+        One forward and one backward of the pass (with the requested layers as one-block stacks, so that each one's
+        dctx is still in place when its map is taken) plus one kernel per requested layer and kind of sequence.  The
+        backward runs under torch.autograd.grad with the embedded input as the leaf: no parameter's .grad or
+        requires_grad changes, frozen models work, and the results carry no graph.
+
+        Eval mode only (RuntimeError otherwise): dropout would change both P and the meaning of dctx.  RuntimeError
+        while a gradient reducer is attached (nothing is handed to it)."""
+        if self.training:
+            raise RuntimeError('attention_gradcam needs eval mode: the maps are pre-dropout and are computed from the '
+                               'activations of a deterministic pass (call model.eval() first)')
+        if engine.GRAD_SINK is not None:
+            raise RuntimeError('attention_gradcam cannot run while a gradient reducer is attached: its backward pass '
+                               'would feed the reducer\'s buckets')
+        if kind not in attnmap.KINDS:
+            raise ValueError(f'kind must be one of {attnmap.KINDS}, got {kind!r}')
+        plan, mode, fl, layers = self._map_plan(img, txt, img_attn_masks, txt_attn_masks, layers, fusion_layer, queries)
+        L, maps = len(self.blocks), {}
+        with torch.no_grad():
+            leaf = self._embed(plan, img, txt, None, img_token_type_idx, 0)
+        leaf.requires_grad_(True)
+        with torch.enable_grad():
+            x, done = leaf, 0
+            for i in layers:
+                x = self._run_blocks(x, plan, mode, fl, range(done, i), 0)
+                cb = attnmap.gradcam_capture(self.blocks[i], maps, i, queries, head_mean, kind)
+                x = self._run_blocks(x, plan, mode, fl, [i], 0, capture={i: cb})
+                done = i + 1
+            x = self._run_blocks(x, plan, mode, fl, range(done, L), 0)
+            out = engine.FinalNormFn.apply(x, self.norm.weight, self.norm.bias, plan,
+                                           (plan.B, plan.T + plan.P, self.embed_dim), self.norm.eps)
+            mask = {'v': img_attn_masks, 'l': txt_attn_masks}.get(mode)
+            if mode == 'vl':
+                mask = torch.cat([txt_attn_masks, img_attn_masks], dim=1)
+            score = score_fn(out, mask)
+            if not torch.is_tensor(score) or score.dim() != 0 or not score.requires_grad:
+                raise ValueError('score_fn must return a scalar tensor that depends on the features it is given')
+            with engine.accumulate_into_grad(False):
+                torch.autograd.grad(score, leaf)
+        return {i: maps[i] for i in layers}
 
     def forward(self, img=None, txt=None, img_attn_masks=None, txt_attn_masks=None, fusion_layer=None,
                 img_token_type_idx=1):

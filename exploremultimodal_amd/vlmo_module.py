@@ -232,6 +232,43 @@ class VlmoModule(nn.Module):
                                           txt_attn_masks=txt_attn_masks, layers=layers, queries=queries,
                                           head_mean=head_mean)
 
+    def attention_gradcam(self, batch, infer_mode='img-txt', layers=None, target='itm', queries=None, head_mean=False,
+                          kind='cam'):
+        """Gradient-weighted attention maps of the backbone pass ``infer(batch, infer_mode)`` runs -> {layer: map}
+        (VLMO.attention_gradcam: kinds, shapes, eval mode only).  target='itm': the score is the "match" logit
+        itm_head(cls_feats)[:, 1], summed over the batch -- in eval mode nothing couples the samples, so every sample
+        gets the gradient of its own logit; needs 'itm' among the losses.  A callable target gets the dict infer returns
+        and gives a scalar tensor.  Masks and inputs are picked exactly as infer picks them."""
+        assert infer_mode in ['img_only', 'txt_only', 'img-txt']
+        if self.training:
+            raise RuntimeError('attention_gradcam needs eval mode: the maps are pre-dropout and are computed from the '
+                               'activations of a deterministic pass (call model.eval() first)')
+        if target == 'itm':
+            if 'itm' not in self.loss_names:
+                raise ValueError("target='itm' needs the ITM head: build the model with 'itm' in train.loss_names")
+        elif not callable(target):
+            raise ValueError(f"target must be 'itm' or a callable on the dict infer returns, got {target!r}")
+        transformer = self.transformer
+        img, img_attn_masks, txt_ids, txt_attn_masks = None, None, None, None
+        if 'img' in infer_mode:
+            img = batch['image_0'] if 'image_0' in batch else batch['image']
+            img_attn_masks = torch.ones([img.size(0), transformer.patch_embed.num_patches + 1], dtype=torch.int64,
+                                        device=img.device)
+        if 'txt' in infer_mode:
+            txt_ids, txt_attn_masks = batch['text_ids'], batch['text_mask']
+
+        def score_fn(co_feats, _):
+            T = transformer.max_text_len
+            txt_feats, img_feats = (co_feats[:, :T], co_feats[:, T:]) if txt_ids is not None else (None, co_feats)
+            out = {'txt_feats': txt_feats, 'img_feats': img_feats, 'co_feats': co_feats,
+                   'cls_feats': transformer.pooler(co_feats), 'img_masks': img_attn_masks, 'img_bool_masked_pos': None,
+                   'txt_labels': None, 'txt_ids': txt_ids, 'txt_masks': txt_attn_masks}
+            return self.itm_head(out['cls_feats'])[:, 1].sum() if target == 'itm' else target(out)
+
+        return transformer.attention_gradcam(score_fn, img=img, txt=txt_ids, img_attn_masks=img_attn_masks,
+                                             txt_attn_masks=txt_attn_masks, layers=layers, queries=queries,
+                                             head_mean=head_mean, kind=kind)
+
     # ------------------------------------------------- merged backbone passes
     @staticmethod
     def _split_infer(out, sizes):

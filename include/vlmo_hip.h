@@ -82,7 +82,7 @@ typedef struct VlmoEpilogue {
 const char* vlmo_last_error(void);
 /* Version of the struct layouts and signatures below; raised whenever one of them changes
  * (exploremultimodal_amd/hip.py mirrors it as ABI_VERSION and refuses any other). */
-#define VLMO_ABI_VERSION 11
+#define VLMO_ABI_VERSION 12
 int vlmo_abi_version(void);     /* = VLMO_ABI_VERSION of the header the library was built from */
 
 /* C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue.  tile: -1 = pick by shape, 0 = 128x128x64
@@ -200,6 +200,23 @@ int vlmo_attn_bwd(const void* qkv, const void* ctx, const void* dctx, const floa
  * q0 + nq > seq_len, num_seq < 1, null qkv / seg / probs. */
 int vlmo_attn_probs(const void* qkv, const int32_t* seg, int num_seq, const int32_t* keymask, float* probs,
                     int heads, int d, int seq_len, int q0, int nq, int head_mean, float scale, hipStream_t stream);
+
+/* Gradient-weighted attention maps (Grad-CAM on `attn`).  With P of vlmo_attn_probs taken as a free variable of
+ * ctx = P v, the gradient of a score with respect to P is G[i, j] = sum_c dctx[row_i, 64 h + c] * v[row_j, 64 h + c]
+ * per head (bf16 products, fp32 accumulation); dctx is the bf16 [M, d] gradient of the attention context on the packed
+ * rows, head-major like ctx.  kind selects what is written to out (fp32, the shape and window of vlmo_attn_probs):
+ *   VLMO_GRADCAM_CAM P * max(G, 0)    VLMO_GRADCAM_ATTN_GRAD P * G    VLMO_GRADCAM_GRAD G
+ * The zero rules of vlmo_attn_probs hold for every kind, GRAD included: a masked key, key columns and query rows past
+ * a sequence's length and a row whose keys are all masked are exactly 0.  head_mean: the mean over heads of the
+ * per-head output (of the products, not the product of the means), summed in head order: bitwise reproducible.
+ * Up to 512 tokens K and V of a head are resident in LDS; 513 - 1024 K is resident and V is streamed.  Read-only.
+ * Refused (negative status, nothing written): whatever vlmo_attn_probs refuses, a null dctx, an unknown kind. */
+#define VLMO_GRADCAM_CAM 0
+#define VLMO_GRADCAM_ATTN_GRAD 1
+#define VLMO_GRADCAM_GRAD 2
+int vlmo_attn_gradcam(const void* qkv, const void* dctx, const int32_t* seg, int num_seq, const int32_t* keymask,
+                      float* out, int heads, int d, int seq_len, int q0, int nq, int kind, int head_mean, float scale,
+                      hipStream_t stream);
 
 /* Residual-branch backward (vlmo.py:194-196): dz = dx * gamma * row_scale * dropmask/(1-p);
  * dgamma += sum_m dx * row_scale * zd;  dbias += sum_m dz. */
