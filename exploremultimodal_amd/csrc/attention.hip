@@ -7,8 +7,9 @@
 // several times).  Forward: attn_fwd1_kernel (one wave per query tile, key
 // tiles one at a time with a lazily rescaled running maximum; sequences of up
 // to 288 tokens) and attn_fwd_kernel (128-key chunks with an exact running
-// maximum; up to 512).  Backward: attn_bwd1_kernel (single pass, up to 256
-// tokens) and attn_bwd_kernel (two phases, up to 288).
+// maximum; up to 512).  Backward: attn_bwd1_kernel (single pass; up to 256
+// tokens as it is, 257 - 288 in its FRINGE form: eight full tiles + one
+// fringe tile).
 // Higher resolutions (384 / 480 px: 577 / 901 image tokens, up to 965 fused)
 // take the streaming kernels: attn_fwd_long_kernel for launches of 513 - 1024
 // tokens, attn_dkdv_long_kernel + attn_dq_long_kernel for 289 - 1024; K / V
@@ -440,246 +441,26 @@ __device__ __forceinline__ float half_wave_total(float v) {
     s_ += dpp_mov<0x142, 0xa, 0xf>(s_);                 // row_bcast15 into rows 1 and 3 -> lanes 31 / 63 = half totals
     return s_;
 }
-__device__ __forceinline__ void colsum_tiles(const f32x16* t, float w, float scale, float* acc, int lane) {
+__device__ __forceinline__ void colsum_tile(const f32x16& t, float w, float scale, float* acc, int lane) {
     const int h = lane >> 5;
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float v = half_wave_total(t[dt][r] * w);
-            if ((lane & 31) == 31) atomicAdd(acc + dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, v * scale);
-        }
+    for (int r = 0; r < 16; ++r) {
+        const float v = half_wave_total(t[r] * w);
+        if ((lane & 31) == 31) atomicAdd(acc + (r & 3) + 8 * (r >> 2) + 4 * h, v * scale);
+    }
 }
-
-__global__ __launch_bounds__(512, 2) void attn_bwd_kernel(const AttnArgs a, const int NPAD) {
-    const int IMG = NPAD * 128;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Qimg = smem;
-    char* Kimg = smem + IMG;
-    char* Vimg = smem + 2 * IMG;
-    char* Dimg = smem + 3 * IMG;
-    float* kbias = (float*)(smem + 4 * IMG);
-    float* lseq = kbias + NPAD;    // log2-domain LSE per query (+inf on padded queries)
-    float* delta = lseq + NPAD;
-    int* rowidx = (int*)(delta + NPAD);
-    int* next_item = rowidx + NPAD;
-    float* csum = (float*)(next_item + 4);      // [2][64]: column sums of dq | dv of this (sequence, head)
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bh = blockIdx.x, sidx = bh / a.heads, hd = bh % a.heads;
-    const int ld = 3 * a.d;
-    int N;
-    setup_rows(a.seg, sidx, a.keymask, NPAD, rowidx, kbias, N);
-    if (threadIdx.x == 0) *next_item = 0;
-    if (threadIdx.x < 128) csum[threadIdx.x] = 0.f;
-    __syncthreads();
-    const int nq = (N + 31) >> 5;   // query tiles == key tiles (self-attention)
-    stage_image<8>(a.qkv, ld, hd * 64, rowidx, Qimg, nq * 4, wave, lane);
-    stage_image<8>(a.qkv, ld, a.d + hd * 64, rowidx, Kimg, nq * 4, wave, lane);
-    stage_image<8>(a.qkv, ld, 2 * a.d + hd * 64, rowidx, Vimg, nq * 4, wave, lane);
-    stage_image<8>(a.dctx, a.d, hd * 64, rowidx, Dimg, nq * 4, wave, lane);
-    const float keep_prob = 1.f / a.inv_keep;
-    for (int i = threadIdx.x; i < NPAD; i += 512) {
-        float dl = 0.f, lq = INFINITY;
-        if (i < N) {
-            const size_t o = (size_t)rowidx[i] * a.d + hd * 64;
+__device__ __forceinline__ void colsum_tiles(const f32x16* t, float w, float scale, float* acc, int lane) {
 #pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const bf16x8 x = *(const bf16x8*)(a.ctx + o + 8 * c);
-                const bf16x8 y = *(const bf16x8*)(a.dctx + o + 8 * c);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) dl += (float)x[j] * (float)y[j];
-            }
-            lq = a.lse[(size_t)bh * a.lse_stride + i] * LOG2E;
-        }
-        delta[i] = dl * keep_prob;      // dS = scale * inv_keep * P * (keep * dP - delta / inv_keep): see below
-        lseq[i] = lq;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    const int l31 = lane & 31, h = lane >> 5;
-    const uint32_t akey = att_key(a.seed, bh + a.bh0);
-    // the constant factors of dS = P * (keep * dP * inv_keep - delta) * scale and Pd = keep * P * inv_keep are
-    // applied ONCE to the 32 accumulator values a lane owns, not to every score element
-    const float out_scale = a.scale * a.inv_keep;
-
-    // running column sums of the tiles this wave finishes (a.qvsum): one kind at a time -- items are handed out dK/dV
-    // first, then dQ, so a wave switches at most once -- reduced over the lanes when the kind changes and at the end
-    f32x16 cs[2] = {zero16(), zero16()};
-    int cs_kind = -1;
-    for (;;) {
-    int item = 0;
-    if (lane == 0) item = atomicAdd(next_item, 1);
-    item = __builtin_amdgcn_readfirstlane(item);
-    if (a.qvsum) {
-        const int kind = item >= 2 * nq ? -1 : (item >= nq ? 0 : 1);        // 0: dq sums, 1: dv sums
-        if (cs_kind >= 0 && kind != cs_kind) {
-            colsum_tiles(cs, 1.f, cs_kind == 0 ? out_scale : a.inv_keep, csum + 64 * cs_kind, lane);
-            cs[0] = zero16(), cs[1] = zero16();
-        }
-        cs_kind = kind;
-    }
-    if (item >= 2 * nq) break;
-    // ---- dQ item: dQ^T[d][q] = sum_k K^T[d][k] dS^T[k][q]
-    if (item >= nq) {
-        const int qt = item - nq;
-        const int qi = qt * 32 + l31;
-        bf16x8 qf[4], df[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            qf[s] = row_frag(Qimg, qt * 32, s, lane);
-            df[s] = row_frag(Dimg, qt * 32, s, lane);
-        }
-        const float lq = lseq[qi], dl = delta[qi];
-        const uint32_t rq = ((uint32_t)qi * 512u + 4u * h) * ATT_G + akey;
-        f32x16 dQ[2] = {zero16(), zero16()};
-        for (int kt = 0; kt < nq; ++kt) {
-            {
-                f32x16 S = zero16(), dP = zero16();
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    S = Elem<bf16>::mfma(row_frag(Kimg, kt * 32, s, lane), qf[s], S);
-                    dP = Elem<bf16>::mfma(row_frag(Vimg, kt * 32, s, lane), df[s], dP);
-                }
-                const uint32_t rk = rq + (uint32_t)(kt * 32) * ATT_G;
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    const f32x4 kb = *(const f32x4*)(kbias + kt * 32 + 8 * g4 + 4 * h);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int i = 4 * g4 + e;
-                        const float p = __builtin_amdgcn_exp2f(S[i] * a.scale_log2e + (kb[e] - lq));
-                        bool keep = true;
-                        if (a.drop_thresh) keep = att_mix(rk + (uint32_t)(8 * g4 + e) * ATT_G) >= a.drop_cmp;
-                        const float dp = keep ? dP[i] : 0.f;
-                        S[i] = p * (dp - dl);
-                    }
-                }
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    bf16x8 sf;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) sf[j] = (bf16)S[8 * s2 + j];
-#pragma unroll
-                    for (int dt = 0; dt < 2; ++dt)
-                        dQ[dt] = Elem<bf16>::mfma(tr_frag(Kimg, kt * 32 + 16 * s2, dt * 32, lane), sf, dQ[dt]);
-                }
-            }
-        }
-        if (a.qvsum) {
-            const float wq = qi < N ? 1.f : 0.f;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) cs[dt][r] = fmaf(dQ[dt][r], wq, cs[dt][r]);
-        }
-        if (qi < N) {
-            bf16* op = a.out + (size_t)rowidx[qi] * ld + hd * 64 + 4 * h;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    bf16x4 o = {(bf16)(dQ[dt][4 * g4 + 0] * out_scale), (bf16)(dQ[dt][4 * g4 + 1] * out_scale),
-                                (bf16)(dQ[dt][4 * g4 + 2] * out_scale), (bf16)(dQ[dt][4 * g4 + 3] * out_scale)};
-                    *(bf16x4*)(op + dt * 32 + 8 * g4) = o;
-                }
-        }
-    }
-
-    // ---- dK/dV item: dV^T[d][k] = sum_q dO^T[d][q] Pd[q][k] ; dK^T[d][k] = sum_q Q^T[d][q] dS[q][k]
-    else {
-        const int kt = item;
-        const int ki = kt * 32 + l31;
-        bf16x8 kf[4], vf[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            kf[s] = row_frag(Kimg, kt * 32, s, lane);
-            vf[s] = row_frag(Vimg, kt * 32, s, lane);
-        }
-        const float kb = kbias[ki];
-        // dropout counter of (q, ki) = q * 512 + ki: affine in q, so a lane walks its 16 queries of a tile with
-        // compile-time constant adds
-        const uint32_t rl = (uint32_t)ki * ATT_G + akey + (uint32_t)(4 * h) * ATT_G512;
-        f32x16 dK[2] = {zero16(), zero16()}, dV[2] = {zero16(), zero16()};
-        for (int qt = 0; qt < nq; ++qt) {
-            {
-                f32x16 S = zero16(), dP = zero16();
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    S = Elem<bf16>::mfma(row_frag(Qimg, qt * 32, s, lane), kf[s], S);
-                    dP = Elem<bf16>::mfma(row_frag(Dimg, qt * 32, s, lane), vf[s], dP);
-                }
-                f32x16 Pd;
-                const uint32_t rqt = rl + (uint32_t)(qt * 32) * ATT_G512;
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    const int q0 = qt * 32 + 8 * g4 + 4 * h;
-                    const f32x4 lq = *(const f32x4*)(lseq + q0);
-                    const f32x4 dl = *(const f32x4*)(delta + q0);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int i = 4 * g4 + e;
-                        const float p = __builtin_amdgcn_exp2f(S[i] * a.scale_log2e + (kb - lq[e]));
-                        bool keep = true;
-                        if (a.drop_thresh) keep = att_mix(rqt + (uint32_t)(8 * g4 + e) * ATT_G512) >= a.drop_cmp;
-                        Pd[i] = keep ? p : 0.f;
-                        S[i] = p * ((keep ? dP[i] : 0.f) - dl[e]);
-                    }
-                }
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    bf16x8 pf, sf;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        pf[j] = (bf16)Pd[8 * s2 + j];
-                        sf[j] = (bf16)S[8 * s2 + j];
-                    }
-#pragma unroll
-                    for (int dt = 0; dt < 2; ++dt) {
-                        dV[dt] = Elem<bf16>::mfma(tr_frag(Dimg, qt * 32 + 16 * s2, dt * 32, lane), pf, dV[dt]);
-                        dK[dt] = Elem<bf16>::mfma(tr_frag(Qimg, qt * 32 + 16 * s2, dt * 32, lane), sf, dK[dt]);
-                    }
-                }
-            }
-        }
-        if (a.qvsum) {
-            const float wk = ki < N ? 1.f : 0.f;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) cs[dt][r] = fmaf(dV[dt][r], wk, cs[dt][r]);
-        }
-        if (ki < N) {
-            bf16* op = a.out + (size_t)rowidx[ki] * ld + hd * 64 + 4 * h;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    bf16x4 ok = {(bf16)(dK[dt][4 * g4 + 0] * out_scale), (bf16)(dK[dt][4 * g4 + 1] * out_scale),
-                                 (bf16)(dK[dt][4 * g4 + 2] * out_scale), (bf16)(dK[dt][4 * g4 + 3] * out_scale)};
-                    bf16x4 ov = {(bf16)(dV[dt][4 * g4 + 0] * a.inv_keep), (bf16)(dV[dt][4 * g4 + 1] * a.inv_keep),
-                                 (bf16)(dV[dt][4 * g4 + 2] * a.inv_keep), (bf16)(dV[dt][4 * g4 + 3] * a.inv_keep)};
-                    *(bf16x4*)(op + a.d + dt * 32 + 8 * g4) = ok;
-                    *(bf16x4*)(op + 2 * a.d + dt * 32 + 8 * g4) = ov;
-                }
-        }
-    }
-    }
-    if (a.qvsum) {
-        __syncthreads();
-        if (threadIdx.x < 128)
-            a.qvsum[(size_t)sidx * 2 * a.d + (threadIdx.x >> 6) * a.d + hd * 64 + (threadIdx.x & 63)] = csum[threadIdx.x];
-    }
+    for (int dt = 0; dt < 2; ++dt) colsum_tile(t[dt], w, scale, acc + dt * 32, lane);
 }
 
 // ------------------------------------------------------------------ backward, single pass
 // One workgroup = one (sequence, head); wave w OWNS key tile w (32 keys: its K / V row fragments, dK^T and dV^T
 // accumulators) AND the dQ^T accumulators of query tile w.  The nq x nq tile pairs are swept along the diagonals of a
 // rotation: in step t wave w works on (query tile (w + t) mod nq, key tile w), so S, dP, P and dS of every pair are
-// computed exactly ONCE (the two-phase kernel above computes them in the dK/dV items and again in the dQ items: 28
-// MFMAs and two passes of soft-max / dropout arithmetic per pair instead of 20 and one).  With the key on the lane
+// computed exactly ONCE (the two-phase kernel this one replaced, one item per key tile and one per query tile handed
+// out to the waves, computed them in the dK/dV items and again in the dQ items: 28 MFMAs and two passes of soft-max /
+// dropout arithmetic per pair instead of 20 and one; DESIGN.md section 5 keeps its numbers).  With the key on the lane
 // (S = Q . K^T, rows = queries) the accumulator tiles P and dS are directly the B operands of dV^T += dO^T . P and
 // dK^T += Q^T . dS; only dS crosses LDS, once: the wave stores its bf16 tile [key][query] into its slot and, after the
 // step's barrier, the owner of that query tile reads it back transposed (ds_read_b64_tr_b16) as the B operand of
@@ -695,12 +476,23 @@ __device__ __forceinline__ int slot_off(int k, int q) {
 // One wave per key tile, at most 8 (two per SIMD, 251 registers): a ninth wave would put three on one SIMD, i.e. a
 // 168-register budget against 96 accumulator registers + V fragments + the S / dP tiles -- hipcc spills 160-330
 // registers there and the N = 261 backward takes 200-450 us instead of 120.  Sequences of 257-288 tokens (the fused
-// layers at T = 64) therefore stay on the two-phase kernel above.
+// layers at T = 64: 261) take the FRINGE instantiation instead: eight waves, the rotation over the eight full tiles as
+// it is, then the 17 pairs that touch the ninth tile in two more steps whose extra accumulators replace dead values:
+//   A  (fringe queries, key tile w) into the wave's own dK / dV, which are then final and stored; dS^T stays in the
+//      wave's slot of ring buffer 0
+//   B  (query tile w, fringe keys) into the wave's own dQ through its slot of buffer 1 (wave-local), and into PARTIAL
+//      dK / dV of the fringe keys in the registers step A freed; wave 0 takes (fringe, fringe) as well
+//   fringe dQ: waves 4 and 5, one 32-feature half each, from the nine dS^T slots of buffer 0 and the K image, key tiles
+//      in order; fringe dK / dV: the eight partials summed through LDS (over the dead Q / dO images) in a fixed tree.
+// Every sum has a fixed order: dq / dk / dv are bitwise reproducible in both forms.  Sequences of <= 256 tokens in a
+// FRINGE launch run the rotation only.  LDS at 288 padded tokens: images 3 x 36 KB, 2 x 9 slots, row constants, column
+// sums, the 4 KB V image of the fringe keys = 155 520 bytes.  The template keeps the <= 256-token kernel as it was.
 // Measured (MI355X, B = 64, 12 heads, dropout 0.1; tools/attn_bench.py): N = 197 78 us (two-phase 94), N = 64 16 us (25).
 // Per workgroup at N = 197 (s_memrealtime stamps): 7 us before the first product (165 KB through one CU's vector
 // memory path at ~25 GB/s: images + V fragments + the ctx / dctx rows for delta), 13 us in the loop (1.9 us per step:
 // the two waves of a SIMD spend it in ~180 + ~180 soft-max / dropout instructions, SQ_ACTIVE_INST_VALU is what bounds
 // it, the 40 MFMAs of both hide under it), 2-3 us of stores; one workgroup per CU, so the three phases add.
+template <bool FRINGE>
 __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const int NPAD) {
     constexpr bool KF_REG = false;      // K row fragments re-read from the LDS image each step (16 registers: no spill)
     const int IMG = NPAD * 128;
@@ -714,7 +506,7 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
     float* nlq = kbias + NPAD;      // -lse / scale per query (-inf on padded queries)
     float* ndl = nlq + NPAD;        // -delta * keep_prob
     float* csum = ndl + NPAD;       // [2][64]: column sums of dq | dv of this (sequence, head)
-
+    char* V8img = (char*)(csum + 128);                      // FRINGE: V of the fringe keys, one 4 KB tile
 
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -727,11 +519,12 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
     // global round trips and a barrier: 6.4 of the 7.2 us a workgroup spent before its first product).
     const int rowA = a.seg[4 * sidx + 0], lenA = a.seg[4 * sidx + 1], rowB = a.seg[4 * sidx + 2], lenB = a.seg[4 * sidx + 3];
     const int N = lenA + lenB;
-    auto rowof = [&](int tok) {
+    auto rowof = [&](int tok) __attribute__((always_inline)) {
         tok = min(tok, N - 1);
         return tok < lenA ? rowA + tok : rowB + (tok - lenA);
     };
     const int nq = (N + 31) >> 5;
+    const int nc = FRINGE ? min(nq, 8) : nq;        // tiles of the rotation = waves at work
     for (int ii = w; ii < nq * 4; ii += nw) {
         const int chhi = lane >> 5, rowlo = (lane >> 2) & 7, pc = lane & 3;
         const int row = ii * 8 + rowlo;
@@ -741,8 +534,14 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
         glds16(a.qkv + r * ld + a.d + hd * 64 + ch * 8, Kimg + ii * 1024);
         glds16(a.dctx + r * a.d + hd * 64 + ch * 8, Dimg + ii * 1024);
     }
+    if (FRINGE && nq > 8 && w >= 4) {       // waves 0-3 staged five rows of instructions above, these four
+        const int chhi = lane >> 5, rowlo = (lane >> 2) & 7, pc = lane & 3;
+        const int row = 256 + (w - 4) * 8 + rowlo;
+        const int ch = chhi * 4 + (pc ^ ((row >> 2) & 3));
+        glds16(a.qkv + (size_t)rowof(row) * ld + 2 * a.d + hd * 64 + ch * 8, V8img + (w - 4) * 1024);
+    }
     const int l31 = lane & 31, h = lane >> 5;
-    const bool active = w < nq;
+    const bool active = w < nc;
     const int ki = w * 32 + l31;
     const int krow = rowof(ki);
     // row fragments (B operands) of this wave's keys straight from global memory: V has no LDS image at all
@@ -786,9 +585,10 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
     const uint32_t akey = att_key(a.seed, bh + a.bh0);
     const float out_scale = a.scale * a.inv_keep;
     const float c_l2 = a.scale_log2e;
-    const float kb = kbias[min(ki, NPAD - 1)];
-    // dropout counter of (q, ki) = q * 512 + ki: affine in q (see attn_bwd_kernel)
-    const uint32_t rl = (uint32_t)ki * ATT_G + akey + (uint32_t)(4 * h) * ATT_G512;
+    const float kb_own = kbias[min(ki, NPAD - 1)];
+    // dropout counter of (q, ki) = q * 512 + ki: affine in q, so a lane walks its 16 queries of a tile with
+    // compile-time constant adds
+    const uint32_t rl_own = (uint32_t)ki * ATT_G + akey + (uint32_t)(4 * h) * ATT_G512;
     f32x16 dK[2] = {zero16(), zero16()}, dV[2] = {zero16(), zero16()}, dQ[2] = {zero16(), zero16()};
 
     // LDS addressing with FOUR per-lane offsets for all image accesses (att_off spelled out for tile-aligned bases: the
@@ -802,10 +602,14 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
     const int tg = (lane >> 4) & 1, tq = (lane >> 2) & 3, tp = lane & 3;
     const int trl = 64 * (4 * h + tq) + 16 * ((2 * tg + (tp >> 1)) ^ h) + 8 * (tp & 1);
     const int trh = 1024 + 64 * (4 * h + tq) + 16 * ((2 * tg + (tp >> 1)) ^ ((2 + h) & 3)) + 8 * (tp & 1);
-    auto rfrag = [&](const char* img_rb, int s) -> bf16x8 {     // img_rb = image + 128 * row base (wave-uniform)
+    // (The lambdas of this kernel are always_inline: the FRINGE form calls the stages from five places, and left as
+    // functions they take the accumulator arrays through scratch memory.)
+    // img_rb = image + 128 * row base (wave-uniform)
+    auto rfrag = [&](const char* img_rb, int s) __attribute__((always_inline)) -> bf16x8 {
         return *(const bf16x8*)(img_rb + 512 * (s >> 1) + ((s & 1) ? rf1 : rf0));
     };
-    auto tfrag = [&](const char* img_rb, int dt) -> bf16x8 {    // img_rb = image + 128 * (row base of the 16-row k-step)
+    // img_rb = image + 128 * (row base of the 16-row k-step)
+    auto tfrag = [&](const char* img_rb, int dt) __attribute__((always_inline)) -> bf16x8 {
         const bf16x4 lo = lds_tr4<bf16>(img_rb + 512 * dt + trl);
         const bf16x4 hi = lds_tr4<bf16>(img_rb + 512 * dt + trh);
         return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -813,7 +617,7 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
     // slot tile [key][query] (slot_off): the producer's two 8-byte stores per k-step, the consumer's transposed reads
     const int sw0 = slot_off(l31, 4 * h), sw1 = slot_off(l31, 8 + 4 * h);           // k-step 1: + 32 bytes XOR-wise
     const int srl = slot_off(4 * h + tq, 16 * tg + 4 * tp), srh = slot_off(8 + 4 * h + tq, 16 * tg + 4 * tp);
-    auto sfrag = [&](const char* slot, int s2) -> bf16x8 {
+    auto sfrag = [&](const char* slot, int s2) __attribute__((always_inline)) -> bf16x8 {
         const bf16x4 lo = lds_tr4<bf16>(slot + 1024 * s2 + srl);
         const bf16x4 hi = lds_tr4<bf16>(slot + 1024 * s2 + srh);
         return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -835,18 +639,19 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
     // Legal because dq(t-1) only needs barrier t-1 behind it and the slot buffer it reads is rewritten after barrier t.
     bf16x8 qa[4], da[4], pf[2], sf[2];
     f32x16 S, dP;
-    auto fetch_a = [&](int qt_) {
+    auto fetch_a = [&](int qt_) __attribute__((always_inline)) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             qa[s] = rfrag(Qimg + qt_ * 4096, s);
             da[s] = rfrag(Dimg + qt_ * 4096, s);
         }
     };
-    auto qtile = [&](int t_) {
+    auto qtile = [&](int t_) __attribute__((always_inline)) {
         int q_ = w + t_;
-        return q_ >= nq ? q_ - nq : q_;
+        return q_ >= nc ? q_ - nc : q_;
     };
-    auto stage_sdp = [&](int qt) {      // qa / da hold the fragments of query tile qt
+    // qa / da hold the fragments of query tile qt; ktile = the K image of the key tile, vfr its V row fragments
+    auto stage_sdp = [&](int qt, const char* ktile, const bf16x8 (&vfr)[4]) __attribute__((always_inline)) {
         // the row constant -lse / scale as the initial accumulator of S (dP starts at zero: its row constant -delta
         // is needed as a value by the dropout select anyway, and a second set of initial registers spills)
         dP = zero16();
@@ -858,13 +663,15 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const bf16x8 kfs = KF_REG ? kf[s] : rfrag(Kimg + w * 4096, s);
+            const bf16x8 kfs = KF_REG ? kf[s] : rfrag(ktile, s);
             S = Elem<bf16>::mfma(qa[s], kfs, S);
-            dP = Elem<bf16>::mfma(da[s], vf[s], dP);
+            dP = Elem<bf16>::mfma(da[s], vfr[s], dP);
         }
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto stage_valu_dvdk = [&](int qt, int t) {
+    // kb / rl: key bias and dropout counter base of the lane's key; dV / dK: the accumulators of that key tile
+    auto stage_valu_dvdk = [&](int qt, char* myslot, float kb, uint32_t rl, f32x16 (&dV)[2],
+                               f32x16 (&dK)[2]) __attribute__((always_inline)) {
         bf16x8 dtr[2], qtr[2];
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
@@ -902,7 +709,6 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
                 }
             }
         }
-        char* myslot = slots + ((t & 1) * nt + w) * 2048;
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             // dS^T tile for the owner of this query tile: registers 4g .. 4g+3 = queries 8g + 4h .. +3 of key l31
@@ -931,16 +737,13 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
     };
     // dq(t): the wave that worked on query tile w in step t owns key tile wp = (w - t) mod nq.  next_q >= 0: also fetch
     // the row fragments of that query tile (the following sdp stage) under these products
-    auto stage_dq = [&](int t, int next_q) {
-        int wp = w - t;
-        if (wp < 0) wp += nq;
-        const char* slot = slots + ((t & 1) * nt + wp) * 2048;
+    auto stage_dq_at = [&](const char* slot, const char* ktile, int next_q) __attribute__((always_inline)) {
         bf16x8 ktr[2][2], sb[2];
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             sb[s2] = sfrag(slot, s2);
 #pragma unroll
-            for (int dt = 0; dt < 2; ++dt) ktr[s2][dt] = tfrag(Kimg + wp * 4096 + 2048 * s2, dt);
+            for (int dt = 0; dt < 2; ++dt) ktr[s2][dt] = tfrag(ktile + 2048 * s2, dt);
         }
         if (next_q >= 0) fetch_a(next_q);
         __builtin_amdgcn_sched_barrier(0);
@@ -950,35 +753,148 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
             for (int dt = 0; dt < 2; ++dt) dQ[dt] = Elem<bf16>::mfma(ktr[s2][dt], sb[s2], dQ[dt]);
         __builtin_amdgcn_sched_barrier(0);
     };
+    auto stage_dq = [&](int t, int next_q) __attribute__((always_inline)) {
+        int wp = w - t;
+        if (wp < 0) wp += nc;
+        stage_dq_at(slots + ((t & 1) * nt + wp) * 2048, Kimg + wp * 4096, next_q);
+    };
+    const char* kown = Kimg + w * 4096;
+    auto core_sdp = [&](int qt) __attribute__((always_inline)) { stage_sdp(qt, kown, vf); };
+    auto core_valu_dvdk = [&](int qt, int t) __attribute__((always_inline)) {
+        stage_valu_dvdk(qt, slots + ((t & 1) * nt + w) * 2048, kb_own, rl_own, dV, dK);
+    };
     // VALU issue is arbitrated by priority, then age: left alone the younger wave of a SIMD (w >= 4) gets the leftovers of
     // the older one's arithmetic stage and every barrier waits for it (interval 3 900 -> 3 540 cycles with this)
     if (w >= 4) __builtin_amdgcn_s_setprio(1);
     if (!active) {
-        for (int t = 0; t < nq; ++t) __syncthreads();
+        for (int t = 0; t < nc; ++t) __syncthreads();
     } else if (w < 4) {
         fetch_a(w);
-        for (int t = 0; t < nq; ++t) {
+        for (int t = 0; t < nc; ++t) {
             const int qt = qtile(t);
-            stage_sdp(qt);
-            stage_valu_dvdk(qt, t);
+            core_sdp(qt);
+            core_valu_dvdk(qt, t);
             __syncthreads();
-            stage_dq(t, t + 1 < nq ? qtile(t + 1) : -1);
+            stage_dq(t, t + 1 < nc ? qtile(t + 1) : -1);
         }
     } else {
         fetch_a(w);
-        stage_sdp(w);
-        for (int t = 0; t < nq; ++t) {
-            stage_valu_dvdk(qtile(t), t);
+        core_sdp(w);
+        for (int t = 0; t < nc; ++t) {
+            core_valu_dvdk(qtile(t), t);
             if (t > 0) stage_dq(t - 1, -1);
-            if (t + 1 < nq) {
+            if (t + 1 < nc) {
                 fetch_a(qtile(t + 1));
-                stage_sdp(qtile(t + 1));
+                core_sdp(qtile(t + 1));
             }
             __syncthreads();
         }
-        stage_dq(nq - 1, -1);
+        stage_dq(nc - 1, -1);
     }
-    if (active && ki < N) {
+    if (FRINGE && nq > 8) {
+        // Nine tiles: the rotation above covered the 8 x 8 core pairs with all eight waves; the 17 pairs that touch the
+        // fringe tile (tokens 256 ..) follow in two more steps, every pair still computed once.
+        // A tile of 32 tokens x 64 features, scaled, to columns col0 .. col0 + 63 of dqkv row `row`
+        auto store_tile = [&](const f32x16 (&t)[2], float sc, int row, int col0) __attribute__((always_inline)) {
+            bf16* op = a.out + (size_t)row * ld + col0 + hd * 64 + 4 * h;
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4)
+                    *(bf16x4*)(op + dt * 32 + 8 * g4) =
+                        bf16x4{(bf16)(t[dt][4 * g4 + 0] * sc), (bf16)(t[dt][4 * g4 + 1] * sc),
+                               (bf16)(t[dt][4 * g4 + 2] * sc), (bf16)(t[dt][4 * g4 + 3] * sc)};
+        };
+        // ---- step A: (fringe queries, key tile w).  dS^T stays in slot w of ring buffer 0 (free since the last core
+        // barrier) for the dQ of the fringe queries below.  dK / dV of key tile w are then final: out they go.
+        fetch_a(8);
+        stage_sdp(8, kown, vf);
+        stage_valu_dvdk(8, slots + w * 2048, kb_own, rl_own, dV, dK);
+        store_tile(dK, out_scale, krow, a.d);
+        store_tile(dV, a.inv_keep, krow, 2 * a.d);
+        if (a.qvsum) colsum_tiles(dV, 1.f, a.inv_keep, csum + 64, lane);
+        dK[0] = zero16(), dK[1] = zero16(), dV[0] = zero16(), dV[1] = zero16();
+        __syncthreads();        // ring buffer 1 has been read by the last core dq stage of every wave
+        // ---- step B: (query tile w, fringe keys).  dK / dV now hold this wave's PARTIAL sums of the fringe keys; dS^T
+        // goes through the wave's own slot of buffer 1 into its dQ (wave-local: LDS executes a wave's accesses in order).
+        const int k8 = 256 + l31;
+        const char* k8tile = Kimg + 8 * 4096;
+        const float kb8 = kbias[k8];
+        const uint32_t rl8 = (uint32_t)k8 * ATT_G + akey + (uint32_t)(4 * h) * ATT_G512;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) vf[s] = rfrag(V8img, s);
+        char* slot1 = slots + (nt + w) * 2048;
+        fetch_a(w);
+        stage_sdp(w, k8tile, vf);
+        stage_valu_dvdk(w, slot1, kb8, rl8, dV, dK);
+        stage_dq_at(slot1, k8tile, w == 0 ? 8 : -1);
+        if (w == 0) {           // the pair (fringe, fringe): its dS^T into the ninth slot of buffer 0
+            stage_sdp(8, k8tile, vf);
+            stage_valu_dvdk(8, slots + 8 * 2048, kb8, rl8, dV, dK);
+        }
+        store_tile(dQ, out_scale, krow, 0);
+        if (a.qvsum) colsum_tiles(dQ, 1.f, out_scale, csum, lane);
+        __syncthreads();        // the Q and dO images are dead, buffer 0 holds dS^T of all nine (fringe query, key tile) pairs
+        // ---- the fringe rows.  dK / dV: eight partial tiles summed through LDS in a fixed tree, ((0+4)+(1+5))+(2+6))+(3+7)
+        // (16 KB regions over the dead images), wave 0 stores.  dQ: waves 4 and 5 each form one 32-feature half from the
+        // nine dS^T slots and the K image, key tiles in order -- no partial sums at all.
+        auto put = [&](int region) __attribute__((always_inline)) {
+            f32x4* p = (f32x4*)(smem + region * 16384) + lane;
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    p[(dt * 4 + g4) * 64] = f32x4{dK[dt][4 * g4], dK[dt][4 * g4 + 1], dK[dt][4 * g4 + 2], dK[dt][4 * g4 + 3]};
+                    p[(8 + dt * 4 + g4) * 64] = f32x4{dV[dt][4 * g4], dV[dt][4 * g4 + 1], dV[dt][4 * g4 + 2], dV[dt][4 * g4 + 3]};
+                }
+        };
+        auto add = [&](int region) __attribute__((always_inline)) {
+            const f32x4* p = (const f32x4*)(smem + region * 16384) + lane;
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const f32x4 uk = p[(dt * 4 + g4) * 64], uv = p[(8 + dt * 4 + g4) * 64];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dK[dt][4 * g4 + e] += uk[e], dV[dt][4 * g4 + e] += uv[e];
+                }
+        };
+        const int row8 = rowof(k8);
+        const float wt8 = k8 < N ? 1.f : 0.f;
+        if (w >= 4) put(w - 4);
+        if (w == 4 || w == 5) {
+            const int dt = w - 4;
+            f32x16 acc = zero16();
+            for (int k = 0; k < 9; ++k) {
+                const char* slot = slots + k * 2048;
+                const bf16x8 s0 = sfrag(slot, 0), s1 = sfrag(slot, 1);
+                const bf16x8 k0 = tfrag(Kimg + k * 4096, dt), k1 = tfrag(Kimg + k * 4096 + 2048, dt);
+                acc = Elem<bf16>::mfma(k0, s0, acc);
+                acc = Elem<bf16>::mfma(k1, s1, acc);
+            }
+            if (k8 < N) {
+                bf16* op = a.out + (size_t)row8 * ld + hd * 64 + dt * 32 + 4 * h;
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4)
+                    *(bf16x4*)(op + 8 * g4) =
+                        bf16x4{(bf16)(acc[4 * g4 + 0] * out_scale), (bf16)(acc[4 * g4 + 1] * out_scale),
+                               (bf16)(acc[4 * g4 + 2] * out_scale), (bf16)(acc[4 * g4 + 3] * out_scale)};
+            }
+            if (a.qvsum) colsum_tile(acc, wt8, out_scale, csum + dt * 32, lane);
+        }
+        __syncthreads();
+        if (w < 4) add(w);
+        if (w >= 1 && w < 4) put(w);
+        __syncthreads();
+        if (w == 0) {
+            add(1), add(2), add(3);
+            if (k8 < N) {
+                store_tile(dK, out_scale, row8, a.d);
+                store_tile(dV, a.inv_keep, row8, 2 * a.d);
+            }
+            if (a.qvsum) colsum_tiles(dV, wt8, a.inv_keep, csum + 64, lane);
+        }
+    } else if (active && ki < N) {
         // ki doubles as the query index of the dQ tile this wave owns
         bf16* op = a.out + (size_t)krow * ld + hd * 64 + 4 * h;
 #pragma unroll
@@ -997,7 +913,7 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
             }
     }
     if (a.qvsum) {
-        if (active) {
+        if (active && !(FRINGE && nq > 8)) {
             const float wt = ki < N ? 1.f : 0.f;
             colsum_tiles(dQ, wt, out_scale, csum, lane);
             colsum_tiles(dV, wt, a.inv_keep, csum + 64, lane);
@@ -1016,7 +932,7 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
 // a chunk = ATT_LCH tiles of 32 tokens x two images (K | V, or Q | dO) = 32 KiB, chunk j + 1 in flight (LDS-DMA) while
 // chunk j is consumed, one barrier per chunk.  One workgroup per (sequence, head) of ATT_LW waves; wave w owns tile
 // w + ATT_LW r in round r, so the number of rounds follows the sequence's OWN length (the short text sequences of a
-// mixed launch take one round of one chunk).  The per-tile arithmetic is that of attn_fwd_kernel / attn_bwd_kernel
+// mixed launch take one round of one chunk).  The per-tile arithmetic is that of attn_fwd_kernel / attn_bwd1_kernel
 // (scores transposed, key on the lane where the next MFMA wants it).
 //   forward   attn_fwd_long_kernel   waves own query tiles, K / V chunks streamed; exact running maximum per chunk
 //   backward  attn_dkdv_long_kernel  waves own key tiles, Q / dO chunks streamed: dK, dV, dv column sums
@@ -1235,7 +1151,7 @@ __global__ __launch_bounds__(512) void attn_fwd_long_kernel(const AttnArgs a) {
     }
 }
 
-// dQ^T[d][q] = sum_k K^T[d][k] dS^T[k][q]: waves own query tiles, K / V chunks streamed (the dQ item of attn_bwd_kernel)
+// dQ^T[d][q] = sum_k K^T[d][k] dS^T[k][q]: waves own query tiles, K / V chunks streamed
 __global__ __launch_bounds__(512) void attn_dq_long_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ring = smem;                                  // [2][K | V]
@@ -1358,7 +1274,7 @@ __global__ __launch_bounds__(512) void attn_dq_long_kernel(const AttnArgs a) {
 }
 
 // dV^T[d][k] = sum_q dO^T[d][q] Pd[q][k], dK^T[d][k] = sum_q Q^T[d][q] dS[q][k]: waves own key tiles, Q / dO chunks
-// streamed (the dK/dV item of attn_bwd_kernel)
+// streamed
 __global__ __launch_bounds__(512) void attn_dkdv_long_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ring = smem;                                  // [2][Q | dO]
@@ -1876,25 +1792,17 @@ int launch_fwd1(const AttnArgs& a, int nt, int nblocks, hipStream_t st) {
     hipLaunchKernelGGL(attn_fwd1_kernel, dim3(nblocks), dim3(nt * 64), LDS, st, a, nt * 32);
     return 0;
 }
-int launch_bwd(const AttnArgs& a, int nt, int nblocks, hipStream_t st) {
-    const int LDS = nt * 32 * 512 + nt * 32 * 16 + 32 + 512;
-    int& max_set = lds_limit_set(1);
-    if (LDS > max_set) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        max_set = LDS;
-    }
-    hipLaunchKernelGGL(attn_bwd_kernel, dim3(nblocks), dim3(512), LDS, st, a, nt * 32);
-    return 0;
-}
-
+template <bool FRINGE>
 int launch_bwd1(const AttnArgs& a, int nt, int nblocks, hipStream_t st) {
-    const int LDS = nt * 32 * 384 + 2 * nt * 2048 + nt * 32 * 12 + 512;
-    int& max_set = lds_limit_set(2);
+    // images Q | dO | K, two rings of nt dS^T slots, row constants, column sums; FRINGE: + the V tile of the fringe keys
+    const int LDS = nt * 32 * 384 + 2 * nt * 2048 + nt * 32 * 12 + 512 + (FRINGE ? 4096 : 0);
+    if (LDS > 160 * 1024) return -1;
+    int& max_set = lds_limit_set(FRINGE ? 1 : 2);
     if (LDS > max_set) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)attn_bwd1_kernel<FRINGE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         max_set = LDS;
     }
-    hipLaunchKernelGGL(attn_bwd1_kernel, dim3(nblocks), dim3(nt * 64), LDS, st, a, nt * 32);
+    hipLaunchKernelGGL(attn_bwd1_kernel<FRINGE>, dim3(nblocks), dim3((FRINGE ? 8 : nt) * 64), LDS, st, a, nt * 32);
     return 0;
 }
 
@@ -1975,8 +1883,9 @@ extern "C" int vlmo_attn_bwd(const void* qkv, const void* ctx, const void* dctx,
         VLMO_CHECK_LAUNCH("vlmo_attn_bwd(long)");
         return 0;
     }
-    if (nt > 8) launch_bwd(a, nt, nb, stream);      // 257 .. 288: one tile more than the single-pass kernel's eight owners
-    else launch_bwd1(a, nt, nb, stream);
+    // 257 .. 288: eight owners + the fringe steps for the ninth tile
+    const int rc = nt > 8 ? launch_bwd1<true>(a, nt, nb, stream) : launch_bwd1<false>(a, nt, nb, stream);
+    VLMO_CHECK_ARG(rc == 0, "vlmo_attn_bwd: %d tokens do not fit the LDS of one CU", max_len);
     VLMO_CHECK_LAUNCH("vlmo_attn_bwd");
     return 0;
 }

@@ -1,5 +1,5 @@
 """Attention forward / backward time against the sequence length at the VLMo-Base B=64 shape (which kernel takes which
-length: single-pass backward up to 256 tokens, two-phase up to 288, streaming above).
+length: single-pass backward up to 256 tokens, its fringe form up to 288, streaming above).
 usage: python tools/attn_len_sweep.py [len ...]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
