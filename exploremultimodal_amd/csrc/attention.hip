@@ -15,8 +15,8 @@
 // tokens, attn_dkdv_long_kernel + attn_dq_long_kernel for 289 - 1024; K / V
 // (or Q / dO) pass through a two-slot LDS ring instead of staying resident.
 // The launch's max_len picks the kernels; nothing else does.
-// attn_probs_kernel (vlmo_attn_probs) writes the probabilities themselves to HBM for inspection, beside this path;
-// attn_gradcam_kernel (vlmo_attn_gradcam) their gradient-weighted form.
+// attn_map_kernel writes the probabilities themselves to HBM for inspection, beside this path (vlmo_attn_probs), or
+// their gradient-weighted form (vlmo_attn_gradcam).
 //
 // Orientation: scores are computed TRANSPOSED, S^T[key][query] = K . Q^T, so a
 // lane owns one query column (softmax reductions are in-register + one
@@ -111,17 +111,64 @@ __device__ __forceinline__ f32x16 zero16() {
     return z;
 }
 
-__device__ __forceinline__ void setup_rows(const int32_t* seg, int sidx, const int32_t* keymask, int npad, int* rowidx,
-                                           float* kbias, int& N) {
-    const int rowA = seg[4 * sidx + 0], lenA = seg[4 * sidx + 1], rowB = seg[4 * sidx + 2], lenB = seg[4 * sidx + 3];
-    N = lenA + lenB;
-    for (int i = threadIdx.x; i < npad; i += blockDim.x) {
-        const int tok = min(i, N - 1);
-        const int row = tok < lenA ? rowA + tok : rowB + (tok - lenA);
-        rowidx[i] = row;
-        const bool ok = (i < N) && (!keymask || keymask[row] != 0);
-        kbias[i] = ok ? 0.f : -INFINITY;
+// Token of a sequence -> row of the packed matrix (the four words of seg: rowA, lenA, rowB, lenB)
+struct SeqRows {
+    int rowA, lenA, rowB, N;
+    __device__ __forceinline__ SeqRows(const int32_t* seg, int sidx)
+        : rowA(seg[4 * sidx + 0]), lenA(seg[4 * sidx + 1]), rowB(seg[4 * sidx + 2]), N(seg[4 * sidx + 1] + seg[4 * sidx + 3]) {}
+    // lengths clamped to [0, cap] tokens in all; an empty sequence reads row 0 (row(i) = rowA + min(i, -1))
+    __device__ __forceinline__ SeqRows(const int32_t* seg, int sidx, int cap)
+        : rowA(seg[4 * sidx + 0]), lenA(min(max(seg[4 * sidx + 1], 0), cap)), rowB(seg[4 * sidx + 2]),
+          N(lenA + min(max(seg[4 * sidx + 3], 0), cap - lenA)) {
+        if (N == 0) rowA = 1;
     }
+    __device__ __forceinline__ int row(int tok) const {        // padded tokens read the last real row
+        tok = min(tok, N - 1);
+        return tok < lenA ? rowA + tok : rowB + (tok - lenA);
+    }
+};
+
+// additive score bias of key i of a sequence of N tokens, `row` its packed row: -inf on padded and masked keys
+__device__ __forceinline__ float key_bias(const int32_t* keymask, int row, int i, int N) {
+    return (i < N && (!keymask || keymask[row] != 0)) ? 0.f : -INFINITY;
+}
+
+// row table and key bias of the padded tokens [0, npad) of a sequence, in LDS
+__device__ __forceinline__ void setup_rows(const SeqRows& sr, const int32_t* keymask, int npad, int* rowidx, float* kbias) {
+    for (int i = threadIdx.x; i < npad; i += blockDim.x) {
+        const int row = sr.row(i);
+        rowidx[i] = row;
+        kbias[i] = key_bias(keymask, row, i, sr.N);
+    }
+}
+
+// zero the dropped scores of an S^T tile; rk = dropout counter base of the lane's first key of the tile.  The tile goes
+// in and out by value: written through a reference, hipcc turns the 16 selects into compare chains and a branch.
+__device__ __forceinline__ f32x16 drop_tile(f32x16 S, uint32_t rk, uint32_t drop_cmp) {
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (att_mix(rk + (uint32_t)(8 * g4 + e) * ATT_G) < drop_cmp) S[4 * g4 + e] = 0.f;
+    return S;
+}
+
+// epilogue of the forwards: the O^T accumulators of query qi (packed row qrow) over the row sum l, as bf16 ctx, and
+// the row's log-sum-exp (the kernels keep their reference maximum in different units, so they pass the finished value).
+// `a` by value: it names the kernel's own argument block either way, and attn_fwd1_kernel keeps its 112 registers.
+__device__ __forceinline__ void store_ctx(const AttnArgs a, const f32x16 (&O)[2], float l, float lse, int bh, int hd,
+                                          int qi, int qrow, int h) {
+    const float inv = a.inv_keep / l;
+    bf16* op = a.out + (size_t)qrow * a.d + hd * 64 + 4 * h;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            bf16x4 o = {(bf16)(O[dt][4 * g4 + 0] * inv), (bf16)(O[dt][4 * g4 + 1] * inv),
+                        (bf16)(O[dt][4 * g4 + 2] * inv), (bf16)(O[dt][4 * g4 + 3] * inv)};
+            *(bf16x4*)(op + dt * 32 + 8 * g4) = o;
+        }
+    if (h == 0 && a.lse) a.lse[(size_t)bh * a.lse_stride + qi] = lse;
 }
 
 // Keys are swept in chunks of CK*32 = 128 with an exact running max (the chunk's
@@ -138,8 +185,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnArgs a, cons
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int bh = blockIdx.x, sidx = bh / a.heads, hd = bh % a.heads;
     const int ld = 3 * a.d;
-    int N;
-    setup_rows(a.seg, sidx, a.keymask, NPAD, rowidx, kbias, N);
+    const SeqRows sr(a.seg, sidx);
+    const int N = sr.N;
+    setup_rows(sr, a.keymask, NPAD, rowidx, kbias);
     __syncthreads();
     const int nq = (N + 31) >> 5;
     stage_image<4>(a.qkv, ld, a.d + hd * 64, rowidx, Kimg, nq * 4, wave, lane);
@@ -209,14 +257,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnArgs a, cons
             for (int c = 0; c < ATT_CK; ++c) {
                 const int kt = c0 + c;
                 if (kt < nq) {
-                    if (a.drop_thresh) {
-                        const uint32_t rk = rq + (uint32_t)(kt * 32) * ATT_G;
-#pragma unroll
-                        for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                if (att_mix(rk + (uint32_t)(8 * g4 + e) * ATT_G) < a.drop_cmp) S[c][4 * g4 + e] = 0.f;
-                    }
+                    if (a.drop_thresh) S[c] = drop_tile(S[c], rq + (uint32_t)(kt * 32) * ATT_G, a.drop_cmp);
 #pragma unroll
                     for (int s2 = 0; s2 < 2; ++s2) {
                         bf16x8 pf;
@@ -229,19 +270,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnArgs a, cons
                 }
             }
         }
-        if (qi < N) {
-            const float inv = a.inv_keep / l_run;
-            bf16* op = a.out + (size_t)qrow * a.d + hd * 64 + 4 * h;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    bf16x4 o = {(bf16)(O[dt][4 * g4 + 0] * inv), (bf16)(O[dt][4 * g4 + 1] * inv),
-                                (bf16)(O[dt][4 * g4 + 2] * inv), (bf16)(O[dt][4 * g4 + 3] * inv)};
-                    *(bf16x4*)(op + dt * 32 + 8 * g4) = o;
-                }
-            if (h == 0 && a.lse) a.lse[(size_t)bh * a.lse_stride + qi] = (m_run + log2f(l_run)) * LN2;
-        }
+        if (qi < N) store_ctx(a, O, l_run, (m_run + log2f(l_run)) * LN2, bh, hd, qi, qrow, h);
     }
 }
 
@@ -271,17 +300,13 @@ __global__ __launch_bounds__(576) void attn_fwd1_kernel(const AttnArgs a, const 
     const int nw = blockDim.x >> 6;
     const int bh = blockIdx.x, sidx = bh / a.heads, hd = bh % a.heads;
     const int ld = 3 * a.d;
-    const int rowA = a.seg[4 * sidx + 0], lenA = a.seg[4 * sidx + 1], rowB = a.seg[4 * sidx + 2], lenB = a.seg[4 * sidx + 3];
-    const int N = lenA + lenB;
-    auto rowof = [&](int tok) {
-        tok = min(tok, N - 1);
-        return tok < lenA ? rowA + tok : rowB + (tok - lenA);
-    };
+    const SeqRows sr(a.seg, sidx);
+    const int N = sr.N;
     const int nq = (N + 31) >> 5;
     const int l31 = lane & 31, h = lane >> 5;
     const bool active = w < nq;
     const int qi = w * 32 + l31;
-    const int qrow = rowof(qi);
+    const int qrow = sr.row(qi);
     bf16x8 qf[4];
     if (active) {
         const bf16* qp = a.qkv + (size_t)qrow * ld + hd * 64 + 8 * h;
@@ -292,13 +317,12 @@ __global__ __launch_bounds__(576) void attn_fwd1_kernel(const AttnArgs a, const 
         const int chhi = lane >> 5, rowlo = (lane >> 2) & 7, pc = lane & 3;
         const int row = ii * 8 + rowlo;
         const int ch = chhi * 4 + (pc ^ ((row >> 2) & 3));
-        const size_t r = (size_t)rowof(row);
+        const size_t r = (size_t)sr.row(row);
         glds16(a.qkv + r * ld + a.d + hd * 64 + ch * 8, Kimg + ii * 1024);
         glds16(a.qkv + r * ld + 2 * a.d + hd * 64 + ch * 8, Vimg + ii * 1024);
     }
     for (int i = threadIdx.x; i < NPAD; i += blockDim.x) {
-        const bool ok = (i < N) && (!a.keymask || a.keymask[rowof(i)] != 0);
-        kbias[i] = ok ? 0.f : -INFINITY;
+        kbias[i] = key_bias(a.keymask, sr.row(i), i, N);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -375,14 +399,7 @@ __global__ __launch_bounds__(576) void attn_fwd1_kernel(const AttnArgs a, const 
             S[i] = pr[0];
             S[i + 1] = pr[1];
         }
-        if (a.drop_thresh) {
-            const uint32_t rk = rq + (uint32_t)(kt * 32) * ATT_G;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (att_mix(rk + (uint32_t)(8 * g4 + e) * ATT_G) < a.drop_cmp) S[4 * g4 + e] = 0.f;
-        }
+        if (a.drop_thresh) S = drop_tile(S, rq + (uint32_t)(kt * 32) * ATT_G, a.drop_cmp);
         const char* vimg = Vimg + 4096 * kt;
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
@@ -410,19 +427,8 @@ __global__ __launch_bounds__(576) void attn_fwd1_kernel(const AttnArgs a, const 
     }
     const float l_run = l2[0] + l2[1];
     const float l_tot = l_run + other_half(l_run);
-    if (qi < N) {
-        const float inv = a.inv_keep / l_tot;
-        bf16* op = a.out + (size_t)qrow * a.d + hd * 64 + 4 * h;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                bf16x4 o = {(bf16)(O[dt][4 * g4 + 0] * inv), (bf16)(O[dt][4 * g4 + 1] * inv),
-                            (bf16)(O[dt][4 * g4 + 2] * inv), (bf16)(O[dt][4 * g4 + 3] * inv)};
-                *(bf16x4*)(op + dt * 32 + 8 * g4) = o;
-            }
-        if (h == 0 && a.lse) a.lse[(size_t)bh * a.lse_stride + qi] = (m_run * c2 + log2f(l_tot)) * LN2;
-    }
+    // the reference maximum is in raw score units here
+    if (qi < N) store_ctx(a, O, l_tot, (m_run * c2 + log2f(l_tot)) * LN2, bh, hd, qi, qrow, h);
 }
 
 // ------------------------------------------------------------------ backward
@@ -494,7 +500,6 @@ __device__ __forceinline__ int slot_off(int k, int q) {
 // it, the 40 MFMAs of both hide under it), 2-3 us of stores; one workgroup per CU, so the three phases add.
 template <bool FRINGE>
 __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const int NPAD) {
-    constexpr bool KF_REG = false;      // K row fragments re-read from the LDS image each step (16 registers: no spill)
     const int IMG = NPAD * 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Qimg = smem;
@@ -517,19 +522,15 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
     // descriptor words (scalar loads), so the LDS-DMA of the three images, the key mask, the rows of ctx / dctx for
     // delta, the log-sum-exp and this wave's V fragments are all issued together (a row table in LDS first costs two more
     // global round trips and a barrier: 6.4 of the 7.2 us a workgroup spent before its first product).
-    const int rowA = a.seg[4 * sidx + 0], lenA = a.seg[4 * sidx + 1], rowB = a.seg[4 * sidx + 2], lenB = a.seg[4 * sidx + 3];
-    const int N = lenA + lenB;
-    auto rowof = [&](int tok) __attribute__((always_inline)) {
-        tok = min(tok, N - 1);
-        return tok < lenA ? rowA + tok : rowB + (tok - lenA);
-    };
+    const SeqRows sr(a.seg, sidx);
+    const int N = sr.N;
     const int nq = (N + 31) >> 5;
     const int nc = FRINGE ? min(nq, 8) : nq;        // tiles of the rotation = waves at work
     for (int ii = w; ii < nq * 4; ii += nw) {
         const int chhi = lane >> 5, rowlo = (lane >> 2) & 7, pc = lane & 3;
         const int row = ii * 8 + rowlo;
         const int ch = chhi * 4 + (pc ^ ((row >> 2) & 3));
-        const size_t r = (size_t)rowof(row);
+        const size_t r = (size_t)sr.row(row);
         glds16(a.qkv + r * ld + hd * 64 + ch * 8, Qimg + ii * 1024);
         glds16(a.qkv + r * ld + a.d + hd * 64 + ch * 8, Kimg + ii * 1024);
         glds16(a.dctx + r * a.d + hd * 64 + ch * 8, Dimg + ii * 1024);
@@ -538,29 +539,27 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
         const int chhi = lane >> 5, rowlo = (lane >> 2) & 7, pc = lane & 3;
         const int row = 256 + (w - 4) * 8 + rowlo;
         const int ch = chhi * 4 + (pc ^ ((row >> 2) & 3));
-        glds16(a.qkv + (size_t)rowof(row) * ld + 2 * a.d + hd * 64 + ch * 8, V8img + (w - 4) * 1024);
+        glds16(a.qkv + (size_t)sr.row(row) * ld + 2 * a.d + hd * 64 + ch * 8, V8img + (w - 4) * 1024);
     }
     const int l31 = lane & 31, h = lane >> 5;
     const bool active = w < nc;
     const int ki = w * 32 + l31;
-    const int krow = rowof(ki);
+    const int krow = sr.row(ki);
     // row fragments (B operands) of this wave's keys straight from global memory: V has no LDS image at all
-    bf16x8 kf[4], vf[4];
+    // (K row fragments are re-read from the LDS image each step: held in 16 more registers they spill)
+    bf16x8 vf[4];
     if (active) {
         const bf16* kp = a.qkv + (size_t)krow * ld + a.d + hd * 64 + 8 * h;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            if (KF_REG) kf[s] = *(const bf16x8*)(kp + 16 * s);
-            vf[s] = *(const bf16x8*)(kp + a.d + 16 * s);
-        }
+        for (int s = 0; s < 4; ++s) vf[s] = *(const bf16x8*)(kp + a.d + 16 * s);
     }
     for (int i = threadIdx.x; i < 128; i += blockDim.x) csum[i] = 0.f;      // a one-tile launch has 64 threads
     const float keep_prob = 1.f / a.inv_keep;
     const float inv_scale = 1.f / a.scale;
     for (int i = threadIdx.x; i < NPAD; i += blockDim.x) {
         float dl = 0.f, lq = INFINITY;
-        const int row = rowof(i);
-        const bool ok = (i < N) && (!a.keymask || a.keymask[row] != 0);
+        const int row = sr.row(i);
+        const float kb = key_bias(a.keymask, row, i, N);
         if (i < N) {
             const size_t o = (size_t)row * a.d + hd * 64;
             bf16x8 x[8], y[8];
@@ -575,7 +574,7 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
 #pragma unroll
                 for (int j = 0; j < 8; ++j) dl += (float)x[c][j] * (float)y[c][j];
         }
-        kbias[i] = ok ? 0.f : -INFINITY;
+        kbias[i] = kb;
         ndl[i] = -dl * keep_prob;       // dS = scale * inv_keep * P * (keep * dP - delta * keep_prob)
         nlq[i] = -lq * inv_scale;
     }
@@ -663,8 +662,7 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const bf16x8 kfs = KF_REG ? kf[s] : rfrag(ktile, s);
-            S = Elem<bf16>::mfma(qa[s], kfs, S);
+            S = Elem<bf16>::mfma(qa[s], rfrag(ktile, s), S);
             dP = Elem<bf16>::mfma(da[s], vfr[s], dP);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -859,7 +857,7 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
                     for (int e = 0; e < 4; ++e) dK[dt][4 * g4 + e] += uk[e], dV[dt][4 * g4 + e] += uv[e];
                 }
         };
-        const int row8 = rowof(k8);
+        const int row8 = sr.row(k8);
         const float wt8 = k8 < N ? 1.f : 0.f;
         if (w >= 4) put(w - 4);
         if (w == 4 || w == 5) {
@@ -952,16 +950,6 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const AttnArgs a, const 
 // not the launch's max_len, so that a backward launch over a subset of a forward launch's sequences regenerates its mask.
 __device__ __forceinline__ uint32_t att_stride(int N) { return N > 512 ? 1024u : 512u; }
 
-struct SeqRows {
-    int rowA, lenA, rowB, N;
-    __device__ __forceinline__ SeqRows(const int32_t* seg, int sidx)
-        : rowA(seg[4 * sidx + 0]), lenA(seg[4 * sidx + 1]), rowB(seg[4 * sidx + 2]), N(seg[4 * sidx + 1] + seg[4 * sidx + 3]) {}
-    __device__ __forceinline__ int row(int tok) const {        // padded tokens read the last real row
-        tok = min(tok, N - 1);
-        return tok < lenA ? rowA + tok : rowB + (tok - lenA);
-    }
-};
-
 // LDS-DMA of tiles [t0, t0 + nt) of two 64-column operands into dual-use images ia / ib (tile-local rows: the swizzle of
 // att_off depends on the row modulo 32 only)
 __device__ __forceinline__ void stage_chunk(const bf16* pa, int lda, const bf16* pb, int ldb, const SeqRows& sr, int t0,
@@ -1012,7 +1000,7 @@ __device__ __forceinline__ void bwd_row_constants(const AttnArgs& a, const SeqRo
         }
         delta[i] = dl * keep_prob;
         lseq[i] = lq;
-        if (kbias) kbias[i] = (i < sr.N && (!a.keymask || a.keymask[row] != 0)) ? 0.f : -INFINITY;
+        if (kbias) kbias[i] = key_bias(a.keymask, row, i, sr.N);
     }
 }
 
@@ -1032,8 +1020,7 @@ __global__ __launch_bounds__(512) void attn_fwd_long_kernel(const AttnArgs a) {
     const bf16* kb0 = a.qkv + a.d + hd * 64;
     const bf16* vb0 = a.qkv + 2 * a.d + hd * 64;
     stage_chunk(kb0, ld, vb0, ld, sr, 0, min(ATT_LCH, nq), ring, ring + ATT_LBUF, w, lane);
-    for (int i = threadIdx.x; i < nq * 32; i += blockDim.x)
-        kbias[i] = (i < N && (!a.keymask || a.keymask[sr.row(i)] != 0)) ? 0.f : -INFINITY;
+    for (int i = threadIdx.x; i < nq * 32; i += blockDim.x) kbias[i] = key_bias(a.keymask, sr.row(i), i, N);
 
     const int l31 = lane & 31, h = lane >> 5;
     const uint32_t akey = att_key(a.seed, bh + a.bh0);
@@ -1116,14 +1103,7 @@ __global__ __launch_bounds__(512) void attn_fwd_long_kernel(const AttnArgs a) {
         for (int cc = 0; cc < ATT_LCH; ++cc) {
             const int kt = c0 + cc;
             if (kt < nq) {
-                if (a.drop_thresh) {
-                    const uint32_t rk = rq + (uint32_t)(kt * 32) * ATT_G;
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (att_mix(rk + (uint32_t)(8 * g4 + e) * ATT_G) < a.drop_cmp) S[cc][4 * g4 + e] = 0.f;
-                }
+                if (a.drop_thresh) S[cc] = drop_tile(S[cc], rq + (uint32_t)(kt * 32) * ATT_G, a.drop_cmp);
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
                     bf16x8 pf;
@@ -1135,19 +1115,7 @@ __global__ __launch_bounds__(512) void attn_fwd_long_kernel(const AttnArgs a) {
                 }
             }
         }
-        if (c == nch - 1 && qi < N) {
-            const float inv = a.inv_keep / l_run;
-            bf16* op = a.out + (size_t)qrow * a.d + hd * 64 + 4 * h;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    bf16x4 o = {(bf16)(O[dt][4 * g4 + 0] * inv), (bf16)(O[dt][4 * g4 + 1] * inv),
-                                (bf16)(O[dt][4 * g4 + 2] * inv), (bf16)(O[dt][4 * g4 + 3] * inv)};
-                    *(bf16x4*)(op + dt * 32 + 8 * g4) = o;
-                }
-            if (h == 0 && a.lse) a.lse[(size_t)bh * a.lse_stride + qi] = (m_run + log2f(l_run)) * LN2;
-        }
+        if (c == nch - 1 && qi < N) store_ctx(a, O, l_run, (m_run + log2f(l_run)) * LN2, bh, hd, qi, qrow, h);
     }
 }
 
@@ -1331,7 +1299,7 @@ __global__ __launch_bounds__(512) void attn_dkdv_long_kernel(const AttnArgs a) {
                 kf[s] = *(const bf16x8*)(kp + 16 * s);
                 vf[s] = *(const bf16x8*)(kp + a.d + 16 * s);
             }
-            kb = (ki < N && (!a.keymask || a.keymask[krow] != 0)) ? 0.f : -INFINITY;
+            kb = key_bias(a.keymask, krow, ki, N);
             rl = (uint32_t)ki * ATT_G + akey + (uint32_t)(4 * h) * gs;
             dK[0] = zero16(), dK[1] = zero16(), dV[0] = zero16(), dV[1] = zero16();
         }
@@ -1406,7 +1374,7 @@ __global__ __launch_bounds__(512) void attn_dkdv_long_kernel(const AttnArgs a) {
     }
 }
 
-// ------------------------------------------------------------------ attention maps (vlmo_attn_probs)
+// ------------------------------------------------------------------ attention maps (vlmo_attn_probs, vlmo_attn_gradcam)
 // P = softmax(q k^T * scale + keymask) written to HBM as fp32 [num_seq, heads | 1, nq, seq_len]: the one tensor the
 // kernels above exist to avoid, for looking at a trained model.  The kernel is bound by its OUTPUT (4 seq_len^2 bytes per
 // sequence and head against 64 multiply-adds per element), so it is laid out for the stores:
@@ -1422,167 +1390,34 @@ __global__ __launch_bounds__(512) void attn_dkdv_long_kernel(const AttnArgs a) {
 //   * head_mean: the workgroup walks the heads in order, restaging K; a lane owns the same output elements for every
 //     head, so the mean is a read-add-write of its own stores: no atomics, no workspace, a fixed order of additions.
 // Zero rules: masked keys, keys and query rows past the sequence's own length, and rows whose keys are all masked
-// (the reference has NaN there) are written as 0.  Lengths in seg are clamped to seq_len: nothing outside probs is written.
-struct ProbsArgs {
-    const bf16* qkv;
-    const int32_t* seg;
-    const int32_t* keymask;
-    float* probs;
-    int heads, d, seq_len, q0, nq, head_mean, tiles_per_block;
-    float scale_log2e;
-};
-#define ATT_PW 8
-#define ATT_LDS_PROBS (ATT_LMAX * 128 + ATT_LMAX * 8)
-
-__global__ __launch_bounds__(64 * ATT_PW) void attn_probs_kernel(const ProbsArgs a, const int NPAD) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Kimg = smem;
-    float* kbias = (float*)(smem + NPAD * 128);
-    int* rowidx = (int*)(kbias + NPAD);
-
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int hout = a.head_mean ? 1 : a.heads;
-    const int sidx = blockIdx.x / hout, hd0 = blockIdx.x % hout;
-    const int nh = a.head_mean ? a.heads : 1;
-    const int ld = 3 * a.d;
-    const int rowA = a.seg[4 * sidx + 0], rowB = a.seg[4 * sidx + 2];
-    const int lenA = min(max(a.seg[4 * sidx + 1], 0), a.seq_len);
-    const int N = lenA + min(max(a.seg[4 * sidx + 3], 0), a.seq_len - lenA);
-    for (int i = threadIdx.x; i < NPAD; i += blockDim.x) {
-        const int tok = max(min(i, N - 1), 0);
-        const int row = N == 0 ? 0 : (tok < lenA ? rowA + tok : rowB + (tok - lenA));
-        rowidx[i] = row;
-        kbias[i] = (i < N && (!a.keymask || a.keymask[row] != 0)) ? 0.f : -INFINITY;
-    }
-    __syncthreads();
-
-    const int l31 = lane & 31, h = lane >> 5;
-    const int nkt = (N + 31) >> 5;                  // key tiles that hold keys of this sequence
-    const int nkt_out = NPAD >> 5;                  // key tiles of the output rows
-    const int ntq = (a.nq + 31) >> 5;
-    const int t_begin = blockIdx.y * a.tiles_per_block, t_end = min(ntq, t_begin + a.tiles_per_block);
-    const float c2 = a.scale_log2e;
-    const float inv_heads = 1.f / (float)nh;
-    float* out = a.probs + (size_t)blockIdx.x * a.nq * a.seq_len;
-
-    for (int hi = 0; hi < nh; ++hi) {
-        const int hd = hd0 + hi;
-        if (hi) __syncthreads();                    // every wave is done with the previous head's K image
-        stage_image<ATT_PW>(a.qkv, ld, a.d + hd * 64, rowidx, Kimg, nkt * 4, w, lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-
-        for (int qt = t_begin + w; qt < t_end; qt += ATT_PW) {
-            const int ql = qt * 32;                 // first row of the tile inside the query window
-            const bf16* qp = a.qkv + (size_t)rowidx[min(a.q0 + ql + l31, NPAD - 1)] * ld + hd * 64 + 8 * h;
-            bf16x8 qf[4];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qp + 16 * s);
-
-            // sweep 1: running maximum and sum of every row over the keys this lane sees
-            f32x16 m, l = zero16();
-#pragma unroll
-            for (int i = 0; i < 16; ++i) m[i] = -INFINITY;
-            for (int kt = 0; kt < nkt; ++kt) {
-                f32x16 S = zero16();
-#pragma unroll
-                for (int s = 0; s < 4; ++s) S = Elem<bf16>::mfma(qf[s], row_frag(Kimg, kt * 32, s, lane), S);
-                const float kb = kbias[kt * 32 + l31];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float t = S[i] * c2 + kb;
-                    const float mn = fmaxf(m[i], t);
-                    const float ms = mn == -INFINITY ? 0.f : mn;
-                    l[i] = l[i] * __builtin_amdgcn_exp2f(m[i] - ms) + __builtin_amdgcn_exp2f(t - ms);
-                    m[i] = mn;
-                }
-            }
-            // the 32 lanes of a half-wave hold the same 16 rows: fold them (fixed order)
-#pragma unroll
-            for (int off = 16; off > 0; off >>= 1)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float mo = __shfl_xor(m[i], off, 64), lo = __shfl_xor(l[i], off, 64);
-                    const float mn = fmaxf(m[i], mo);
-                    const float ms = mn == -INFINITY ? 0.f : mn;
-                    l[i] = l[i] * __builtin_amdgcn_exp2f(m[i] - ms) + lo * __builtin_amdgcn_exp2f(mo - ms);
-                    m[i] = mn;
-                }
-            // l becomes the factor of the row (0: the row is written as zeros), m its finite reference
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int qi = a.q0 + ql + 8 * (i >> 2) + 4 * h + (i & 3);
-                const bool zero = qi >= N || m[i] == -INFINITY;
-                l[i] = zero ? 0.f : inv_heads / l[i];
-                m[i] = zero ? 0.f : m[i];
-            }
-
-            // sweep 2: the same scores again, normalised and stored
-            const int rows_left = a.nq - ql - 4 * h;        // row 8 (i >> 2) + (i & 3) of this half is inside the window
-            for (int kt = 0; kt < nkt_out; ++kt) {
-                const int key = kt * 32 + l31;
-                const bool has_keys = kt < nkt;             // wave-uniform
-                f32x16 S = zero16();
-                float kb = 0.f;
-                if (has_keys) {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) S = Elem<bf16>::mfma(qf[s], row_frag(Kimg, kt * 32, s, lane), S);
-                    kb = kbias[key];
-                }
-                if (key < a.seq_len) {
-                    float* op = out + (size_t)(ql + 4 * h) * a.seq_len + key;
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int r = 8 * (i >> 2) + (i & 3);
-                        if (r < rows_left) {
-                            float v = 0.f;
-                            if (has_keys && l[i] != 0.f) v = __builtin_amdgcn_exp2f(S[i] * c2 + kb - m[i]) * l[i];
-                            float* p = op + (size_t)r * a.seq_len;
-                            *p = hi ? *p + v : v;
-                        }
-                    }
-                }
-            }
-        }
-    }
-}
-
-int launch_probs(const ProbsArgs& a, int gx, int gy, hipStream_t st) {
-    static DeviceOnce once;
-    if (once.first())
-        (void)hipFuncSetAttribute((const void*)attn_probs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_PROBS);
-    const int npad = (a.seq_len + 31) / 32 * 32;
-    hipLaunchKernelGGL(attn_probs_kernel, dim3(gx, gy), dim3(64 * ATT_PW), npad * 136, st, a, npad);
-    return 0;
-}
-
-// ------------------------------------------------------------------ gradient-weighted maps (vlmo_attn_gradcam)
-// Grad-CAM on the attention maps: with P taken as a free variable, d score / d P[i, j] = G[i, j] = dctx[i, :] . v[j, :]
-// per head (ctx = P v).  The kernel is attn_probs_kernel with one more MFMA chain in the second sweep: the dctx rows of
-// the query tile are a second row operand held in registers beside q, and V is a second key-row image beside K, so G
-// lands in the accumulator layout of S (query row on the register, key on the lane) and the combination
+// (the reference has NaN there) are written as 0.  Lengths in seg are clamped to seq_len: nothing outside out is written.
+//
+// The two MAP_CAM modes write Grad-CAM on these maps instead: with P taken as a free variable, d score / d P[i, j] =
+// G[i, j] = dctx[i, :] . v[j, :] per head (ctx = P v).  That is one more MFMA chain in the second sweep: the dctx rows of
+// the query tile are a second row operand held in registers beside q, and V is a second key-row operand beside K, so G
+// lands in the accumulator layout of S and the combination
 //   kind GRAD: G      ATTN_GRAD: P * G      CAM: P * max(G, 0)
-// is stored exactly as the maps are (128-byte key runs, read-add-write head mean in head order).
-//   * VRES (seq_len <= 512): K and V of the head both resident, 2 x 64 KB + the 4 KB of key bias and row table.
-//   * longer (513 - 1024): K alone takes 128 KB, so the V operand of a key tile (4 x 16 B per lane, the bytes row_frag
-//     would read from an image) is streamed from global memory into registers, one tile ahead: the loads of tile kt + 1
-//     are issued before the stores of tile kt.  A wave reads 4 KB of V (L2 hits: the head's V is 128 KB) per 4 KB tile
-//     it stores, and the stores go to HBM.
-// The zero rules of the maps hold for every kind: G is written only where the definition of P has a non-zero.
-struct GradcamArgs {
+// is stored exactly as the maps are.  G is written only where the definition of P has a non-zero.
+//   * MAP_CAM_VRES (seq_len <= 512): K and V of the head both resident, 2 x 64 KB + the 4 KB of key bias and row table.
+//   * MAP_CAM_VSTREAM (513 - 1024): K alone takes 128 KB, so the V operand of a key tile (4 x 16 B per lane, the bytes
+//     row_frag would read from an image) is streamed from global memory into registers, one tile ahead: the loads of
+//     tile kt + 1 are issued before the stores of tile kt.  A wave reads 4 KB of V (L2 hits: the head's V is 128 KB) per
+//     4 KB tile it stores, and the stores go to HBM.
+struct MapArgs {
     const bf16* qkv;
-    const bf16* dctx;
+    const bf16* dctx;       // MAP_CAM modes
     const int32_t* seg;
     const int32_t* keymask;
     float* out;
-    int heads, d, seq_len, q0, nq, head_mean, tiles_per_block, kind;
+    int heads, d, seq_len, q0, nq, head_mean, tiles_per_block, kind;        // kind: MAP_CAM modes
     float scale_log2e;
 };
-#define ATT_LDS_GRADCAM (512 * 256 + 512 * 8)   // VRES at 512 tokens; the long form needs ATT_LDS_PROBS
+enum { MAP_PROBS, MAP_CAM_VRES, MAP_CAM_VSTREAM };
+#define ATT_PW 8
 
-template <bool VRES>
-__global__ __launch_bounds__(64 * ATT_PW) void attn_gradcam_kernel(const GradcamArgs a, const int NPAD) {
+template <int MODE>
+__global__ __launch_bounds__(64 * ATT_PW) void attn_map_kernel(const MapArgs a, const int NPAD) {
+    constexpr bool CAM = MODE != MAP_PROBS, VRES = MODE == MAP_CAM_VRES, VSTREAM = MODE == MAP_CAM_VSTREAM;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Kimg = smem;
     char* Vimg = smem + NPAD * 128;                 // VRES only
@@ -1595,15 +1430,9 @@ __global__ __launch_bounds__(64 * ATT_PW) void attn_gradcam_kernel(const Gradcam
     const int sidx = blockIdx.x / hout, hd0 = blockIdx.x % hout;
     const int nh = a.head_mean ? a.heads : 1;
     const int ld = 3 * a.d;
-    const int rowA = a.seg[4 * sidx + 0], rowB = a.seg[4 * sidx + 2];
-    const int lenA = min(max(a.seg[4 * sidx + 1], 0), a.seq_len);
-    const int N = lenA + min(max(a.seg[4 * sidx + 3], 0), a.seq_len - lenA);
-    for (int i = threadIdx.x; i < NPAD; i += blockDim.x) {
-        const int tok = max(min(i, N - 1), 0);
-        const int row = N == 0 ? 0 : (tok < lenA ? rowA + tok : rowB + (tok - lenA));
-        rowidx[i] = row;
-        kbias[i] = (i < N && (!a.keymask || a.keymask[row] != 0)) ? 0.f : -INFINITY;
-    }
+    const SeqRows sr(a.seg, sidx, a.seq_len);
+    const int N = sr.N;
+    setup_rows(sr, a.keymask, NPAD, rowidx, kbias);
     __syncthreads();
 
     const int l31 = lane & 31, h = lane >> 5;
@@ -1639,15 +1468,16 @@ __global__ __launch_bounds__(64 * ATT_PW) void attn_gradcam_kernel(const Gradcam
             const int ql = qt * 32;                 // first row of the tile inside the query window
             const size_t qrow = (size_t)rowidx[min(a.q0 + ql + l31, NPAD - 1)];
             const bf16* qp = a.qkv + qrow * ld + hd * 64 + 8 * h;
-            const bf16* dp = a.dctx + qrow * a.d + hd * 64 + 8 * h;
             bf16x8 qf[4], df[4];
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                qf[s] = *(const bf16x8*)(qp + 16 * s);
-                df[s] = *(const bf16x8*)(dp + 16 * s);
+            for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qp + 16 * s);
+            if (CAM) {
+                const bf16* dp = a.dctx + qrow * a.d + hd * 64 + 8 * h;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) df[s] = *(const bf16x8*)(dp + 16 * s);
             }
 
-            // sweep 1: running maximum and sum of every row over the keys this lane sees (as attn_probs_kernel)
+            // sweep 1: running maximum and sum of every row over the keys this lane sees
             f32x16 m, l = zero16();
 #pragma unroll
             for (int i = 0; i < 16; ++i) m[i] = -INFINITY;
@@ -1665,6 +1495,7 @@ __global__ __launch_bounds__(64 * ATT_PW) void attn_gradcam_kernel(const Gradcam
                     m[i] = mn;
                 }
             }
+            // the 32 lanes of a half-wave hold the same 16 rows: fold them (fixed order)
 #pragma unroll
             for (int off = 16; off > 0; off >>= 1)
 #pragma unroll
@@ -1675,7 +1506,7 @@ __global__ __launch_bounds__(64 * ATT_PW) void attn_gradcam_kernel(const Gradcam
                     l[i] = l[i] * __builtin_amdgcn_exp2f(m[i] - ms) + lo * __builtin_amdgcn_exp2f(mo - ms);
                     m[i] = mn;
                 }
-            // l becomes the factor of the row (0: the row is written as zeros, for every kind), m its finite reference
+            // l becomes the factor of the row (0: the row is written as zeros, in every mode), m its finite reference
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int qi = a.q0 + ql + 8 * (i >> 2) + 4 * h + (i & 3);
@@ -1684,23 +1515,25 @@ __global__ __launch_bounds__(64 * ATT_PW) void attn_gradcam_kernel(const Gradcam
                 m[i] = zero ? 0.f : m[i];
             }
 
-            // sweep 2: the scores again and G = dctx . v^T beside them, combined and stored
+            // sweep 2: the same scores again (CAM: and G = dctx . v^T beside them), normalised, combined and stored
             const int rows_left = a.nq - ql - 4 * h;        // row 8 (i >> 2) + (i & 3) of this half is inside the window
             bf16x8 vf[4];
-            if (!VRES && nkt > 0) v_frags(0, vf);
+            if (VSTREAM && nkt > 0) v_frags(0, vf);
             for (int kt = 0; kt < nkt_out; ++kt) {
                 const int key = kt * 32 + l31;
                 const bool has_keys = kt < nkt;             // wave-uniform
                 f32x16 S = zero16(), G = zero16();
-                float kb = -INFINITY;
+                float kb = CAM ? -INFINITY : 0.f;
                 if (has_keys) {
                     if (VRES) v_frags(kt, vf);
 #pragma unroll
                     for (int s = 0; s < 4; ++s) S = Elem<bf16>::mfma(qf[s], row_frag(Kimg, kt * 32, s, lane), S);
+                    if (CAM) {
 #pragma unroll
-                    for (int s = 0; s < 4; ++s) G = Elem<bf16>::mfma(df[s], vf[s], G);
+                        for (int s = 0; s < 4; ++s) G = Elem<bf16>::mfma(df[s], vf[s], G);
+                    }
                     kb = kbias[key];
-                    if (!VRES && kt + 1 < nkt) v_frags(kt + 1, vf);     // in flight during this tile's stores
+                    if (VSTREAM && kt + 1 < nkt) v_frags(kt + 1, vf);       // in flight during this tile's stores
                 }
                 if (key < a.seq_len) {
                     float* op = out + (size_t)(ql + 4 * h) * a.seq_len + key;
@@ -1708,8 +1541,12 @@ __global__ __launch_bounds__(64 * ATT_PW) void attn_gradcam_kernel(const Gradcam
                     for (int i = 0; i < 16; ++i) {
                         const int r = 8 * (i >> 2) + (i & 3);
                         if (r < rows_left) {
+                            // MAP_PROBS adds the key bias inside the exponent (fma(S, c, kb) - m: two roundings), the
+                            // CAM modes test it instead (fma(S, c, -m): one).  Each keeps the bits it has always written.
                             float v = 0.f;
-                            if (kb == 0.f && l[i] != 0.f) {     // a key the definition gives a non-zero P, in a live row
+                            if (!CAM) {
+                                if (has_keys && l[i] != 0.f) v = __builtin_amdgcn_exp2f(S[i] * c2 + kb - m[i]) * l[i];
+                            } else if (kb == 0.f && l[i] != 0.f) {      // a key the definition gives a non-zero P, in a live row
                                 const float g = kind == VLMO_GRADCAM_CAM ? fmaxf(G[i], 0.f) : G[i];
                                 v = kind == VLMO_GRADCAM_GRAD ? g * inv_heads
                                                               : __builtin_amdgcn_exp2f(S[i] * c2 - m[i]) * l[i] * g;
@@ -1724,85 +1561,49 @@ __global__ __launch_bounds__(64 * ATT_PW) void attn_gradcam_kernel(const Gradcam
     }
 }
 
-int launch_gradcam(const GradcamArgs& a, int gx, int gy, hipStream_t st) {
-    static DeviceOnce once;
-    if (once.first()) {
-        (void)hipFuncSetAttribute((const void*)attn_gradcam_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  ATT_LDS_GRADCAM);
-        (void)hipFuncSetAttribute((const void*)attn_gradcam_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  ATT_LDS_PROBS);
-    }
-    const int npad = (a.seq_len + 31) / 32 * 32;
-    if (a.seq_len <= 512)
-        hipLaunchKernelGGL(attn_gradcam_kernel<true>, dim3(gx, gy), dim3(64 * ATT_PW), npad * 264, st, a, npad);
-    else
-        hipLaunchKernelGGL(attn_gradcam_kernel<false>, dim3(gx, gy), dim3(64 * ATT_PW), npad * 136, st, a, npad);
-    return 0;
-}
-
-int launch_fwd_long(const AttnArgs& a, int nblocks, hipStream_t st) {
-    static DeviceOnce once;
-    if (once.first())
-        (void)hipFuncSetAttribute((const void*)attn_fwd_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_FWD);
-    hipLaunchKernelGGL(attn_fwd_long_kernel, dim3(nblocks), dim3(64 * ATT_LW), ATT_LDS_FWD, st, a);
-    return 0;
-}
-int launch_bwd_long(const AttnArgs& a, int nblocks, hipStream_t st) {
-    static DeviceOnce once;
-    if (once.first()) {
-        (void)hipFuncSetAttribute((const void*)attn_dkdv_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_BWD);
-        (void)hipFuncSetAttribute((const void*)attn_dq_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_BWD);
-    }
-    hipLaunchKernelGGL(attn_dkdv_long_kernel, dim3(nblocks), dim3(64 * ATT_LW), ATT_LDS_BWD, st, a);
-    hipLaunchKernelGGL(attn_dq_long_kernel, dim3(nblocks), dim3(64 * ATT_LW), ATT_LDS_BWD, st, a);
-    return 0;
-}
-
-// dynamic-LDS limit already raised for a kernel on a device (a process may drive several GPUs)
-int& lds_limit_set(int which) {
-    static int lim[4][64];
-    static bool init = false;
-    if (!init) {
-        for (auto& r : lim)
-            for (int& v : r) v = 65536;
-        init = true;
-    }
+// Launch with `lds` bytes of dynamic LDS.  Beyond the 64 KB default a kernel's limit has to be raised first, on every
+// device it runs on (a process may drive several GPUs): mark[] is the limit set so far for this kernel, per device,
+// raised atomically as DeviceOnce does it.
+template <auto Kernel, class... Args>
+void launch(dim3 grid, int threads, int lds, hipStream_t st, const Args&... args) {
+    static int mark[64];
     int dev = 0;
     (void)hipGetDevice(&dev);
-    return lim[which][dev & 63];
+    int& set = mark[dev & 63];
+    int old = __atomic_load_n(&set, __ATOMIC_RELAXED);
+    while (lds > std::max(old, 65536))
+        if (__atomic_compare_exchange_n(&set, &old, lds, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+            (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            break;
+        }
+    hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, st, args...);
 }
 
-int launch_fwd(const AttnArgs& a, int nt, int nblocks, hipStream_t st) {
-    const int LDS = nt * 32 * 256 + nt * 32 * 8;
-    int& max_set = lds_limit_set(0);
-    if (LDS > max_set) {
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        max_set = LDS;
-    }
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3(nblocks), dim3(256), LDS, st, a, nt * 32);
-    return 0;
+void launch_map(const MapArgs& a, int gx, int gy, hipStream_t st) {
+    const int npad = (a.seq_len + 31) / 32 * 32;
+    if (!a.dctx) launch<attn_map_kernel<MAP_PROBS>>(dim3(gx, gy), 64 * ATT_PW, npad * 136, st, a, npad);
+    else if (a.seq_len <= 512) launch<attn_map_kernel<MAP_CAM_VRES>>(dim3(gx, gy), 64 * ATT_PW, npad * 264, st, a, npad);
+    else launch<attn_map_kernel<MAP_CAM_VSTREAM>>(dim3(gx, gy), 64 * ATT_PW, npad * 136, st, a, npad);
 }
-int launch_fwd1(const AttnArgs& a, int nt, int nblocks, hipStream_t st) {
-    const int LDS = nt * 32 * 256 + nt * 32 * 4;
-    int& max_set = lds_limit_set(3);
-    if (LDS > max_set) {
-        (void)hipFuncSetAttribute((const void*)attn_fwd1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        max_set = LDS;
-    }
-    hipLaunchKernelGGL(attn_fwd1_kernel, dim3(nblocks), dim3(nt * 64), LDS, st, a, nt * 32);
-    return 0;
+void launch_fwd_long(const AttnArgs& a, int nblocks, hipStream_t st) {
+    launch<attn_fwd_long_kernel>(dim3(nblocks), 64 * ATT_LW, ATT_LDS_FWD, st, a);
+}
+void launch_bwd_long(const AttnArgs& a, int nblocks, hipStream_t st) {
+    launch<attn_dkdv_long_kernel>(dim3(nblocks), 64 * ATT_LW, ATT_LDS_BWD, st, a);
+    launch<attn_dq_long_kernel>(dim3(nblocks), 64 * ATT_LW, ATT_LDS_BWD, st, a);
+}
+void launch_fwd(const AttnArgs& a, int nt, int nblocks, hipStream_t st) {
+    launch<attn_fwd_kernel>(dim3(nblocks), 256, nt * 32 * 256 + nt * 32 * 8, st, a, nt * 32);
+}
+void launch_fwd1(const AttnArgs& a, int nt, int nblocks, hipStream_t st) {
+    launch<attn_fwd1_kernel>(dim3(nblocks), nt * 64, nt * 32 * 256 + nt * 32 * 4, st, a, nt * 32);
 }
 template <bool FRINGE>
 int launch_bwd1(const AttnArgs& a, int nt, int nblocks, hipStream_t st) {
     // images Q | dO | K, two rings of nt dS^T slots, row constants, column sums; FRINGE: + the V tile of the fringe keys
     const int LDS = nt * 32 * 384 + 2 * nt * 2048 + nt * 32 * 12 + 512 + (FRINGE ? 4096 : 0);
     if (LDS > 160 * 1024) return -1;
-    int& max_set = lds_limit_set(FRINGE ? 1 : 2);
-    if (LDS > max_set) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd1_kernel<FRINGE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        max_set = LDS;
-    }
-    hipLaunchKernelGGL(attn_bwd1_kernel<FRINGE>, dim3(nblocks), dim3((FRINGE ? 8 : nt) * 64), LDS, st, a, nt * 32);
+    launch<attn_bwd1_kernel<FRINGE>>(dim3(nblocks), (FRINGE ? 8 : nt) * 64, LDS, st, a, nt * 32);
     return 0;
 }
 
@@ -1815,18 +1616,12 @@ int check_common(const char* fn, const void* qkv, const int32_t* seg, int num_se
     return 0;
 }
 
-}  // namespace
-
-extern "C" int vlmo_attn_fwd(const void* qkv, const int32_t* seg, int num_seq, const int32_t* keymask, void* ctx,
-                             float* lse, int lse_stride, int heads, int d, int max_len, float scale,
-                             uint32_t drop_thresh, float inv_keep, uint64_t seed, int mask_seq0, hipStream_t stream) {
-    if (int rc = check_common("vlmo_attn_fwd", qkv, seg, num_seq, heads, d, max_len, 1024)) return rc;
-    VLMO_CHECK_ARG(ctx, "vlmo_attn_fwd: null ctx");
-    VLMO_CHECK_ARG(!lse || lse_stride >= max_len, "vlmo_attn_fwd: lse_stride too small");
+// the arguments vlmo_attn_fwd and vlmo_attn_bwd share; the tensors that differ are left to the caller
+AttnArgs make_args(const void* qkv, const int32_t* seg, const int32_t* keymask, const float* lse, int lse_stride, int heads,
+                   int d, float scale, uint32_t drop_thresh, float inv_keep, uint64_t seed, int mask_seq0) {
     AttnArgs a{};
     a.qkv = (const bf16*)qkv;
-    a.out = (bf16*)ctx;
-    a.lse = lse;
+    a.lse = (float*)lse;
     a.seg = seg;
     a.keymask = keymask;
     a.lse_stride = lse_stride;
@@ -1839,6 +1634,51 @@ extern "C" int vlmo_attn_fwd(const void* qkv, const int32_t* seg, int num_seq, c
     a.inv_keep = drop_thresh ? inv_keep : 1.f;
     a.seed = seed;
     a.bh0 = mask_seq0 * heads;
+    return a;
+}
+
+// vlmo_attn_probs (dctx null, kind unused) and vlmo_attn_gradcam, behind the checks of their own arguments
+int run_map(const char* fn, const void* qkv, const void* dctx, const int32_t* seg, int num_seq, const int32_t* keymask,
+            float* out, int heads, int d, int seq_len, int q0, int nq, int kind, int head_mean, float scale,
+            hipStream_t stream) {
+    if (int rc = check_common(fn, qkv, seg, num_seq, heads, d, seq_len, ATT_LMAX)) return rc;
+    VLMO_CHECK_ARG(q0 >= 0 && nq >= 1 && q0 <= seq_len - nq, "%s: query rows [%d, %d + %d) outside [0, %d)", fn, q0, q0, nq,
+                   seq_len);
+    MapArgs a{};
+    a.qkv = (const bf16*)qkv;
+    a.dctx = (const bf16*)dctx;
+    a.seg = seg;
+    a.keymask = keymask;
+    a.out = out;
+    a.heads = heads;
+    a.d = d;
+    a.seq_len = seq_len;
+    a.q0 = q0;
+    a.nq = nq;
+    a.kind = kind;
+    a.head_mean = head_mean != 0;
+    a.scale_log2e = scale * LOG2E;
+    // one query tile per wave and round; the query tiles of a (sequence, head) are split over workgroups only while
+    // that adds workgroups the chip has room for (each one stages the head's images again)
+    const int gx = num_seq * (a.head_mean ? 1 : heads);
+    const int rounds = ((nq + 31) / 32 + ATT_PW - 1) / ATT_PW;
+    const int gy = std::min(rounds, std::max(1, (768 + gx - 1) / gx));
+    a.tiles_per_block = ATT_PW * ((rounds + gy - 1) / gy);
+    launch_map(a, gx, (rounds * ATT_PW + a.tiles_per_block - 1) / a.tiles_per_block, stream);
+    VLMO_CHECK_LAUNCH(fn);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int vlmo_attn_fwd(const void* qkv, const int32_t* seg, int num_seq, const int32_t* keymask, void* ctx,
+                             float* lse, int lse_stride, int heads, int d, int max_len, float scale,
+                             uint32_t drop_thresh, float inv_keep, uint64_t seed, int mask_seq0, hipStream_t stream) {
+    if (int rc = check_common("vlmo_attn_fwd", qkv, seg, num_seq, heads, d, max_len, 1024)) return rc;
+    VLMO_CHECK_ARG(ctx, "vlmo_attn_fwd: null ctx");
+    VLMO_CHECK_ARG(!lse || lse_stride >= max_len, "vlmo_attn_fwd: lse_stride too small");
+    AttnArgs a = make_args(qkv, seg, keymask, lse, lse_stride, heads, d, scale, drop_thresh, inv_keep, seed, mask_seq0);
+    a.out = (bf16*)ctx;
     const int nt = (max_len + 31) / 32, nb = num_seq * heads;
     if (max_len > 512) {        // 513 .. 1024 tokens: K / V streamed (the resident kernels' 512-token dropout counter ends here)
         launch_fwd_long(a, nb, stream);
@@ -1858,25 +1698,11 @@ extern "C" int vlmo_attn_bwd(const void* qkv, const void* ctx, const void* dctx,
     if (int rc = check_common("vlmo_attn_bwd", qkv, seg, num_seq, heads, d, max_len, 1024)) return rc;
     VLMO_CHECK_ARG(ctx && dctx && lse && dqkv, "vlmo_attn_bwd: null pointer");
     VLMO_CHECK_ARG(lse_stride >= max_len, "vlmo_attn_bwd: lse_stride too small");
-    AttnArgs a{};
-    a.qkv = (const bf16*)qkv;
+    AttnArgs a = make_args(qkv, seg, keymask, lse, lse_stride, heads, d, scale, drop_thresh, inv_keep, seed, mask_seq0);
     a.ctx = (const bf16*)ctx;
     a.dctx = (const bf16*)dctx;
     a.out = (bf16*)dqkv;
     a.qvsum = qv_colsum;
-    a.lse = (float*)lse;
-    a.seg = seg;
-    a.keymask = keymask;
-    a.lse_stride = lse_stride;
-    a.heads = heads;
-    a.d = d;
-    a.scale = scale;
-    a.scale_log2e = scale * LOG2E;
-    a.drop_thresh = drop_thresh;
-    a.drop_cmp = drop_thresh >= 65536u ? 0xFFFFFFFFu : drop_thresh << 16;
-    a.inv_keep = drop_thresh ? inv_keep : 1.f;
-    a.seed = seed;
-    a.bh0 = mask_seq0 * heads;
     const int nt = (max_len + 31) / 32, nb = num_seq * heads;
     if (max_len > 288) {        // 289 .. 1024 tokens: the dK/dV and the dQ streaming kernels, back to back
         launch_bwd_long(a, nb, stream);
@@ -1893,63 +1719,17 @@ extern "C" int vlmo_attn_bwd(const void* qkv, const void* ctx, const void* dctx,
 extern "C" int vlmo_attn_probs(const void* qkv, const int32_t* seg, int num_seq, const int32_t* keymask, float* probs,
                                int heads, int d, int seq_len, int q0, int nq, int head_mean, float scale,
                                hipStream_t stream) {
-    if (int rc = check_common("vlmo_attn_probs", qkv, seg, num_seq, heads, d, seq_len, ATT_LMAX)) return rc;
     VLMO_CHECK_ARG(probs, "vlmo_attn_probs: null probs");
-    VLMO_CHECK_ARG(q0 >= 0 && nq >= 1 && q0 <= seq_len - nq, "vlmo_attn_probs: query rows [%d, %d + %d) outside [0, %d)", q0,
-                   q0, nq, seq_len);
-    ProbsArgs a{};
-    a.qkv = (const bf16*)qkv;
-    a.seg = seg;
-    a.keymask = keymask;
-    a.probs = probs;
-    a.heads = heads;
-    a.d = d;
-    a.seq_len = seq_len;
-    a.q0 = q0;
-    a.nq = nq;
-    a.head_mean = head_mean != 0;
-    a.scale_log2e = scale * LOG2E;
-    // one query tile per wave and round; the query tiles of a (sequence, head) are split over workgroups only while
-    // that adds workgroups the chip has room for (each one stages the head's K again)
-    const int gx = num_seq * (a.head_mean ? 1 : heads);
-    const int rounds = ((nq + 31) / 32 + ATT_PW - 1) / ATT_PW;
-    const int gy = std::min(rounds, std::max(1, (768 + gx - 1) / gx));
-    a.tiles_per_block = ATT_PW * ((rounds + gy - 1) / gy);
-    launch_probs(a, gx, (rounds * ATT_PW + a.tiles_per_block - 1) / a.tiles_per_block, stream);
-    VLMO_CHECK_LAUNCH("vlmo_attn_probs");
-    return 0;
+    return run_map("vlmo_attn_probs", qkv, nullptr, seg, num_seq, keymask, probs, heads, d, seq_len, q0, nq, 0, head_mean,
+                   scale, stream);
 }
 
 extern "C" int vlmo_attn_gradcam(const void* qkv, const void* dctx, const int32_t* seg, int num_seq, const int32_t* keymask,
                                  float* out, int heads, int d, int seq_len, int q0, int nq, int kind, int head_mean,
                                  float scale, hipStream_t stream) {
-    if (int rc = check_common("vlmo_attn_gradcam", qkv, seg, num_seq, heads, d, seq_len, ATT_LMAX)) return rc;
     VLMO_CHECK_ARG(dctx && out, "vlmo_attn_gradcam: null dctx or out");
-    VLMO_CHECK_ARG(q0 >= 0 && nq >= 1 && q0 <= seq_len - nq, "vlmo_attn_gradcam: query rows [%d, %d + %d) outside [0, %d)",
-                   q0, q0, nq, seq_len);
     VLMO_CHECK_ARG(kind == VLMO_GRADCAM_CAM || kind == VLMO_GRADCAM_ATTN_GRAD || kind == VLMO_GRADCAM_GRAD,
                    "vlmo_attn_gradcam: unknown kind %d", kind);
-    GradcamArgs a{};
-    a.qkv = (const bf16*)qkv;
-    a.dctx = (const bf16*)dctx;
-    a.seg = seg;
-    a.keymask = keymask;
-    a.out = out;
-    a.heads = heads;
-    a.d = d;
-    a.seq_len = seq_len;
-    a.q0 = q0;
-    a.nq = nq;
-    a.kind = kind;
-    a.head_mean = head_mean != 0;
-    a.scale_log2e = scale * LOG2E;
-    // the split of vlmo_attn_probs: one query tile per wave and round, more workgroups per (sequence, head) only while
-    // the chip has room for them
-    const int gx = num_seq * (a.head_mean ? 1 : heads);
-    const int rounds = ((nq + 31) / 32 + ATT_PW - 1) / ATT_PW;
-    const int gy = std::min(rounds, std::max(1, (768 + gx - 1) / gx));
-    a.tiles_per_block = ATT_PW * ((rounds + gy - 1) / gy);
-    launch_gradcam(a, gx, (rounds * ATT_PW + a.tiles_per_block - 1) / a.tiles_per_block, stream);
-    VLMO_CHECK_LAUNCH("vlmo_attn_gradcam");
-    return 0;
+    return run_map("vlmo_attn_gradcam", qkv, dctx, seg, num_seq, keymask, out, heads, d, seq_len, q0, nq, kind, head_mean,
+                   scale, stream);
 }
