@@ -39,10 +39,7 @@ inline char* bp(void* p, size_t row, size_t ld, size_t esz) { return (char*)p + 
 #define TRY(x)              \
     do {                    \
         int rc__ = (x);     \
-        if (rc__) {         \
-            vlmo_defer_reduce = nullptr; \
-            return rc__;    \
-        }                   \
+        if (rc__) return rc__; \
     } while (0)
 
 VlmoEpilogue epi() {
@@ -161,31 +158,59 @@ struct Deferred {
     bool store = false;         // weight-gradient matrices are written, not accumulated (VlmoStackDesc.wgrad_store)
 };
 
-void push_fold(Deferred& D, const PartialReduce& r) {
-    if (!r.ws) return;
-    VlmoColJob j{};
-    j.kind = 0;
-    j.ld = r.ncols;
-    j.src = r.ws;
-    j.rows = r.nblk;
-    j.ncols = r.ncols;
-    j.out[0] = r.out0, j.out[1] = r.out1, j.out[2] = r.out2, j.out[3] = r.out3;
-    j.n0 = r.n0;
-    D.col.push_back(j);
-}
-void push_colsum(Deferred& D, const void* x, int ld, int rows, int ncols, float* out) {
-    VlmoColJob j{};
-    j.kind = 1;
-    j.ld = ld;
-    j.src = x;
-    j.rows = rows;
-    j.ncols = ncols;
-    j.out[0] = out;
-    j.n0 = ncols;
-    D.col.push_back(j);
+// a launcher that had nothing to fold leaves the job empty
+void push_col(Deferred& D, const VlmoColJob& j) {
+    if (j.src && j.rows > 0) D.col.push_back(j);
 }
 void push_tn(Deferred& D, const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N1, int N2) {
     D.tn.push_back(VlmoTnProblem{A, B, C, lda, ldb, ldc, M, N1, N2, 1.f, D.store ? 0 : 1});
+}
+
+// Column workspace of one block of vlmo_stack_bwd (VlmoBlockDesc.ws_main), offsets in floats.  THE definition: the
+// chain below takes its pointers from it and vlmo_stack_bwd_ws_bytes() is its `total`.  Sized for the largest block the
+// descriptor allows -- two experts, norm1 fused with the FFN branch of the block below -- whatever the block at hand is.
+struct StackWs {
+    int64_t ln2;        // norm2 + attention residual branch: [workgroups][4d] partial rows (two fold slots)
+    int64_t resid[2];   // FFN residual branch of expert x: [workgroups][2d] (one fold slot each)
+    int64_t ln1;        // norm1 (+ FFN residual branch of the block below): [workgroups][2d or 4d] (two fold slots)
+    int64_t colpart;    // fc1 bias: column partials of the DGELU epilogue, [ceil(rows / 16)][hidden] per expert, expert 1
+                        // behind expert 0: ceil(a / 16) + ceil(b / 16) <= ceil(M / 16) + 1 rows for a + b <= M
+    int64_t qv;         // q / v bias: per-sequence dq | dv column sums of the attention backward, [sequences][2d]
+    int64_t total;
+    int64_t slot;       // one fold slot: at most VLMO_MAX_PARTIAL_BLOCKS partial rows of 2d columns
+};
+StackWs stack_ws_layout(int M, int d, int hidden, int max_seqs) {
+    StackWs w{};
+    w.slot = reduce_ws_need(2 * d) / 4;
+    w.ln2 = 0;
+    w.resid[0] = w.ln2 + 2 * w.slot;
+    w.resid[1] = w.resid[0] + w.slot;
+    w.ln1 = w.resid[1] + w.slot;
+    w.colpart = w.ln1 + 2 * w.slot;
+    w.qv = w.colpart + (int64_t)((M + 15) / 16 + 1) * hidden;
+    w.total = w.qv + (int64_t)max_seqs * 2 * d;
+    return w;
+}
+int block_seqs(const VlmoBlockDesc* b) {
+    int n = 0;
+    for (int a = 0; a < b->n_attn; ++a) n += b->nseq[a];
+    return n;
+}
+
+// what block_dgrad_chain relies on, checked for all blocks before vlmo_stack_bwd enqueues anything
+int check_block_bwd(const VlmoBlockDesc* b, int i) {
+    VLMO_CHECK_ARG(b->dx2 && b->dx1 && b->dx0, "vlmo_stack_bwd: block %d: null gradient buffers", i);
+    VLMO_CHECK_ARG(b->n_experts >= 1 && b->n_experts <= 2 && b->n_attn >= 1 && b->n_attn <= 2,
+                   "vlmo_stack_bwd: block %d: 1..2 experts and attention launches per block", i);
+    VLMO_CHECK_ARG(b->M > 0 && b->exp_rows[0] >= 0 && (b->n_experts == 1 || b->exp_rows[1] >= 0) &&
+                       (int64_t)b->exp_rows[0] + (b->n_experts == 2 ? b->exp_rows[1] : 0) <= b->M,
+                   "vlmo_stack_bwd: block %d: expert rows exceed M = %d", i, b->M);
+    const int64_t need = stack_ws_layout(b->M, b->d, b->hidden, block_seqs(b)).total * 4;
+    VLMO_CHECK_ARG(b->ws_main && b->ws_bytes >= need,
+                   "vlmo_stack_bwd: block %d: column workspace of %lld bytes is too small: need %lld bytes = "
+                   "vlmo_stack_bwd_ws_bytes(%d, %d, %d, %d)",
+                   i, (long long)b->ws_bytes, (long long)need, b->M, b->d, b->hidden, block_seqs(b));
+    return 0;
 }
 
 // activation-gradient chain of one block on `st`; parameter-gradient work is appended to D.
@@ -196,36 +221,24 @@ void push_tn(Deferred& D, const void* A, int lda, const void* B, int ldb, float*
 int block_dgrad_chain(const VlmoBlockDesc* b, hipStream_t st, Deferred& D, const VlmoBlockDesc* below, bool skip_resid,
                       bool* fused_below) {
     const int M = b->M, d = b->d, hid = b->hidden;
-    const int64_t slot = reduce_ws_need(2 * d);
-    VLMO_CHECK_ARG(b->dx2 && b->dx1 && b->dx0, "vlmo_stack_bwd: null gradient buffers");
-    VLMO_CHECK_ARG(b->n_experts >= 1 && b->n_experts <= 2, "vlmo_stack_bwd: 1..2 experts per block");
-    VLMO_CHECK_ARG(b->ws_main && b->ws_bytes >= (int64_t)(3 + b->n_experts) * slot,
-                   "vlmo_stack_bwd: column workspace too small (need %lld bytes per block)",
-                   (long long)((3 + b->n_experts) * slot));
-    auto ws_slot = [&](int k) { return (float*)((char*)b->ws_main + k * slot); };
-    PartialReduce pend;
-    auto arm = [&]() {
-        pend = PartialReduce{};
-        vlmo_defer_reduce = &pend;
-    };
-    auto collect = [&]() {
-        vlmo_defer_reduce = nullptr;
-        push_fold(D, pend);
-    };
+    const int nseq_all = block_seqs(b);
+    const StackWs W = stack_ws_layout(M, d, hid, nseq_all);
+    const int64_t slot_bytes = W.slot * 4;
+    float* const ws = b->ws_main;
     const void *ag[4], *wg[4], *af[4], *wf[4];
     int32_t rows[4];
     VlmoEpilogue eg[4], ef[4];
-    int64_t colpart_off = (int64_t)(4 + b->n_experts) * slot / 4;       // floats (behind the fold slots)
+    float* colpart = ws + W.colpart;
     for (int x = 0; x < b->n_experts; ++x) {
         const size_t r0 = b->exp_row0[x];
         const int n = rows[x] = b->exp_rows[x];
         if (!skip_resid) {
-            arm();
-            TRY(vlmo_resid_bwd(b->dx2 + r0 * d, bp(b->zd2, r0, d, 2), b->g2,
-                               b->row_index ? b->rs2 : (b->rs2 ? b->rs2 + r0 : nullptr),
-                               b->row_index ? b->row_index + r0 : nullptr, bp(b->dz2, r0, d, 2), b->dg2, b->db2[x], n, d,
-                               b->drop_thresh, b->inv_keep, b->seed + 21 + 2 * x, ws_slot(2 + x), slot, st));
-            collect();
+            VlmoColJob fold{};
+            TRY(resid_bwd_launch(b->dx2 + r0 * d, bp(b->zd2, r0, d, 2), b->g2,
+                                 b->row_index ? b->rs2 : (b->rs2 ? b->rs2 + r0 : nullptr),
+                                 b->row_index ? b->row_index + r0 : nullptr, bp(b->dz2, r0, d, 2), b->dg2, b->db2[x], n, d,
+                                 b->drop_thresh, b->inv_keep, b->seed + 21 + 2 * x, ws + W.resid[x], slot_bytes, &fold, st));
+            push_col(D, fold);
         }
         ag[x] = bp(b->dz2, r0, d, 2);
         wg[x] = b->w2T[x];
@@ -239,23 +252,12 @@ int block_dgrad_chain(const VlmoBlockDesc* b, hipStream_t st, Deferred& D, const
         e.seed = b->seed + 20 + 2 * x;
         e.relu = GELU_DERIV;
         // fc1 bias gradient: the DGELU epilogue leaves column-sum partials (one row per 16 output rows, see
-        // VlmoEpilogue.colpart) behind the (4 + experts) fold slots when the workspace has room; they join the block's
-        // other column folds.  Else: a pass over du.
-        const int nblk64 = (n + 15) / 16;       // 16-row blocks
-        if (b->db1[x] && (colpart_off + (int64_t)nblk64 * hid) * 4 <= b->ws_bytes) {
-            e.colpart = (float*)b->ws_main + colpart_off;
-            colpart_off += (int64_t)nblk64 * hid;
-            VlmoColJob j{};
-            j.kind = 0;
-            j.ld = hid;
-            j.src = e.colpart;
-            j.rows = nblk64;
-            j.ncols = hid;
-            j.out[0] = b->db1[x];
-            j.n0 = hid;
-            D.col.push_back(j);
-        } else {
-            push_colsum(D, bp(b->du, r0, hid, 2), hid, n, hid, b->db1[x]);
+        // VlmoEpilogue.colpart); they join the block's other column folds
+        if (b->db1[x]) {
+            const int nblk16 = (n + 15) / 16;
+            e.colpart = colpart;
+            push_col(D, fold_job(colpart, hid, nblk16, hid, hid, b->db1[x]));
+            colpart += (int64_t)nblk16 * hid;
         }
         af[x] = bp(b->du, r0, hid, 2);
         wf[x] = b->w1T[x];
@@ -267,11 +269,13 @@ int block_dgrad_chain(const VlmoBlockDesc* b, hipStream_t st, Deferred& D, const
     }
     TRY(vlmo_gemm_nt_grouped(VLMO_EPI_DGELU, VLMO_BF16, b->tile, b->n_experts, ag, d, wg, d, rows, hid, d, eg, st));
     TRY(vlmo_gemm_nt_grouped(VLMO_EPI_BIAS, VLMO_BF16, b->tile, b->n_experts, af, hid, wf, hid, rows, d, hid, ef, st));
-    arm();
-    TRY(vlmo_ln_resid_bwd(b->dy2, b->x1, b->n2w, b->mean2, b->rstd2, b->dx2, b->dx1, b->dn2w, b->dn2b, b->zd1, b->g1,
-                          b->rs1, b->row_index, b->dz1, b->dg1, b->dproj_b, b->drop_thresh, b->inv_keep, b->seed + 1, M, d,
-                          ws_slot(0), 2 * slot, st));
-    collect();
+    {
+        VlmoColJob fold{};
+        TRY(ln_bwd_fold(b->dy2, b->x1, b->n2w, b->mean2, b->rstd2, b->dx2, b->dx1, b->dn2w, b->dn2b, b->zd1, b->g1, b->rs1,
+                        b->row_index, b->dz1, b->dg1, b->dproj_b, b->drop_thresh, b->inv_keep, b->seed + 1, M, d, ws + W.ln2,
+                        2 * slot_bytes, &fold, st));
+        push_col(D, fold);
+    }
     {
         VlmoEpilogue e = epi();
         e.out = b->dctx;
@@ -281,32 +285,16 @@ int block_dgrad_chain(const VlmoBlockDesc* b, hipStream_t st, Deferred& D, const
     const float scale = 1.0f / sqrtf((float)(d / b->heads));
     // q_bias / v_bias gradient = column sums of the q and v thirds of dqkv (the k third of the bias is a constant zero,
     // vlmo.py:71-75, and its gradient vanishes anyway: the soft-max is invariant to a shift of the scores along the
-    // keys).  The attention backward leaves them per sequence ([sequences][2d], behind the other column partials of
-    // this block's workspace) and the batched column kernel folds 64-128 rows instead of reading 51 MB of dqkv again.
-    int nseq_all = 0;
-    for (int a = 0; a < b->n_attn; ++a) nseq_all += b->nseq[a];
-    float* qvsum = nullptr;
-    if ((colpart_off + (int64_t)nseq_all * 2 * d) * 4 <= b->ws_bytes) qvsum = (float*)b->ws_main + colpart_off;
+    // keys).  The attention backward leaves them per sequence ([sequences][2d]) and the batched column kernel folds
+    // 64-128 rows instead of reading 51 MB of dqkv again.
+    float* const qvsum = ws + W.qv;
     for (int a = 0, s0 = 0; a < b->n_attn; s0 += b->nseq[a], ++a)
         TRY(vlmo_attn_bwd(b->qkv, b->ctx, b->dctx, b->lse[a], b->lse_stride[a], b->seg[a], b->nseq[a], b->keymask,
-                          b->dqkv, qvsum ? qvsum + (size_t)s0 * 2 * d : nullptr, b->heads, d, b->maxlen[a], scale,
-                          b->attn_drop_thresh, b->attn_inv_keep, b->seed + 11 + b->attn_seed_idx[a], b->attn_seq0[a], st));
+                          b->dqkv, qvsum + (size_t)s0 * 2 * d, b->heads, d, b->maxlen[a], scale, b->attn_drop_thresh,
+                          b->attn_inv_keep, b->seed + 11 + b->attn_seed_idx[a], b->attn_seq0[a], st));
     push_tn(D, b->dz1, d, b->ctx, d, b->dproj_w, d, M, d, d);
     push_tn(D, b->dqkv, 3 * d, b->y1, d, b->dqkv_w, d, M, 3 * d, d);
-    if (qvsum) {
-        VlmoColJob j{};
-        j.kind = 0;
-        j.ld = 2 * d;
-        j.src = qvsum;
-        j.rows = nseq_all;
-        j.ncols = 2 * d;
-        j.out[0] = b->dqkv_b, j.out[1] = b->dqkv_b + 2 * d;
-        j.n0 = d;
-        D.col.push_back(j);
-    } else {
-        push_colsum(D, b->dqkv, 3 * d, M, d, b->dqkv_b);
-        push_colsum(D, bp(b->dqkv, 0, 0, 2) + 4 * (size_t)d, 3 * d, M, d, b->dqkv_b + 2 * d);
-    }
+    push_col(D, fold_job(qvsum, 2 * d, nseq_all, 2 * d, d, b->dqkv_b, b->dqkv_b + 2 * d));
     {
         VlmoEpilogue e = epi();
         e.out = b->dy1;
@@ -314,43 +302,35 @@ int block_dgrad_chain(const VlmoBlockDesc* b, hipStream_t st, Deferred& D, const
         TRY(vlmo_gemm_nt(VLMO_EPI_BIAS, VLMO_BF16, b->tile, b->dqkv, 3 * d, b->qkv_wT, 3 * d, M, d, 3 * d, &e, st));
     }
     const VlmoBlockDesc* n = below;
-    *fused_below = false;
-    if (n && n->M == M && n->d == d && n->dx2 == b->dx0 && n->zd2 && n->dz2 && n->n_experts >= 1 && n->n_experts <= 2 &&
-        n->exp_row0[0] == 0 && (n->n_experts == 1 ? n->exp_rows[0] == M
-                                                   : (n->exp_row0[1] == n->exp_rows[0] && n->exp_rows[0] + n->exp_rows[1] == M)) &&
-        b->ws_bytes >= (int64_t)(4 + b->n_experts) * slot) {
+    *fused_below = n && n->M == M && n->d == d && n->dx2 == b->dx0 && n->zd2 && n->dz2 && n->exp_row0[0] == 0 &&
+                   (n->n_experts == 1 ? n->exp_rows[0] == M
+                                      : (n->exp_row0[1] == n->exp_rows[0] && n->exp_rows[0] + n->exp_rows[1] == M));
+    VlmoColJob fold{};
+    if (*fused_below) {
         const int seg = n->n_experts == 1 ? M : n->exp_row0[1];
-        float* wsf = ws_slot(2 + b->n_experts);        // [workgroups][4d]: two slots
-        int nb0 = 0, nblk = 0;
-        arm();
+        float* wsf = ws + W.ln1;        // [workgroups][4d]
+        int nb0 = 0;
         TRY(ln_resid_seg_bwd(b->dy1, b->x, b->n1w, b->mean1, b->rstd1, b->dx1, b->dx0, b->dn1w, b->dn1b, n->zd2, n->g2,
                              n->rs2, n->row_index, n->dz2, n->dg2, n->drop_thresh, n->inv_keep, n->seed + 21, n->seed + 23,
-                             seg, M, d, wsf, 2 * slot, &nb0, &nblk, st));
-        collect();
+                             seg, M, d, wsf, 2 * slot_bytes, &fold, &nb0, st));
+        push_col(D, fold);
         // the FFN bias gradients of the block below: columns [3d, 4d) of the partial rows of each segment
-        for (int x = 0; x < n->n_experts; ++x) {
-            if (!n->db2[x]) continue;
-            VlmoColJob j{};
-            j.kind = 0;
-            j.ld = 4 * d;
-            j.src = wsf + 3 * d + (x ? (size_t)nb0 * 4 * d : 0);
-            j.rows = x ? nblk - nb0 : nb0;
-            j.ncols = d;
-            j.out[0] = n->db2[x];
-            j.n0 = d;
-            if (j.rows > 0) D.col.push_back(j);
-        }
-        *fused_below = true;
-        return 0;
+        if (n->db2[0]) push_col(D, fold_job(wsf + 3 * d, 4 * d, nb0, d, d, n->db2[0]));
+        if (n->n_experts == 2 && n->db2[1])
+            push_col(D, fold_job(wsf + 3 * d + (size_t)nb0 * 4 * d, 4 * d, fold.rows - nb0, d, d, n->db2[1]));
+    } else {
+        TRY(ln_bwd_fold(b->dy1, b->x, b->n1w, b->mean1, b->rstd1, b->dx1, b->dx0, b->dn1w, b->dn1b, nullptr, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, nullptr, 0, 1.f, 0, M, d, ws + W.ln1, slot_bytes, &fold, st));
+        push_col(D, fold);
     }
-    arm();
-    TRY(vlmo_ln_bwd(b->dy1, 0, nullptr, b->x, b->n1w, b->mean1, b->rstd1, b->dx1, b->dx0, b->dn1w, b->dn1b, M, d,
-                    ws_slot(2 + b->n_experts), slot, st));
-    collect();
     return 0;
 }
 
 }  // namespace
+
+extern "C" int64_t vlmo_stack_bwd_ws_bytes(int M, int d, int hidden, int max_seqs) {
+    return stack_ws_layout(M, d, hidden, max_seqs).total * 4;
+}
 
 extern "C" int vlmo_stack_fwd(const VlmoStackDesc* s, hipStream_t st) {
     VLMO_CHECK_ARG(s && s->blocks && s->n_blocks >= 1, "vlmo_stack_fwd: empty stack");
@@ -362,6 +342,7 @@ extern "C" int vlmo_stack_fwd(const VlmoStackDesc* s, hipStream_t st) {
 extern "C" int vlmo_stack_bwd(const VlmoStackDesc* s, hipStream_t st) {
     VLMO_CHECK_ARG(s && s->blocks && s->n_blocks >= 1, "vlmo_stack_bwd: empty stack");
     const int nb = s->n_blocks;
+    for (int i = 0; i < nb; ++i) TRY(check_block_bwd(&s->blocks[i], i));
     const int batch = s->wgrad_batch >= 1 ? s->wgrad_batch : 1;
     const int nsets = s->n_tmp_sets >= 1 ? s->n_tmp_sets : 1;
     hipStream_t side = s->side_stream ? s->side_stream : st;

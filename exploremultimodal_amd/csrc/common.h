@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
+#include "vlmo_hip.h"
 
 typedef __bf16 bf16;
 typedef _Float16 f16;
@@ -53,32 +55,54 @@ struct DeviceOnce {
 // ---- column reductions -------------------------------------------------------
 // Column sums over the token dimension (bias / gamma / LayerNorm-weight gradients)
 // are done in two stages: each workgroup writes its partial row to a caller-owned
-// workspace [nblk, ncols], then reduce_partials() folds the partials into the
-// outputs with ~8 atomics per address.  (One atomic per column per workgroup straight
-// into the output serialises ~1000 adders on each address: measured 7x slower.)
+// workspace [nblk, ncols], then a FOLD adds the partial rows into the outputs with
+// ~8 atomics per address.  (One atomic per column per workgroup straight into the
+// output serialises ~1000 adders on each address: measured 7x slower.)
+// A fold is described by a kind-0 VlmoColJob (fold_job).  Every launcher that leaves
+// partials takes an optional `VlmoColJob* fold`: null, it launches the fold itself
+// (fold_partials); set, it launches none and hands the job to the caller --
+// vlmo_stack_bwd batches the folds of a block into its vlmo_colwork_multi launch on
+// the side stream (they only produce parameter gradients; launched one by one on the
+// caller's stream, each is a launch + dependency bubble on the critical path).  A
+// launcher with nothing to fold leaves *fold untouched: start from VlmoColJob{}.
 #define VLMO_MAX_PARTIAL_BLOCKS 512
-int reduce_partials(const float* ws, int nblk, int ncols, float* out0, int n0, float* out1, hipStream_t stream,
-                    float* out2 = nullptr, float* out3 = nullptr);
-// vlmo_stack_bwd defers these tiny folds into its batched column launches (they only produce parameter gradients;
-// launched one by one on the caller's stream, each is a launch + dependency bubble on the critical path): while
-// `vlmo_defer_reduce` points at a record, the NEXT reduce_partials() of this thread fills it instead of launching.
-struct PartialReduce {
-    const float* ws = nullptr;
-    int nblk = 0, ncols = 0;
-    float* out0 = nullptr;
-    int n0 = 0;
-    float* out1 = nullptr;
-    float* out2 = nullptr;
-    float* out3 = nullptr;
-};
-extern thread_local PartialReduce* vlmo_defer_reduce;
-// layernorm.hip: LayerNorm backward fused with the residual-branch backward of the block below (see there)
+inline int64_t reduce_ws_need(int ncols) { return (int64_t)VLMO_MAX_PARTIAL_BLOCKS * ncols * 4; }
+// out_k[c % n0] += sum over the rows of src[rows, ld], column c < ncols, k = c / n0
+inline VlmoColJob fold_job(const float* src, int ld, int rows, int ncols, int n0, float* out0, float* out1 = nullptr,
+                           float* out2 = nullptr, float* out3 = nullptr) {
+    VlmoColJob j{};
+    j.kind = 0, j.ld = ld, j.src = src, j.rows = rows, j.ncols = ncols, j.n0 = n0;
+    j.out[0] = out0, j.out[1] = out1, j.out[2] = out2, j.out[3] = out3;
+    return j;
+}
+// elementwise.hip: launches job (ld == ncols) on `stream`, or, with `fold`, only copies it there
+int fold_partials(const VlmoColJob& job, VlmoColJob* fold, hipStream_t stream);
+// elementwise.hip: vlmo_resid_bwd with the optional fold
+int resid_bwd_launch(const float* dx, const void* zd, const float* gamma, const float* row_scale, const int32_t* row_index,
+                     void* dz, float* dgamma, float* dbias, int M, int d, uint32_t drop_thresh, float inv_keep, uint64_t seed,
+                     float* ws, int64_t ws_bytes, VlmoColJob* fold, hipStream_t stream);
+// layernorm.hip: vlmo_ln_bwd / vlmo_ln_resid_bwd with the optional fold (zd, dz null: no residual branch), and the
+// LayerNorm backward fused with the residual-branch backward of the block below (see there)
+int ln_bwd_fold(const void* dy, const float* x, const float* w, const float* mean, const float* rstd, const float* dres,
+                float* dx, float* dw, float* db, const void* zd, const float* gamma, const float* row_scale,
+                const int32_t* row_index, void* dz, float* dgamma, float* dbias, uint32_t drop_thresh, float inv_keep,
+                uint64_t seed, int M, int d, float* ws, int64_t ws_bytes, VlmoColJob* fold, hipStream_t stream);
 int ln_resid_seg_bwd(const void* dy, const float* x, const float* w, const float* mean, const float* rstd,
                      const float* dres, float* dx, float* dw, float* db, const void* zd, const float* gamma,
                      const float* row_scale, const int32_t* row_index, void* dz, float* dgamma, uint32_t drop_thresh,
                      float inv_keep, uint64_t seed0, uint64_t seed1, int seg, int M, int d, float* ws, int64_t ws_bytes,
-                     int* nb0, int* nblk, hipStream_t stream);
-inline int64_t reduce_ws_need(int ncols) { return (int64_t)VLMO_MAX_PARTIAL_BLOCKS * ncols * 4; }
+                     VlmoColJob* fold, int* nb0, hipStream_t stream);
+
+// Kernels templated on the vectors (4 floats) each of 64 lanes holds of a row of d <= 1024 floats:
+// f(std::integral_constant<int, V>{}) for V = 1..4
+template <typename F> inline void dispatch_vpl(int d, F&& f) {
+    switch ((d / 4 + 63) / 64) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
 
 // ---- element traits: the transformer runs bf16, the dVAE runs fp16 --------
 template <typename T> struct Elem;

@@ -20,6 +20,38 @@ extern "C" int vlmo_abi_version(void) { return VLMO_ABI_VERSION; }
 
 namespace {
 
+// The two bodies the single and the batched column kernels share (block (64, 4): threadIdx.y = row lane); how the
+// four row lanes' sums leave the workgroup -- a workspace row or atomics -- is each kernel's own.
+// fold of partial rows: this row lane's share of column c of ws[r0 .. r1, ld]
+__device__ __forceinline__ float fold_column(const float* __restrict__ ws, int ld, int ncols, int c, int r0, int r1) {
+    float a = 0.f;
+    if (c < ncols)
+        for (int r = r0 + threadIdx.y; r < r1; r += 4) a += ws[(size_t)r * ld + c];
+    return a;
+}
+// column sums of a matrix: this row lane's share of the 8 columns from c8 of x[r0 .. r1, ld], four rows in flight
+template <typename T>
+__device__ __forceinline__ void colsum8(const T* __restrict__ x, int ld, int ncols, int c8, int r0, int r1, float (&acc)[8]) {
+    typedef typename Elem<T>::v8 v8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    if (c8 < ncols) {
+        for (int mb = r0 + threadIdx.y; mb < r1; mb += 16) {
+            v8 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int m = mb + 4 * k;
+                v[k] = *(const v8*)(x + (size_t)(m < r1 ? m : mb) * ld + c8);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (mb + 4 * k < r1)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[j] += (float)v[k][j];
+        }
+    }
+}
+
 // out_k[c - k*n0] += sum_b ws[b][c] for k = c / n0 (up to 4 outputs of n0 columns each).  block (64, 4), grid (ncols/64, S)
 __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ ws, int nblk, int ncols,
                                                               float* __restrict__ out0, int n0,
@@ -28,10 +60,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
     __shared__ float red[4][64];
     const int c = blockIdx.x * 64 + threadIdx.x;
     const int r0 = blockIdx.y * rows_per_slice, r1 = min(nblk, r0 + rows_per_slice);
-    float a = 0.f;
-    if (c < ncols)
-        for (int r = r0 + threadIdx.y; r < r1; r += 4) a += ws[(size_t)r * ncols + c];
-    red[threadIdx.y][threadIdx.x] = a;
+    red[threadIdx.y][threadIdx.x] = fold_column(ws, ncols, ncols, c, r0, r1);
     __syncthreads();
     if (threadIdx.y == 0 && c < ncols) {
         const float t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
@@ -117,26 +146,11 @@ __global__ void resid_bwd_kernel(const float* __restrict__ dx, const bf16* __res
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, int ld, float* __restrict__ ws, int M,
                                                      int N, int rows_per_block) {
-    typedef typename Elem<T>::v8 v8;
     __shared__ float red[4][64][8];
     const int c8 = (blockIdx.x * 64 + threadIdx.x) * 8;
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float acc[8];
     const int r0 = blockIdx.y * rows_per_block, r1 = min(M, r0 + rows_per_block);
-    if (c8 < N) {
-        for (int mb = r0 + threadIdx.y; mb < r1; mb += 16) {
-            v8 v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int m = mb + 4 * k;
-                v[k] = *(const v8*)(x + (size_t)(m < r1 ? m : mb) * ld + c8);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (mb + 4 * k < r1)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[j] += (float)v[k][j];
-        }
-    }
+    colsum8(x, ld, N, c8, r0, r1, acc);
 #pragma unroll
     for (int j = 0; j < 8; ++j) red[threadIdx.y][threadIdx.x][j] = acc[j];
     __syncthreads();
@@ -159,7 +173,6 @@ struct ColMulti {
 };
 template <typename T>
 __global__ __launch_bounds__(256) void colwork_multi_kernel(const ColMulti cm) {
-    typedef typename Elem<T>::v8 v8;
     __shared__ float red[4][64][8];
     int ji = 0;
 #pragma unroll
@@ -172,12 +185,8 @@ __global__ __launch_bounds__(256) void colwork_multi_kernel(const ColMulti cm) {
     const int r0 = by * rps, r1 = min(J.rows, r0 + rps);
     const int tx = threadIdx.x, ty = threadIdx.y;
     if (J.kind == 0) {
-        const float* ws = (const float*)J.src;
         const int c = bx * 64 + tx;
-        float a = 0.f;
-        if (c < J.ncols)
-            for (int r = r0 + ty; r < r1; r += 4) a += ws[(size_t)r * J.ld + c];
-        red[ty][tx][0] = a;
+        red[ty][tx][0] = fold_column((const float*)J.src, J.ld, J.ncols, c, r0, r1);
         __syncthreads();
         if (ty == 0 && c < J.ncols) {
             const float t = red[0][tx][0] + red[1][tx][0] + red[2][tx][0] + red[3][tx][0];
@@ -186,24 +195,9 @@ __global__ __launch_bounds__(256) void colwork_multi_kernel(const ColMulti cm) {
             if (base) atomicAdd(base + (c - k * J.n0), t);
         }
     } else {
-        const T* x = (const T*)J.src;
         const int c8 = (bx * 64 + tx) * 8;
-        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (c8 < J.ncols) {
-            for (int mb = r0 + ty; mb < r1; mb += 16) {
-                v8 v[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int m = mb + 4 * k;
-                    v[k] = *(const v8*)(x + (size_t)(m < r1 ? m : mb) * J.ld + c8);
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (mb + 4 * k < r1)
-#pragma unroll
-                        for (int jj = 0; jj < 8; ++jj) acc[jj] += (float)v[k][jj];
-            }
-        }
+        float acc[8];
+        colsum8((const T*)J.src, J.ld, J.ncols, c8, r0, r1, acc);
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) red[ty][tx][jj] = acc[jj];
         __syncthreads();
@@ -525,23 +519,17 @@ __global__ __launch_bounds__(256) void embed_txt_bwd_kernel(const float* __restr
 
 }  // namespace
 
-thread_local PartialReduce* vlmo_defer_reduce = nullptr;
-
-int reduce_partials(const float* ws, int nblk, int ncols, float* out0, int n0, float* out1, hipStream_t stream,
-                    float* out2, float* out3) {
-    if (vlmo_defer_reduce) {
-        PartialReduce* r = vlmo_defer_reduce;
-        vlmo_defer_reduce = nullptr;
-        r->ws = ws, r->nblk = nblk, r->ncols = ncols, r->out0 = out0, r->n0 = n0, r->out1 = out1;
-        r->out2 = out2, r->out3 = out3;
+int fold_partials(const VlmoColJob& job, VlmoColJob* fold, hipStream_t stream) {
+    if (fold) {
+        *fold = job;
         return 0;
     }
-    int slices = nblk >= 64 ? 8 : 1;
-    const int rps = (nblk + slices - 1) / slices;
-    slices = (nblk + rps - 1) / rps;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3((ncols + 63) / 64, slices), dim3(64, 4), 0, stream, ws, nblk, ncols,
-                       out0, n0, out1, rps, out2, out3);
-    VLMO_CHECK_LAUNCH("reduce_partials");
+    int slices = job.rows >= 64 ? 8 : 1;
+    const int rps = (job.rows + slices - 1) / slices;
+    slices = (job.rows + rps - 1) / rps;
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((job.ncols + 63) / 64, slices), dim3(64, 4), 0, stream,
+                       (const float*)job.src, job.rows, job.ncols, job.out[0], job.n0, job.out[1], rps, job.out[2], job.out[3]);
+    VLMO_CHECK_LAUNCH("fold_partials");
     return 0;
 }
 
@@ -557,10 +545,9 @@ int rows_per_block_for(int M, int target_blocks, int mult) {
 
 }  // namespace
 
-extern "C" int vlmo_resid_bwd(const float* dx, const void* zd, const float* gamma, const float* row_scale,
-                              const int32_t* row_index, void* dz, float* dgamma, float* dbias, int M, int d,
-                              uint32_t drop_thresh, float inv_keep,
-                              uint64_t seed, float* ws, int64_t ws_bytes, hipStream_t stream) {
+int resid_bwd_launch(const float* dx, const void* zd, const float* gamma, const float* row_scale, const int32_t* row_index,
+                     void* dz, float* dgamma, float* dbias, int M, int d, uint32_t drop_thresh, float inv_keep, uint64_t seed,
+                     float* ws, int64_t ws_bytes, VlmoColJob* fold, hipStream_t stream) {
     VLMO_CHECK_ARG(dx && dz, "vlmo_resid_bwd: null pointer");
     VLMO_CHECK_ARG(!dgamma || zd, "vlmo_resid_bwd: dgamma needs zd");
     VLMO_CHECK_ARG(M > 0 && d % 4 == 0 && d >= 4 && d <= 4096, "vlmo_resid_bwd: bad shape M=%d d=%d", M, d);
@@ -576,8 +563,16 @@ extern "C" int vlmo_resid_bwd(const float* dx, const void* zd, const float* gamm
                        (const bf16*)zd, gamma, row_scale, row_index, (bf16*)dz, ws, dgamma != nullptr, M, d, rpb, drop_thresh,
                        inv_keep, seed);
     VLMO_CHECK_LAUNCH("vlmo_resid_bwd");
-    if (dgamma || dbias) return reduce_partials(ws, grid, 2 * d, dgamma, d, dbias, stream);
+    if (dgamma || dbias) return fold_partials(fold_job(ws, 2 * d, grid, 2 * d, d, dgamma, dbias), fold, stream);
     return 0;
+}
+
+extern "C" int vlmo_resid_bwd(const float* dx, const void* zd, const float* gamma, const float* row_scale,
+                              const int32_t* row_index, void* dz, float* dgamma, float* dbias, int M, int d,
+                              uint32_t drop_thresh, float inv_keep, uint64_t seed, float* ws, int64_t ws_bytes,
+                              hipStream_t stream) {
+    return resid_bwd_launch(dx, zd, gamma, row_scale, row_index, dz, dgamma, dbias, M, d, drop_thresh, inv_keep, seed, ws,
+                            ws_bytes, nullptr, stream);
 }
 
 extern "C" int vlmo_colsum(int dtype, const void* x, int ld, float* out, int M, int N, float* ws, int64_t ws_bytes,
@@ -598,7 +593,7 @@ extern "C" int vlmo_colsum(int dtype, const void* x, int ld, float* out, int M, 
         return -1;
     }
     VLMO_CHECK_LAUNCH("vlmo_colsum");
-    return reduce_partials(ws, grid.y, N, out, N, nullptr, stream);
+    return fold_partials(fold_job(ws, N, grid.y, N, N, out), nullptr, stream);
 }
 
 extern "C" int vlmo_colwork_multi(int dtype, const VlmoColJob* jobs, int n, hipStream_t stream) {
@@ -716,18 +711,12 @@ extern "C" int vlmo_embed_txt_fwd(const int64_t* ids, const float* word, const f
                                   uint64_t seed, hipStream_t stream) {
     VLMO_CHECK_ARG(ids && word && pos && btype0 && ln_w && ln_b && type0 && x, "vlmo_embed_txt_fwd: null pointer");
     VLMO_CHECK_ARG(B > 0 && T > 0 && d % 4 == 0 && d <= 1024, "vlmo_embed_txt_fwd: bad shape");
-    const int ntok = B * T, vpl = (d / 4 + 63) / 64;
+    const int ntok = B * T;
     const int grid = (ntok + 3) / 4 < 8192 ? (ntok + 3) / 4 : 8192;
-#define ETF(V)                                                                                                         \
-    hipLaunchKernelGGL(embed_txt_fwd_kernel<V>, dim3(grid), dim3(256), 0, stream, ids, word, pos, btype0, ln_w, ln_b,  \
-                       type0, x, xhat, rstd, ntok, T, d, eps, drop_thresh, inv_keep, seed);
-    switch (vpl) {
-        case 1: ETF(1) break;
-        case 2: ETF(2) break;
-        case 3: ETF(3) break;
-        default: ETF(4) break;
-    }
-#undef ETF
+    dispatch_vpl(d, [&](auto V) {
+        hipLaunchKernelGGL(embed_txt_fwd_kernel<decltype(V)::value>, dim3(grid), dim3(256), 0, stream, ids, word, pos, btype0,
+                           ln_w, ln_b, type0, x, xhat, rstd, ntok, T, d, eps, drop_thresh, inv_keep, seed);
+    });
     VLMO_CHECK_LAUNCH("vlmo_embed_txt_fwd");
     return 0;
 }
@@ -738,19 +727,13 @@ extern "C" int vlmo_embed_txt_bwd(const float* dx, const int64_t* ids, const flo
                                   float inv_keep, uint64_t seed, hipStream_t stream) {
     VLMO_CHECK_ARG(dx && ids && xhat && rstd && ln_w, "vlmo_embed_txt_bwd: null pointer");
     VLMO_CHECK_ARG(B > 0 && T > 0 && d % 4 == 0 && d <= 1024, "vlmo_embed_txt_bwd: bad shape");
-    const int ntok = B * T, vpl = (d / 4 + 63) / 64;
+    const int ntok = B * T;
     const int rpb = B >= 64 ? 16 : (B >= 16 ? 8 : 4);         // sequences per workgroup (one position each)
     const int grid = T * ((B + rpb - 1) / rpb);
-#define ETB(V)                                                                                                          \
-    hipLaunchKernelGGL(embed_txt_bwd_kernel<V>, dim3(grid), dim3(256), 0, stream, dx, ids, xhat, rstd, ln_w, dword,    \
-                       dpos, dbtype0, dln_w, dln_b, dtype0, ntok, T, d, rpb, drop_thresh, inv_keep, seed);
-    switch (vpl) {
-        case 1: ETB(1) break;
-        case 2: ETB(2) break;
-        case 3: ETB(3) break;
-        default: ETB(4) break;
-    }
-#undef ETB
+    dispatch_vpl(d, [&](auto V) {
+        hipLaunchKernelGGL(embed_txt_bwd_kernel<decltype(V)::value>, dim3(grid), dim3(256), 0, stream, dx, ids, xhat, rstd,
+                           ln_w, dword, dpos, dbtype0, dln_w, dln_b, dtype0, ntok, T, d, rpb, drop_thresh, inv_keep, seed);
+    });
     VLMO_CHECK_LAUNCH("vlmo_embed_txt_bwd");
     return 0;
 }

@@ -94,8 +94,9 @@ struct ResidArgs {
     // rows [seg, M) form a second segment with its own dropout stream (seed1) whose counters restart at row seg:
     // the per-modality experts of a block below the fusion layer (their FFN residual branches were produced by
     // separate problems of a grouped GEMM).  seg = M: one segment.  No workgroup straddles the boundary, so the
-    // column partials of the two segments are separate rows of the workspace.
-    int seg;
+    // column partials of the two segments are separate rows of the workspace: workgroups [0, nb0) work on segment 0
+    // (ln_bwd_grid)
+    int seg, nb0;
     uint64_t seed1;
 };
 
@@ -124,12 +125,11 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
     uint64_t drop_seed = 0;
     int drop_row0 = 0;
     if constexpr (RESID) {
-        const int nb0 = (ra.seg + rows_per_block - 1) / rows_per_block;
         drop_seed = ra.seed;
-        if ((int)blockIdx.x < nb0) {
+        if ((int)blockIdx.x < ra.nb0) {
             r1 = min(ra.seg, r0 + rows_per_block);
         } else {
-            r0 = ra.seg + ((int)blockIdx.x - nb0) * rows_per_block;
+            r0 = ra.seg + ((int)blockIdx.x - ra.nb0) * rows_per_block;
             r1 = min(M, r0 + rows_per_block);
             drop_seed = ra.seed1;
             drop_row0 = ra.seg;
@@ -251,28 +251,38 @@ extern "C" int vlmo_ln_fwd(const float* x, const float* w, const float* b, void*
                            float* rstd, const int32_t* rowmap, int M, int d, float eps, hipStream_t stream) {
     VLMO_CHECK_ARG(x && w && b && y, "vlmo_ln_fwd: null pointer");
     VLMO_CHECK_ARG(M > 0 && d > 0 && d % 4 == 0 && d <= 1024, "vlmo_ln_fwd: need 0 < d <= 1024, d %% 4 == 0 (d=%d, M=%d)", d, M);
-    const int vpl = (d / 4 + 63) / 64;
     const int grid = min((M + 7) / 8, 8192);
-#define LNF(V)                                                                                        \
-    if (out_f32)                                                                                      \
-        hipLaunchKernelGGL((ln_fwd_kernel<V, true>), dim3(grid), dim3(256), 0, stream, x, w, b, y, mean, rstd, rowmap, M, d, eps); \
-    else                                                                                              \
-        hipLaunchKernelGGL((ln_fwd_kernel<V, false>), dim3(grid), dim3(256), 0, stream, x, w, b, y, mean, rstd, rowmap, M, d, eps);
-    switch (vpl) {
-        case 1: LNF(1) break;
-        case 2: LNF(2) break;
-        case 3: LNF(3) break;
-        default: LNF(4) break;
-    }
-#undef LNF
+    dispatch_vpl(d, [&](auto V) {
+        constexpr int VPL = decltype(V)::value;
+        if (out_f32)
+            hipLaunchKernelGGL((ln_fwd_kernel<VPL, true>), dim3(grid), dim3(256), 0, stream, x, w, b, y, mean, rstd, rowmap, M, d, eps);
+        else
+            hipLaunchKernelGGL((ln_fwd_kernel<VPL, false>), dim3(grid), dim3(256), 0, stream, x, w, b, y, mean, rstd, rowmap, M, d, eps);
+    });
     VLMO_CHECK_LAUNCH("vlmo_ln_fwd");
     return 0;
 }
 
 namespace {
+// The grid of ln_bwd_kernel over the rows [0, seg) + [seg, M) (seg = M: one segment): rpb rows per workgroup, a multiple
+// of the 4 waves; no workgroup straddles the boundary -- workgroups [0, nb0) take segment 0, [nb0, grid) segment 1, and
+// their partial rows of the workspace fold into different gradients; grid <= VLMO_MAX_PARTIAL_BLOCKS.
+struct LnBwdGrid {
+    int rpb, grid, nb0;
+};
+LnBwdGrid ln_bwd_grid(int M, int seg) {
+    int rpb = (M + VLMO_MAX_PARTIAL_BLOCKS - 1) / VLMO_MAX_PARTIAL_BLOCKS;
+    rpb = ((rpb + 3) / 4) * 4;
+    if (rpb < 8) rpb = 8;
+    auto blocks = [&](int rows) { return (rows + rpb - 1) / rpb; };
+    while (blocks(seg) + blocks(M - seg) > VLMO_MAX_PARTIAL_BLOCKS) rpb += 4;
+    return {rpb, blocks(seg) + blocks(M - seg), blocks(seg)};
+}
+
+// ra (optional): the residual branch; its nb0 is set here.  fold, nb0 (optional): see common.h, ln_resid_seg_bwd.
 int ln_bwd_launch(const void* dy, int dy_f32, const int32_t* rowmap, const float* x, const float* w, const float* mean,
                   const float* rstd, const float* dres, float* dx, float* dw, float* db, int M, int d, float* ws,
-                  int64_t ws_bytes, const ResidArgs* ra, float* dgamma, float* dbias, hipStream_t stream) {
+                  int64_t ws_bytes, ResidArgs* ra, float* dgamma, float* dbias, VlmoColJob* fold, hipStream_t stream) {
     VLMO_CHECK_ARG(dy && x && w && mean && rstd && dx, "vlmo_ln_bwd: null pointer");
     VLMO_CHECK_ARG(M > 0 && d > 0 && d % 4 == 0 && d <= 1024, "vlmo_ln_bwd: need 0 < d <= 1024, d %% 4 == 0 (d=%d, M=%d)", d, M);
     const int ncol = ra ? 4 : 2;
@@ -280,34 +290,20 @@ int ln_bwd_launch(const void* dy, int dy_f32, const int32_t* rowmap, const float
     VLMO_CHECK_ARG(!need_w || (ws && ws_bytes >= reduce_ws_need(ncol * d)),
                    "vlmo_ln_bwd: workspace too small (need %lld bytes)", (long long)reduce_ws_need(ncol * d));
     if (!need_w) ws = nullptr;
-    const int vpl = (d / 4 + 63) / 64;
-    int rpb = (M + VLMO_MAX_PARTIAL_BLOCKS - 1) / VLMO_MAX_PARTIAL_BLOCKS;
-    rpb = ((rpb + 3) / 4) * 4;
-    if (rpb < 8) rpb = 8;
-    int grid = (M + rpb - 1) / rpb;
-    if (ra && ra->seg < M) {        // two segments: workgroups do not straddle the boundary
-        for (;; rpb += 4) {
-            grid = (ra->seg + rpb - 1) / rpb + (M - ra->seg + rpb - 1) / rpb;
-            if (grid <= VLMO_MAX_PARTIAL_BLOCKS) break;
-        }
-    }
+    const LnBwdGrid g = ln_bwd_grid(M, ra ? ra->seg : M);
     const ResidArgs none{};
-#define LNB(V)                                                                                         \
-    if (ra)                                                                                            \
-        hipLaunchKernelGGL((ln_bwd_kernel<V, false, true>), dim3(grid), dim3(256), 0, stream, dy, rowmap, x, w, mean, rstd, dres, dx, ws, M, d, rpb, *ra); \
-    else if (dy_f32)                                                                                   \
-        hipLaunchKernelGGL((ln_bwd_kernel<V, true, false>), dim3(grid), dim3(256), 0, stream, dy, rowmap, x, w, mean, rstd, dres, dx, ws, M, d, rpb, none); \
-    else                                                                                               \
-        hipLaunchKernelGGL((ln_bwd_kernel<V, false, false>), dim3(grid), dim3(256), 0, stream, dy, rowmap, x, w, mean, rstd, dres, dx, ws, M, d, rpb, none);
-    switch (vpl) {
-        case 1: LNB(1) break;
-        case 2: LNB(2) break;
-        case 3: LNB(3) break;
-        default: LNB(4) break;
-    }
-#undef LNB
+    if (ra) ra->nb0 = g.nb0;
+    dispatch_vpl(d, [&](auto V) {
+        constexpr int VPL = decltype(V)::value;
+        if (ra)
+            hipLaunchKernelGGL((ln_bwd_kernel<VPL, false, true>), dim3(g.grid), dim3(256), 0, stream, dy, rowmap, x, w, mean, rstd, dres, dx, ws, M, d, g.rpb, *ra);
+        else if (dy_f32)
+            hipLaunchKernelGGL((ln_bwd_kernel<VPL, true, false>), dim3(g.grid), dim3(256), 0, stream, dy, rowmap, x, w, mean, rstd, dres, dx, ws, M, d, g.rpb, none);
+        else
+            hipLaunchKernelGGL((ln_bwd_kernel<VPL, false, false>), dim3(g.grid), dim3(256), 0, stream, dy, rowmap, x, w, mean, rstd, dres, dx, ws, M, d, g.rpb, none);
+    });
     VLMO_CHECK_LAUNCH("vlmo_ln_bwd");
-    if (need_w) return reduce_partials(ws, grid, ncol * d, dw, d, db, stream, dgamma, dbias);
+    if (need_w) return fold_partials(fold_job(ws, ncol * d, g.grid, ncol * d, d, dw, db, dgamma, dbias), fold, stream);
     return 0;
 }
 }  // namespace
@@ -316,7 +312,16 @@ extern "C" int vlmo_ln_bwd(const void* dy, int dy_f32, const int32_t* rowmap, co
                            const float* mean, const float* rstd, const float* dres, float* dx, float* dw, float* db,
                            int M, int d, float* ws, int64_t ws_bytes, hipStream_t stream) {
     return ln_bwd_launch(dy, dy_f32, rowmap, x, w, mean, rstd, dres, dx, dw, db, M, d, ws, ws_bytes, nullptr, nullptr,
-                         nullptr, stream);
+                         nullptr, nullptr, stream);
+}
+
+int ln_bwd_fold(const void* dy, const float* x, const float* w, const float* mean, const float* rstd, const float* dres,
+                float* dx, float* dw, float* db, const void* zd, const float* gamma, const float* row_scale,
+                const int32_t* row_index, void* dz, float* dgamma, float* dbias, uint32_t drop_thresh, float inv_keep,
+                uint64_t seed, int M, int d, float* ws, int64_t ws_bytes, VlmoColJob* fold, hipStream_t stream) {
+    ResidArgs ra{(const bf16*)zd, gamma, row_scale, row_index, (bf16*)dz, drop_thresh, inv_keep, seed, M, 0, 0};
+    return ln_bwd_launch(dy, 0, nullptr, x, w, mean, rstd, dres, dx, dw, db, M, d, ws, ws_bytes, zd ? &ra : nullptr, dgamma,
+                         dbias, fold, stream);
 }
 
 extern "C" int vlmo_ln_resid_bwd(const void* dy, const float* x, const float* w, const float* mean, const float* rstd,
@@ -325,32 +330,24 @@ extern "C" int vlmo_ln_resid_bwd(const void* dy, const float* x, const float* w,
                                  uint32_t drop_thresh, float inv_keep, uint64_t seed, int M, int d, float* ws,
                                  int64_t ws_bytes, hipStream_t stream) {
     VLMO_CHECK_ARG(zd && dz, "vlmo_ln_resid_bwd: null pointer");
-    const ResidArgs ra{(const bf16*)zd, gamma, row_scale, row_index, (bf16*)dz, drop_thresh, inv_keep, seed, M, 0};
-    return ln_bwd_launch(dy, 0, nullptr, x, w, mean, rstd, dres, dx, dw, db, M, d, ws, ws_bytes, &ra, dgamma, dbias, stream);
+    return ln_bwd_fold(dy, x, w, mean, rstd, dres, dx, dw, db, zd, gamma, row_scale, row_index, dz, dgamma, dbias, drop_thresh,
+                       inv_keep, seed, M, d, ws, ws_bytes, nullptr, stream);
 }
 
 // LayerNorm backward of one block fused with the residual-branch backward of the block BELOW it (block.hip: norm1
 // of block i + the FFN branch of block i-1, whose incoming gradient is exactly the dx this kernel writes).  The
 // branch may consist of two row segments [0, seg) and [seg, M) with their own dropout streams (per-modality experts);
 // the caller folds the bias-gradient partials of the segments itself: workspace rows [0, *nb0) belong to segment 0,
-// [*nb0, *nblk) to segment 1, columns [3d, 4d).
+// [*nb0, fold->rows) to segment 1, columns [3d, 4d).
 int ln_resid_seg_bwd(const void* dy, const float* x, const float* w, const float* mean, const float* rstd,
                      const float* dres, float* dx, float* dw, float* db, const void* zd, const float* gamma,
                      const float* row_scale, const int32_t* row_index, void* dz, float* dgamma, uint32_t drop_thresh,
                      float inv_keep, uint64_t seed0, uint64_t seed1, int seg, int M, int d, float* ws, int64_t ws_bytes,
-                     int* nb0, int* nblk, hipStream_t stream) {
-    VLMO_CHECK_ARG(zd && dz && seg >= 1 && seg <= M, "ln_resid_seg_bwd: bad arguments");
-    const ResidArgs ra{(const bf16*)zd, gamma, row_scale, row_index, (bf16*)dz, drop_thresh, inv_keep, seed0, seg, seed1};
-    int rpb = (M + VLMO_MAX_PARTIAL_BLOCKS - 1) / VLMO_MAX_PARTIAL_BLOCKS;
-    rpb = ((rpb + 3) / 4) * 4;
-    if (rpb < 8) rpb = 8;
-    int grid = (M + rpb - 1) / rpb;
-    if (seg < M)
-        for (;; rpb += 4) {
-            grid = (seg + rpb - 1) / rpb + (M - seg + rpb - 1) / rpb;
-            if (grid <= VLMO_MAX_PARTIAL_BLOCKS) break;
-        }
-    *nb0 = (seg + rpb - 1) / rpb;
-    *nblk = grid;
-    return ln_bwd_launch(dy, 0, nullptr, x, w, mean, rstd, dres, dx, dw, db, M, d, ws, ws_bytes, &ra, dgamma, nullptr, stream);
+                     VlmoColJob* fold, int* nb0, hipStream_t stream) {
+    VLMO_CHECK_ARG(zd && dz && seg >= 1 && seg <= M && fold && nb0, "ln_resid_seg_bwd: bad arguments");
+    ResidArgs ra{(const bf16*)zd, gamma, row_scale, row_index, (bf16*)dz, drop_thresh, inv_keep, seed0, seg, 0, seed1};
+    const int rc = ln_bwd_launch(dy, 0, nullptr, x, w, mean, rstd, dres, dx, dw, db, M, d, ws, ws_bytes, &ra, dgamma, nullptr,
+                                 fold, stream);
+    *nb0 = ra.nb0;
+    return rc;
 }

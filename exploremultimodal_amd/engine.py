@@ -647,16 +647,15 @@ _Scratch = namedtuple('_Scratch', 'nsets batch tb ws ws_n dxs')
 def _backward_scratch(dev, nb, M, d, hid, B):
     """Scratch sizing: how many sets of backward temporaries rotate (nsets) and how many blocks share one deferred
     weight-gradient launch (batch), and the three persistent buffers: tb, the bf16 temporaries
-    (dz2 | du(4) | dy2=dctx | dz1 | dqkv(3) | dy1), one set per block in flight; ws, per set the column-fold slots + the
-    du column partials of the DGELU epilogue + the attention backward's per-sequence dq | dv sums (ws_n fp32 each);
-    dxs, the dx ping-pong and dx1."""
+    (dz2 | du(4) | dy2=dctx | dz1 | dqkv(3) | dy1), one set per block in flight; ws, per set the column workspace of a
+    block with up to 2 B attention sequences (ws_n fp32 each, laid out by vlmo_stack_bwd_ws_bytes); dxs, the dx
+    ping-pong and dx1."""
     want = wgrad_batch_for(d, hid)
     nsets = max(1, min(max(TMP_SETS, want + 1), nb))
     batch = max(1, min(want, nsets - 1)) if nb > nsets else max(1, want)
     md = M * d
     tb = _persist(dev, 'tb', nsets * 11 * md, torch.bfloat16)
-    slot = hip.lib().vlmo_reduce_ws_bytes(2 * d)
-    ws_n = 6 * slot // 4 + (M // 16 + 4) * hid + 4 * B * d
+    ws_n = hip.lib().vlmo_stack_bwd_ws_bytes(M, d, hid, 2 * B) // 4
     ws = _persist(dev, 'ws', nsets * ws_n, torch.float32)
     dxs = _persist(dev, 'dx', 3 * md, torch.float32)
     return _Scratch(nsets, batch, tb, ws, ws_n, dxs)

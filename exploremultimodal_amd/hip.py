@@ -167,7 +167,7 @@ _SIGS = {
 }
 
 _lib = None
-ABI_VERSION = 12     # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
+ABI_VERSION = 13     # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
 
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is missing."""
@@ -186,6 +186,8 @@ def lib():
                                'rebuild it (make -C exploremultimodal_amd/csrc)')
         L.vlmo_reduce_ws_bytes.restype = ctypes.c_int64
         L.vlmo_reduce_ws_bytes.argtypes = [_i32]
+        L.vlmo_stack_bwd_ws_bytes.restype = ctypes.c_int64
+        L.vlmo_stack_bwd_ws_bytes.argtypes = [_i32, _i32, _i32, _i32]
         L.vlmo_gemm_tn_ws_bytes.restype = ctypes.c_int64
         L.vlmo_isda_ws_bytes.restype = ctypes.c_int64
         L.vlmo_isda_ws_bytes.argtypes = [_i32, _i32, _i32]
@@ -203,8 +205,8 @@ def lib():
 
 
 def exported_symbols():
-    return ['vlmo_last_error', 'vlmo_abi_version', 'vlmo_reduce_ws_bytes', 'vlmo_gemm_tn_ws_bytes',
-            'vlmo_isda_ws_bytes', 'vlmo_sim_topk_ws_bytes', 'vlmo_randaug_ws_bytes'] + list(_SIGS)
+    return ['vlmo_last_error', 'vlmo_abi_version', 'vlmo_reduce_ws_bytes', 'vlmo_stack_bwd_ws_bytes',
+            'vlmo_gemm_tn_ws_bytes', 'vlmo_isda_ws_bytes', 'vlmo_sim_topk_ws_bytes', 'vlmo_randaug_ws_bytes'] + list(_SIGS)
 
 
 def _check(rc, name):

@@ -82,7 +82,7 @@ typedef struct VlmoEpilogue {
 const char* vlmo_last_error(void);
 /* Version of the struct layouts and signatures below; raised whenever one of them changes
  * (exploremultimodal_amd/hip.py mirrors it as ABI_VERSION and refuses any other). */
-#define VLMO_ABI_VERSION 12
+#define VLMO_ABI_VERSION 13
 int vlmo_abi_version(void);     /* = VLMO_ABI_VERSION of the header the library was built from */
 
 /* C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue.  tile: -1 = pick by shape, 0 = 128x128x64
@@ -230,8 +230,9 @@ int vlmo_colsum(int dtype, const void* x, int ld, float* out, int M, int N, floa
                 int64_t ws_bytes, hipStream_t stream);
 
 /* Column work of several producers in ONE launch (the bias / layer-scale / LayerNorm-weight gradients of one or
- * two transformer blocks):  kind 0 folds fp32 partial rows ws[rows, ncols] (written by vlmo_ln_bwd /
- * vlmo_ln_resid_bwd / vlmo_resid_bwd with defer), kind 1 sums the columns of a bf16/f16 matrix x[rows, ld].
+ * two transformer blocks):  kind 0 folds fp32 partial rows ws[rows, ld] (the column partials the kernels behind
+ * vlmo_ln_bwd / vlmo_ln_resid_bwd / vlmo_resid_bwd, the VLMO_EPI_DGELU epilogue and vlmo_attn_bwd's qv_colsum leave
+ * behind), kind 1 sums the columns of a bf16/f16 matrix x[rows, ld].
  * Column c goes to out[c / n0][c % n0] += sum (out[k] may be NULL). */
 typedef struct VlmoColJob {
     int32_t kind, ld;
@@ -381,8 +382,10 @@ typedef struct VlmoBlockDesc {
  * `side_stream` in batches of `wgrad_batch` blocks, one vlmo_gemm_tn_multi + one vlmo_colwork_multi launch
  * per batch (parameter gradients are ACCUMULATED: zero or pre-load them; with wgrad_store only the vector ones).  Because that work runs later than
  * the block's own chain, the caller gives the k-th block in backward order its own backward temporaries
- * (dz2, du, dz1, dqkv) and column workspace ws_main (>= (3 + n_experts) * vlmo_reduce_ws_bytes(2*d) bytes),
- * rotating over n_tmp_sets > wgrad_batch sets (set k % n_tmp_sets); the call waits for a set's deferred readers
+ * (dz2, du, dz1, dqkv) and column workspace ws_main of ws_bytes >= vlmo_stack_bwd_ws_bytes(M, d, hidden, sequences of
+ * the block's attention launches) bytes, rotating over n_tmp_sets > wgrad_batch sets (set k % n_tmp_sets).  A block
+ * with a smaller workspace is an argument error, found before anything is enqueued (up to ABI 12 such a block ran with
+ * extra passes over du and dqkv and without the fusion across blocks).  The call waits for a set's deferred readers
  * before reusing it and joins the side stream before it returns control of the buffers.  grad_ready (optional,
  * [n_blocks] hipEvent_t handles from vlmo_event_create): event i is recorded when block i's parameter gradients
  * are complete, so a gradient all-reduce on another stream can start per block (vlmo_stream_wait_event). */
@@ -394,6 +397,10 @@ typedef struct VlmoStackDesc {
     hipStream_t side_stream;
     void* const* grad_ready;
 } VlmoStackDesc;
+/* Bytes of VlmoBlockDesc.ws_main for a block of M rows and at most max_seqs attention sequences: the partial rows of the
+ * LayerNorm / residual-branch folds, the fc1-bias column partials and the per-sequence q / v bias sums, sized for two
+ * experts and the fusion with the block below whatever the block has.  Monotone in every argument. */
+int64_t vlmo_stack_bwd_ws_bytes(int M, int d, int hidden, int max_seqs);
 int vlmo_stack_fwd(const VlmoStackDesc* s, hipStream_t stream);
 int vlmo_stack_bwd(const VlmoStackDesc* s, hipStream_t stream);
 int vlmo_event_create(void** out);

@@ -43,3 +43,27 @@ def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(hip, '_lib', None)
     with pytest.raises(RuntimeError, match='no CPU fallback'):
         hip.lib()
+
+
+def test_stack_bwd_workspace_layout():
+    """vlmo_stack_bwd_ws_bytes, the one definition of a block's column workspace (no GPU: a host function): monotone in
+    every argument; no larger than the formula the engine carried before it, at the Base (B = 64) and Large (B = 32)
+    training shapes with 2 B sequences; and room for the six fold slots of the partial rows at the smallest stack
+    shape of the suite (mini, one 5-token text + one image: M = 22)."""
+    L = hip.lib()
+    ws = L.vlmo_stack_bwd_ws_bytes
+    base = (16704, 768, 3072, 128)
+    for k, steps in enumerate([(1, 15, 16, 17), (4, 64), (8, 1024), (1, 2, 64)]):
+        prev = ws(*base)
+        for s_ in steps:
+            a = list(base)
+            a[k] += s_
+            assert ws(*a) >= prev, (k, s_)
+            prev = ws(*a)
+        assert prev > ws(*base), k
+
+    def old_bytes(M, d, hid, B):
+        return 4 * (6 * L.vlmo_reduce_ws_bytes(2 * d) // 4 + (M // 16 + 4) * hid + 4 * B * d)
+    for M, d, hid, seqs in [base, (8352, 1024, 4096, 64)]:
+        assert 0 < ws(M, d, hid, seqs) <= old_bytes(M, d, hid, seqs // 2), (M, d, hid, seqs)
+    assert ws(22, 128, 512, 2) >= 6 * L.vlmo_reduce_ws_bytes(2 * 128)

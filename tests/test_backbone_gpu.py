@@ -279,6 +279,49 @@ def test_native_stack_path_equals_per_block_path(preset, B):
         assert (gs[n] - gb[n]).abs().max().item() <= tol, (n, (gs[n] - gb[n]).abs().max().item(), tol)
 
 
+def test_stack_bwd_refuses_a_short_column_workspace(monkeypatch):
+    """A two-block stack (the smallest with a block below), described the way the engine does it except that every
+    block's ws_bytes is one fold slot short of vlmo_stack_bwd_ws_bytes: vlmo_stack_bwd returns an argument error that
+    names the bytes it needs, before it enqueues anything -- the backward temporaries and the dx buffers, which the
+    first kernels of a chain write, still hold what was put there.  The same pass with the whole workspace runs."""
+    from exploremultimodal_amd import engine, hip
+    model, mc = build('mini')
+    assert mc.depth == 2
+    B = 2
+    kw = modes(mc, synth.synth_batch(mc, B, seed=80), B)['vl']
+    L = hip.lib()
+    slot = L.vlmo_reduce_ws_bytes(2 * mc.embed_dim)
+    wire, seen = engine._wire_temporaries, {}
+
+    def short_wire(D, k, nb, md, sc, dxo, dx_in):
+        wire(D, k, nb, md, sc, dxo, dx_in)
+        nseq = sum(D.nseq[a] for a in range(D.n_attn))
+        assert D.ws_bytes == L.vlmo_stack_bwd_ws_bytes(D.M, D.d, D.hidden, 2 * B)
+        seen.setdefault('need', []).append(L.vlmo_stack_bwd_ws_bytes(D.M, D.d, D.hidden, nseq))
+        D.ws_bytes -= slot
+        if k == 0:
+            seen['bufs'] = [sc.tb, sc.dxs, dx_in]
+            for t in seen['bufs']:
+                t.fill_(3.0)
+    monkeypatch.setattr(engine, '_wire_temporaries', short_wire)
+    x, _ = model.forward_features(**kw)
+    with pytest.raises(RuntimeError) as e:
+        x.sum().backward()
+    torch.cuda.synchronize()
+    assert len(seen['need']) == 2
+    assert 'vlmo_stack_bwd' in str(e.value) and 'rc=-1' in str(e.value), str(e.value)
+    assert f'need {seen["need"][-1]} bytes' in str(e.value), str(e.value)       # block 0 is checked first
+    for t in seen['bufs']:
+        assert bool((t == 3.0).all())
+    monkeypatch.setattr(engine, '_wire_temporaries', wire)
+    for p in model.parameters():
+        p.grad = None
+    x, _ = model.forward_features(**kw)
+    x.sum().backward()
+    torch.cuda.synchronize()
+    assert all(torch.isfinite(p.grad).all() for p in model.parameters() if p.grad is not None)
+
+
 @pytest.mark.parametrize('stack', [True, False])
 def test_one_stream_and_side_stream_schedules_give_the_same_gradients(stack):
     """engine.OVERLAP_WGRAD: weight gradients and column folds on the caller's stream (the default without a gradient

@@ -677,6 +677,58 @@ def test_colwork_multi():
     _close(cs2, 1 + x2.float().sum(0), 1e-5, 1e-3, 'colsum small')
 
 
+def test_two_segment_ln_resid_bias_folds_with_a_ragged_segment_boundary():
+    """norm1's backward fused with the FFN residual branch of the block below, two segments (ln_resid_seg_bwd): the
+    workgroups' partial rows [0, nb0) fold into the text expert's fc2 bias gradient and [nb0, grid) into the image
+    expert's.  mini, B = 3 with 9-token texts: 27 text rows + 51 image rows, 8 rows per workgroup, so the last
+    workgroup of either segment is short (3 rows) and the boundary is no multiple of the row block; nb0 = 4 of 11.
+    Through StackFn: one call per pass (the fused kernel) against one call per block (engine.USE_STACK off: no block
+    below, each expert's vlmo_resid_bwd folds its own rows).  Same dropout / drop-path seed; 1e-4 of the gradient's
+    largest element, the bound of test_native_stack_path_equals_per_block_path (summation order only)."""
+    from functools import partial
+    from exploremultimodal_amd import engine
+    from exploremultimodal_amd.vlmo import VLMO, LayerNorm
+    from oracle import synth
+    mc = synth.make_config('mini').model
+    model = VLMO(img_size=mc.img_size, patch_size=mc.patch_size, in_chans=mc.in_chans, num_classes=mc.num_classes,
+                 embed_dim=mc.embed_dim, depth=mc.depth, num_heads=mc.num_heads, mlp_ratio=mc.mlp_ratio,
+                 qkv_bias=mc.qkv_bias, drop_rate=0.1, attn_drop_rate=0.1, drop_path_rate=0.1,
+                 norm_layer=partial(LayerNorm, eps=1e-12), init_values=mc.init_values, vocab_size=mc.vocab_size,
+                 max_text_len=mc.max_text_len, fusion_layer=mc.fusion_layer)
+    model.load_state_dict(synth.synth_backbone_state_dict(mc, 0, [('v', 'l', 'vl')] * mc.depth), strict=True)
+    model = model.to(DEV).train()
+    assert mc.fusion_layer == 1 and mc.depth == 2           # block 0: two experts, under a block that fuses with it
+    B, T, P = 3, 9, synth.num_img_tokens(mc)
+    assert (B * T) % 8 and (B * P) % 8
+    g = torch.Generator().manual_seed(41)
+    kw = dict(img=torch.randn(B, 3, mc.img_size, mc.img_size, generator=g).to(DEV),
+              txt=torch.randint(1000, mc.vocab_size, (B, T), generator=g).to(DEV),
+              img_attn_masks=torch.ones(B, P, dtype=torch.int64, device=DEV),
+              txt_attn_masks=torch.ones(B, T, dtype=torch.int64, device=DEV))
+    R = torch.randn(B, T + P, mc.embed_dim, generator=g).to(DEV)
+    names = ['blocks.0.mlp.l.fc2.bias', 'blocks.0.mlp.v.fc2.bias']
+    got = {}
+    old = engine.USE_STACK
+    try:
+        for stack in (True, False):
+            engine.USE_STACK = stack
+            for p in model.parameters():
+                p.grad = None
+            torch.manual_seed(5)
+            x, _ = model.forward_features(**kw)
+            (x * R).sum().backward()
+            torch.cuda.synchronize()
+            pg = dict(model.named_parameters())
+            got[stack] = [pg[n].grad.detach().clone() for n in names]
+    finally:
+        engine.USE_STACK = old
+    for n, a, b in zip(names, got[True], got[False]):
+        err, top = (a - b).abs().max().item(), b.abs().max().item()
+        print(n, 'max |stack - per block| =', err, 'largest element', top)
+        assert top > 0
+        assert err <= 1e-4 * top, (n, err, top)
+
+
 def test_gemm_tn_multi_more_tiles_than_one_placement_table():
     """20 problems x 64 tiles = 1 280 workgroups: more than one launch's placement table (1 024) holds, so the call
     is cut into several launches; mixed reduction lengths exercise the cost-balanced XCD placement."""
