@@ -375,6 +375,54 @@ __global__ void embed_img_bwd_kernel(const float* __restrict__ dx, const uint8_t
     }
 }
 
+// One text row of the forward, a wave per row: token `id` at position t -> packed row m of x / xhat / rstd.  The fixed-
+// length kernel (m = b * T + t) and the row-table kernel (m = packed row of a variable-length batch) share it.
+template <int VPL>
+__device__ __forceinline__ void embed_txt_row(int64_t id, int t, int m, int lane, int nv, const float* __restrict__ word,
+                                              const float* __restrict__ pos, const float* __restrict__ btype0,
+                                              const float* __restrict__ ln_w, const float* __restrict__ ln_b,
+                                              const float* __restrict__ type0, float* __restrict__ x,
+                                              float* __restrict__ xhat, float* __restrict__ rstd, int d, float eps,
+                                              uint32_t thresh, float inv_keep, uint64_t seed) {
+    f32x4 v[VPL];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        const int i = lane + 64 * j;
+        if (i < nv) {
+            v[j] = ((const f32x4*)(word + (size_t)id * d))[i] + ((const f32x4*)btype0)[i] +
+                   ((const f32x4*)(pos + (size_t)t * d))[i];
+            s += v[j][0] + v[j][1] + v[j][2] + v[j][3];
+        } else {
+            v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+    const float mu = wave_sum(s) / d;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j)
+        if (lane + 64 * j < nv)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q += (v[j][k] - mu) * (v[j][k] - mu);
+    const float rs = rsqrtf(wave_sum(q) / d + eps);
+    if (lane == 0 && rstd) rstd[m] = rs;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        const int i = lane + 64 * j;
+        if (i < nv) {
+            const f32x4 xh = (v[j] - mu) * rs;
+            if (xhat) ((f32x4*)(xhat + (size_t)m * d))[i] = xh;
+            f32x4 o = xh * ((const f32x4*)ln_w)[i] + ((const f32x4*)ln_b)[i];
+            if (thresh) {
+                const uint64_t bits = drop_bits4(seed, ((uint64_t)m * d >> 2) + i);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] = drop_keep(bits, k, thresh) ? o[k] * inv_keep : 0.f;
+            }
+            ((f32x4*)(x + (size_t)m * d))[i] = o + ((const f32x4*)type0)[i];
+        }
+    }
+}
+
 template <int VPL>
 __global__ __launch_bounds__(256) void embed_txt_fwd_kernel(const int64_t* __restrict__ ids, const float* __restrict__ word,
                                                             const float* __restrict__ pos, const float* __restrict__ btype0,
@@ -384,45 +432,109 @@ __global__ __launch_bounds__(256) void embed_txt_fwd_kernel(const int64_t* __res
                                                             int T, int d, float eps, uint32_t thresh, float inv_keep,
                                                             uint64_t seed) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nv = d >> 2;
-    for (int m = blockIdx.x * 4 + wave; m < ntok; m += gridDim.x * 4) {
-        const int64_t id = ids[m];
-        const int t = m % T;
-        f32x4 v[VPL];
-        float s = 0.f;
+    for (int m = blockIdx.x * 4 + wave; m < ntok; m += gridDim.x * 4)
+        embed_txt_row<VPL>(ids[m], m % T, m, lane, nv, word, pos, btype0, ln_w, ln_b, type0, x, xhat, rstd, d, eps, thresh,
+                           inv_keep, seed);
+}
+
+// Row-table form (variable-length text): packed row m embeds ids[src[m]], src[m] = b * T + t of the [B, T] id matrix;
+// positions a sample does not have are in no row.  The dropout stream is indexed by the PACKED row.
+template <int VPL>
+__global__ __launch_bounds__(256) void embed_txt_rows_fwd_kernel(const int64_t* __restrict__ ids, const int32_t* __restrict__ src,
+                                                                 const float* __restrict__ word, const float* __restrict__ pos,
+                                                                 const float* __restrict__ btype0, const float* __restrict__ ln_w,
+                                                                 const float* __restrict__ ln_b, const float* __restrict__ type0,
+                                                                 float* __restrict__ x, float* __restrict__ xhat,
+                                                                 float* __restrict__ rstd, int nrows, int T, int d, float eps,
+                                                                 uint32_t thresh, float inv_keep, uint64_t seed) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nv = d >> 2;
+    for (int m = blockIdx.x * 4 + wave; m < nrows; m += gridDim.x * 4) {
+        const int s = src[m];
+        embed_txt_row<VPL>(ids[s], s % T, m, lane, nv, word, pos, btype0, ln_w, ln_b, type0, x, xhat, rstd, d, eps, thresh,
+                           inv_keep, seed);
+    }
+}
+
+// Backward state of a wave: the column sums it gathers over its rows (ln_w, ln_b, type0 and de = d e, which is both the
+// position row's and btype0's gradient) and its slice of ln_w.
+template <int VPL>
+struct EmbedTxtAcc {
+    f32x4 aw[VPL], ab[VPL], at[VPL], ae[VPL], ww[VPL];
+    __device__ __forceinline__ void init(const float* __restrict__ ln_w, int lane, int nv) {
 #pragma unroll
         for (int j = 0; j < VPL; ++j) {
-            const int i = lane + 64 * j;
-            if (i < nv) {
-                v[j] = ((const f32x4*)(word + (size_t)id * d))[i] + ((const f32x4*)btype0)[i] +
-                       ((const f32x4*)(pos + (size_t)t * d))[i];
-                s += v[j][0] + v[j][1] + v[j][2] + v[j][3];
-            } else {
-                v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
+            aw[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            ab[j] = aw[j];
+            at[j] = aw[j];
+            ae[j] = aw[j];
+            ww[j] = (lane + 64 * j < nv) ? ((const f32x4*)ln_w)[lane + 64 * j] : aw[j];
         }
-        const float mu = wave_sum(s) / d;
-        float q = 0.f;
+    }
+    // the wave's sums into the workgroup's LDS image red[wave][lnw, lnb, type0, de][VPL * 256]
+    __device__ __forceinline__ void spill(float (*red)[VPL * 256], int lane) const {
 #pragma unroll
         for (int j = 0; j < VPL; ++j)
-            if (lane + 64 * j < nv)
 #pragma unroll
-                for (int k = 0; k < 4; ++k) q += (v[j][k] - mu) * (v[j][k] - mu);
-        const float rs = rsqrtf(wave_sum(q) / d + eps);
-        if (lane == 0 && rstd) rstd[m] = rs;
-#pragma unroll
-        for (int j = 0; j < VPL; ++j) {
-            const int i = lane + 64 * j;
-            if (i < nv) {
-                const f32x4 xh = (v[j] - mu) * rs;
-                if (xhat) ((f32x4*)(xhat + (size_t)m * d))[i] = xh;
-                f32x4 o = xh * ((const f32x4*)ln_w)[i] + ((const f32x4*)ln_b)[i];
-                if (thresh) {
-                    const uint64_t bits = drop_bits4(seed, ((uint64_t)m * d >> 2) + i);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) o[k] = drop_keep(bits, k, thresh) ? o[k] * inv_keep : 0.f;
-                }
-                ((f32x4*)(x + (size_t)m * d))[i] = o + ((const f32x4*)type0)[i];
+            for (int k = 0; k < 4; ++k) {
+                const int idx = (j * 64 + lane) * 4 + k;
+                red[0][idx] = aw[j][k];
+                red[1][idx] = ab[j][k];
+                red[2][idx] = at[j][k];
+                red[3][idx] = ae[j][k];
             }
+    }
+};
+
+// LDS index of column c in the images EmbedTxtAcc::spill writes
+__device__ __forceinline__ int embed_txt_red_index(int c) {
+    const int i = c >> 2;
+    return ((i >> 6) * 64 + (i & 63)) * 4 + (c & 3);
+}
+
+// One text row of the backward, a wave per row: packed row m holds token `id`; adds the row's terms to A and scatters
+// d e into the word row (padding_idx 0 gets none).
+template <int VPL>
+__device__ __forceinline__ void embed_txt_row_bwd(int64_t id, int m, int lane, int nv, const float* __restrict__ dx,
+                                                  const float* __restrict__ xhat, const float* __restrict__ rstd,
+                                                  float* __restrict__ dword, EmbedTxtAcc<VPL>& A, int d, uint32_t thresh,
+                                                  float inv_keep, uint64_t seed) {
+    const float rs = rstd[m];
+    f32x4 g[VPL], xh[VPL];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        const int i = lane + 64 * j;
+        g[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        xh[j] = g[j];
+        if (i < nv) {
+            f32x4 gy = ((const f32x4*)(dx + (size_t)m * d))[i];
+            A.at[j] += gy;
+            if (thresh) {
+                const uint64_t bits = drop_bits4(seed, ((uint64_t)m * d >> 2) + i);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) gy[k] = drop_keep(bits, k, thresh) ? gy[k] * inv_keep : 0.f;
+            }
+            xh[j] = ((const f32x4*)(xhat + (size_t)m * d))[i];
+            A.aw[j] += gy * xh[j];
+            A.ab[j] += gy;
+            g[j] = gy * A.ww[j];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                s1 += g[j][k];
+                s2 += g[j][k] * xh[j][k];
+            }
+        }
+    }
+    const float c1 = wave_sum(s1) / d, c2 = wave_sum(s2) / d;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        const int i = lane + 64 * j;
+        if (i < nv) {
+            const f32x4 de = rs * (g[j] - c1 - xh[j] * c2);
+            A.ae[j] += de;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (dword && id != 0) atomicAdd(dword + (size_t)id * d + 4 * i + k, de[k]);   // padding_idx = 0
         }
     }
 }
@@ -438,15 +550,8 @@ __global__ __launch_bounds__(256) void embed_txt_bwd_kernel(const float* __restr
                                                             uint64_t seed) {
     __shared__ float red[4][4][VPL * 256];   // [wave][lnw, lnb, type0, btype0 (= position row of this workgroup)]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nv = d >> 2;
-    f32x4 aw[VPL], ab[VPL], at[VPL], ae[VPL], ww[VPL];
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-        aw[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        ab[j] = aw[j];
-        at[j] = aw[j];
-        ae[j] = aw[j];
-        ww[j] = (lane + 64 * j < nv) ? ((const f32x4*)ln_w)[lane + 64 * j] : aw[j];
-    }
+    EmbedTxtAcc<VPL> A;
+    A.init(ln_w, lane, nv);
     // a workgroup owns ONE position t and `rows_per_block` sequences: the position-embedding gradient of its rows is one
     // register accumulator (ae) folded once per workgroup, not an atomic per row (64 sequences on every position row:
     // 106 -> ~40 us); the word-embedding rows are scattered per token as before
@@ -454,66 +559,79 @@ __global__ __launch_bounds__(256) void embed_txt_bwd_kernel(const float* __restr
     const int b0 = (blockIdx.x / T) * rows_per_block, b1 = min(ntok / T, b0 + rows_per_block);
     for (int bq = b0 + wave; bq < b1; bq += 4) {
         const int m = bq * T + t;
-        const int64_t id = ids[m];
-        const float rs = rstd[m];
-        f32x4 g[VPL], xh[VPL];
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < VPL; ++j) {
-            const int i = lane + 64 * j;
-            g[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-            xh[j] = g[j];
-            if (i < nv) {
-                f32x4 gy = ((const f32x4*)(dx + (size_t)m * d))[i];
-                at[j] += gy;
-                if (thresh) {
-                    const uint64_t bits = drop_bits4(seed, ((uint64_t)m * d >> 2) + i);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) gy[k] = drop_keep(bits, k, thresh) ? gy[k] * inv_keep : 0.f;
-                }
-                xh[j] = ((const f32x4*)(xhat + (size_t)m * d))[i];
-                aw[j] += gy * xh[j];
-                ab[j] += gy;
-                g[j] = gy * ww[j];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    s1 += g[j][k];
-                    s2 += g[j][k] * xh[j][k];
-                }
-            }
-        }
-        const float c1 = wave_sum(s1) / d, c2 = wave_sum(s2) / d;
-#pragma unroll
-        for (int j = 0; j < VPL; ++j) {
-            const int i = lane + 64 * j;
-            if (i < nv) {
-                const f32x4 de = rs * (g[j] - c1 - xh[j] * c2);
-                ae[j] += de;
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (dword && id != 0) atomicAdd(dword + (size_t)id * d + 4 * i + k, de[k]);   // padding_idx = 0
-            }
-        }
+        embed_txt_row_bwd<VPL>(ids[m], m, lane, nv, dx, xhat, rstd, dword, A, d, thresh, inv_keep, seed);
     }
-#pragma unroll
-    for (int j = 0; j < VPL; ++j)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int idx = (j * 64 + lane) * 4 + k;
-            red[wave][0][idx] = aw[j][k];
-            red[wave][1][idx] = ab[j][k];
-            red[wave][2][idx] = at[j][k];
-            red[wave][3][idx] = ae[j][k];
-        }
+    A.spill(red[wave], lane);
     __syncthreads();
     float* outs[4] = {dln_w, dln_b, dtype0, dbtype0};
     for (int c = threadIdx.x; c < d; c += 256) {
-        const int i = c >> 2, idx = ((i >> 6) * 64 + (i & 63)) * 4 + (c & 3);
+        const int idx = embed_txt_red_index(c);
 #pragma unroll
         for (int w = 0; w < 4; ++w)
             if (outs[w]) atomicAdd(outs[w] + c, red[0][w][idx] + red[1][w][idx] + red[2][w][idx] + red[3][w][idx]);
         // dbtype0 and the position row both sum `de` (red[..][3]): the position row of THIS workgroup's t
         if (dpos) atomicAdd(dpos + (size_t)t * d + c, red[0][3][idx] + red[1][3][idx] + red[2][3][idx] + red[3][3][idx]);
+    }
+}
+
+// Row-table form of the backward.  Workgroup (chunk, t) owns position t of `rows_per_block` sequences, as above; sequence
+// b has that position when t < off[b + 1] - off[b] and keeps it in packed row off[b] + t.  The column sums leave the
+// workgroup as ONE workspace row ws[blockIdx.x][lnw | lnb | type0 | de][d] (plain stores, a workgroup without rows
+// stores zeros); embed_txt_fold_kernel adds the rows up in index order, so the result does not depend on the order the
+// workgroups ran in.  Grid = maxlen * chunks: no workgroup for a position no sample has.
+template <int VPL>
+__global__ __launch_bounds__(256) void embed_txt_rows_bwd_kernel(const float* __restrict__ dx, const int64_t* __restrict__ ids,
+                                                                 const int32_t* __restrict__ off, const float* __restrict__ xhat,
+                                                                 const float* __restrict__ rstd, const float* __restrict__ ln_w,
+                                                                 float* __restrict__ dword, float* __restrict__ ws, int B, int T,
+                                                                 int maxlen, int d, int rows_per_block, uint32_t thresh,
+                                                                 float inv_keep, uint64_t seed) {
+    __shared__ float red[4][4][VPL * 256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nv = d >> 2;
+    EmbedTxtAcc<VPL> A;
+    A.init(ln_w, lane, nv);
+    const int t = blockIdx.x % maxlen;
+    const int b0 = (blockIdx.x / maxlen) * rows_per_block, b1 = min(B, b0 + rows_per_block);
+    for (int bq = b0 + wave; bq < b1; bq += 4) {
+        const int r0 = off[bq];
+        if (t >= off[bq + 1] - r0) continue;                   // wave-uniform: the whole wave works on one row
+        embed_txt_row_bwd<VPL>(ids[(size_t)bq * T + t], r0 + t, lane, nv, dx, xhat, rstd, dword, A, d, thresh, inv_keep,
+                               seed);
+    }
+    A.spill(red[wave], lane);
+    __syncthreads();
+    float* row = ws + (size_t)blockIdx.x * 4 * d;
+    for (int c = threadIdx.x; c < d; c += 256) {
+        const int idx = embed_txt_red_index(c);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) row[w * d + c] = red[0][w][idx] + red[1][w][idx] + red[2][w][idx] + red[3][w][idx];
+    }
+}
+
+// Fixed-order fold of the workspace rows of embed_txt_rows_bwd_kernel.  block (64, 4), grid (ceil(d / 64), 1 + maxlen):
+// blockIdx.y = 0 adds ALL rows into dln_w, dln_b, dtype0, dbtype0; blockIdx.y = 1 + t adds the `de` part of position t's
+// rows (one per chunk, row = chunk * maxlen + t) into dpos[t].  Every output element has one owner thread (plain +=).
+__global__ __launch_bounds__(256) void embed_txt_fold_kernel(const float* __restrict__ ws, int nrows, int maxlen, int d,
+                                                             float* __restrict__ dln_w, float* __restrict__ dln_b,
+                                                             float* __restrict__ dtype0, float* __restrict__ dbtype0,
+                                                             float* __restrict__ dpos) {
+    __shared__ float red[4][4][64];          // [part][row lane][column]
+    const int c = blockIdx.x * 64 + threadIdx.x, ld = 4 * d;
+    if (blockIdx.y == 0) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) red[w][threadIdx.y][threadIdx.x] = fold_column(ws + w * d, ld, d, c, 0, nrows);
+        __syncthreads();
+        if (c < d) {
+            const int w = threadIdx.y;
+            float* out = w == 0 ? dln_w : (w == 1 ? dln_b : (w == 2 ? dtype0 : dbtype0));
+            if (out) out[c] += red[w][0][threadIdx.x] + red[w][1][threadIdx.x] + red[w][2][threadIdx.x] + red[w][3][threadIdx.x];
+        }
+    } else {
+        const int t = blockIdx.y - 1;
+        red[0][threadIdx.y][threadIdx.x] = fold_column(ws + (size_t)t * ld + 3 * d, maxlen * ld, d, c, 0, nrows / maxlen);
+        __syncthreads();
+        if (threadIdx.y == 0 && c < d && dpos)
+            dpos[(size_t)t * d + c] += red[0][0][threadIdx.x] + red[0][1][threadIdx.x] + red[0][2][threadIdx.x] + red[0][3][threadIdx.x];
     }
 }
 
@@ -735,5 +853,54 @@ extern "C" int vlmo_embed_txt_bwd(const float* dx, const int64_t* ids, const flo
                            ln_w, dword, dpos, dbtype0, dln_w, dln_b, dtype0, ntok, T, d, rpb, drop_thresh, inv_keep, seed);
     });
     VLMO_CHECK_LAUNCH("vlmo_embed_txt_bwd");
+    return 0;
+}
+
+namespace {
+int embed_txt_rows_rpb(int B) { return B >= 64 ? 16 : (B >= 16 ? 8 : 4); }   // sequences per workgroup, as vlmo_embed_txt_bwd
+}  // namespace
+
+extern "C" int vlmo_embed_txt_rows_fwd(const int64_t* ids, const int32_t* src, const float* word, const float* pos,
+                                       const float* btype0, const float* ln_w, const float* ln_b, const float* type0,
+                                       float* x, float* xhat, float* rstd, int nrows, int T, int d, float eps,
+                                       uint32_t drop_thresh, float inv_keep, uint64_t seed, hipStream_t stream) {
+    VLMO_CHECK_ARG(ids && src && word && pos && btype0 && ln_w && ln_b && type0 && x, "vlmo_embed_txt_rows_fwd: null pointer");
+    VLMO_CHECK_ARG(nrows > 0 && T > 0 && d % 4 == 0 && d > 0 && d <= 1024, "vlmo_embed_txt_rows_fwd: bad shape");
+    const int grid = (nrows + 3) / 4 < 8192 ? (nrows + 3) / 4 : 8192;
+    dispatch_vpl(d, [&](auto V) {
+        hipLaunchKernelGGL(embed_txt_rows_fwd_kernel<decltype(V)::value>, dim3(grid), dim3(256), 0, stream, ids, src, word, pos,
+                           btype0, ln_w, ln_b, type0, x, xhat, rstd, nrows, T, d, eps, drop_thresh, inv_keep, seed);
+    });
+    VLMO_CHECK_LAUNCH("vlmo_embed_txt_rows_fwd");
+    return 0;
+}
+
+extern "C" int64_t vlmo_embed_txt_rows_ws_bytes(int B, int maxlen, int d) {
+    if (B <= 0 || maxlen <= 0 || d <= 0) return 0;
+    const int rpb = embed_txt_rows_rpb(B);
+    return (int64_t)maxlen * ((B + rpb - 1) / rpb) * 4 * d * (int64_t)sizeof(float);
+}
+
+extern "C" int vlmo_embed_txt_rows_bwd(const float* dx, const int64_t* ids, const int32_t* off, const float* xhat,
+                                       const float* rstd, const float* ln_w, float* dword, float* dpos, float* dbtype0,
+                                       float* dln_w, float* dln_b, float* dtype0, float* ws, int64_t ws_bytes, int B, int T,
+                                       int maxlen, int d, uint32_t drop_thresh, float inv_keep, uint64_t seed,
+                                       hipStream_t stream) {
+    VLMO_CHECK_ARG(dx && ids && off && xhat && rstd && ln_w && ws, "vlmo_embed_txt_rows_bwd: null pointer");
+    VLMO_CHECK_ARG(B > 0 && T > 0 && maxlen > 0 && maxlen <= T && d % 4 == 0 && d > 0 && d <= 1024,
+                   "vlmo_embed_txt_rows_bwd: bad shape B=%d T=%d maxlen=%d d=%d", B, T, maxlen, d);
+    VLMO_CHECK_ARG(ws_bytes >= vlmo_embed_txt_rows_ws_bytes(B, maxlen, d),
+                   "vlmo_embed_txt_rows_bwd: workspace too small (need %lld bytes)",
+                   (long long)vlmo_embed_txt_rows_ws_bytes(B, maxlen, d));
+    const int rpb = embed_txt_rows_rpb(B);
+    const int grid = maxlen * ((B + rpb - 1) / rpb);
+    dispatch_vpl(d, [&](auto V) {
+        hipLaunchKernelGGL(embed_txt_rows_bwd_kernel<decltype(V)::value>, dim3(grid), dim3(256), 0, stream, dx, ids, off, xhat,
+                           rstd, ln_w, dword, ws, B, T, maxlen, d, rpb, drop_thresh, inv_keep, seed);
+    });
+    VLMO_CHECK_LAUNCH("vlmo_embed_txt_rows_bwd");
+    hipLaunchKernelGGL(embed_txt_fold_kernel, dim3((d + 63) / 64, 1 + maxlen), dim3(64, 4), 0, stream, (const float*)ws, grid,
+                       maxlen, d, dln_w, dln_b, dtype0, dbtype0, dpos);
+    VLMO_CHECK_LAUNCH("vlmo_embed_txt_rows_bwd");
     return 0;
 }

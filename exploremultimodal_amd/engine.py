@@ -146,14 +146,120 @@ class _PlanStatic:
                                     B + torch.arange(B).repeat_interleave(P)]).to(torch.int32).to(device)
 
 
-class Plan:
-    """Row layout + attention launches of one backbone pass."""
+def check_txt_lens(txt_lens, B, T):
+    """The row counts of a variable-length text batch as a tuple of B python ints, each in [1, T] (host only: no
+    device is asked).  A sequence of ints or a CPU integer tensor is taken; a wrong count, a value outside [1, T], a
+    non-integer or a device tensor raises ValueError."""
+    if torch.is_tensor(txt_lens):
+        if txt_lens.device.type != 'cpu':
+            raise ValueError('txt_lens must live on the host (python ints or a CPU tensor): reading a device tensor '
+                             'would stall the pass (objectives.attach_text_lens builds it from the host batch)')
+        if txt_lens.dim() != 1 or txt_lens.dtype.is_floating_point or txt_lens.dtype in (torch.bool, torch.complex64,
+                                                                                          torch.complex128):
+            raise ValueError(f'txt_lens must be a 1-D integer tensor, got {txt_lens.dtype} {tuple(txt_lens.shape)}')
+        txt_lens = txt_lens.tolist()
+    try:
+        lens = tuple(txt_lens)
+    except TypeError:
+        raise ValueError(f'txt_lens must be a sequence of {B} ints, got {type(txt_lens).__name__}') from None
+    if len(lens) != B:
+        raise ValueError(f'txt_lens has {len(lens)} entries for a batch of {B}')
+    for n in lens:
+        if isinstance(n, bool) or not isinstance(n, int):
+            raise ValueError(f'txt_lens must hold python ints, got {n!r}')
+        if not 1 <= n <= T:
+            raise ValueError(f'txt_lens entries must be in [1, {T}], got {n}')
+    return lens
 
-    def __init__(self, B, T, P, device, txt_mask=None, img_mask=None):
+
+class _PlanRagged:
+    """Shape-only part of a plan whose text sample b keeps its first lens[b] positions (1 <= lens[b] <= T) as packed
+    rows off[b] .. off[b + 1]; the image rows start at nt = sum(lens).  The tables are functions of the host lengths
+    alone.  They are built with device ops whose sizes come from the host, out of ONE small device tensor (off, int32
+    [B + 1]: the caller's, or uploaded here from pinned memory without waiting), so building asks the device nothing;
+    the last few are kept, so the passes of a step that share a batch share its tables."""
+    _cache = {}
+    KEEP = 8
+
+    @classmethod
+    def get(cls, B, T, P, device, lens, off=None):
+        key = (B, T, P, str(device), lens)
+        st = cls._cache.pop(key, None)
+        if st is None:
+            st = cls(B, T, P, device, lens, off)
+            while len(cls._cache) >= cls.KEEP:
+                cls._cache.pop(next(iter(cls._cache)))
+        cls._cache[key] = st                      # most recently used last
+        return st
+
+    def __init__(self, B, T, P, device, lens, off=None):
+        dev = torch.device(device)
+        host_off = [0]
+        for n in lens:
+            host_off.append(host_off[-1] + n)
+        nt = self.nt = host_off[-1]
+        self.maxT = max(lens)
+        if off is None:
+            off = torch.tensor(host_off, dtype=torch.int32)
+            if dev.type != 'cpu':
+                off = off.pin_memory().to(dev, non_blocking=True)
+        elif off.device != dev or off.dtype != torch.int32 or tuple(off.shape) != (B + 1,):
+            raise ValueError(f'txt_off must be an int32 [{B + 1}] tensor on {dev}')
+        self.off = off
+        i32 = torch.int32
+        ar = torch.arange(B, dtype=i32, device=dev)
+        z = torch.zeros(B, dtype=i32, device=dev)
+        row0, ln = off[:-1], off[1:] - off[:-1]
+
+        def seg(a0, la, b0, lb):
+            return torch.stack([a0, la, b0, lb], 1).to(i32).contiguous()
+
+        pl = torch.full((B,), P, dtype=i32, device=dev)
+        img0 = nt + ar * P
+        self.seg_txt = seg(row0, ln, z, z)
+        self.seg_img = seg(img0, pl, z, z) if P else None
+        self.seg_vl = seg(row0, ln, img0, pl) if P else None
+        self.seg_sep = torch.cat([self.seg_img, self.seg_txt]).contiguous() if P else None
+        # sample and in-sequence position of every packed text row
+        rb = torch.repeat_interleave(torch.arange(B, device=dev), ln.long(), output_size=nt)
+        tt = torch.arange(nt, device=dev) - row0.long()[rb]
+        self.src = (rb * T + tt).to(i32)          # packed text row -> b * T + t: ids, key mask (vlmo_embed_txt_rows_fwd)
+        N = T + P
+        bi = torch.arange(B, device=dev).repeat_interleave(P)
+        rm_i = bi * N + T + torch.arange(P, device=dev).repeat(B)
+        self.rowmap = torch.cat([rb * N + tt, rm_i]).to(i32)
+        self.row_group = torch.cat([rb, B + bi]).to(i32)
+
+
+class Plan:
+    """Row layout + attention launches of one backbone pass.
+
+    txt_lens (a tuple from check_txt_lens): text sample b has its first txt_lens[b] positions only; nt = sum(txt_lens),
+    the segment descriptors, the row map into [B, T + P, d], the drop-path groups and the key mask are those of the
+    packed rows, and maxT is the longest text (T without lengths).  T stays the width of the id matrix and of the
+    output.  txt_off: the prefix sums of txt_lens as an int32 [B + 1] tensor already on the device (optional)."""
+
+    def __init__(self, B, T, P, device, txt_mask=None, img_mask=None, txt_lens=None, txt_off=None):
         self.B, self.T, self.P = B, T, P
-        self.nt, self.ni = B * T, B * P
-        self.M = self.nt + self.ni
         self.device = device
+        self.txt_lens = txt_lens
+        if txt_lens is not None:
+            assert T > 0
+            st = _PlanRagged.get(B, T, P, device, txt_lens, txt_off)
+            self.nt, self.ni, self.maxT = st.nt, B * P, st.maxT
+            self.M = self.nt + self.ni
+            self.seg_txt, self.seg_img, self.seg_vl, self.seg_sep = st.seg_txt, st.seg_img, st.seg_vl, st.seg_sep
+            self.rowmap, self.row_group = st.rowmap, st.row_group
+            self.txt_src, self.txt_off = st.src, st.off
+            parts = [txt_mask.reshape(-1).to(torch.int32)[st.src.long()] if txt_mask is not None
+                     else torch.ones(self.nt, dtype=torch.int32, device=device)]
+            if P:
+                parts.append(img_mask.reshape(-1).to(torch.int32) if img_mask is not None
+                             else torch.ones(self.ni, dtype=torch.int32, device=device))
+            self.keymask = torch.cat(parts).contiguous() if (txt_mask is not None or img_mask is not None) else None
+            return
+        self.nt, self.ni, self.maxT = B * T, B * P, T
+        self.M = self.nt + self.ni
         st = _PlanStatic.get(B, T, P, device)
         self.seg_txt, self.seg_img, self.seg_vl, self.seg_sep = st.seg_txt, st.seg_img, st.seg_vl, st.seg_sep
         self.rowmap, self.row_group = st.rowmap, st.row_group
@@ -168,13 +274,14 @@ class Plan:
         self.keymask = torch.cat(parts).contiguous() if (txt_mask is not None or img_mask is not None) else None
 
     def attn_launches(self, fused):
+        # the maximum a launch reports picks its attention kernel: with text lengths it is the batch's true maximum
         if fused and self.seg_vl is not None:
-            return [(self.seg_vl, self.B, self.T + self.P)]
+            return [(self.seg_vl, self.B, self.maxT + self.P)]
         if self.seg_sep is not None:
-            return [(self.seg_sep, 2 * self.B, max(self.T, self.P))]
+            return [(self.seg_sep, 2 * self.B, max(self.maxT, self.P))]
         out = []
         if self.seg_txt is not None:
-            out.append((self.seg_txt, self.B, self.T))
+            out.append((self.seg_txt, self.B, self.maxT))
         if self.seg_img is not None:
             out.append((self.seg_img, self.B, self.P))
         return out
@@ -370,7 +477,7 @@ def _split_backward_attention(D, meta):
     stride = D.lse_stride[0]
     D.n_attn = 2
     D.nseq[0], D.nseq[1] = pl.B, pl.B
-    D.maxlen[0], D.maxlen[1] = pl.P, pl.T
+    D.maxlen[0], D.maxlen[1] = pl.P, pl.maxT                             # the text launch's true maximum
     D.lse_stride[1] = stride
     D.seg[1] = D.seg[0] + pl.B * 16                                       # 4 int32 per sequence
     # the text launch regenerates the attention-dropout mask of ITS sequences of the shared forward launch
@@ -925,7 +1032,9 @@ class FinalNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, plan, out_shape, eps=LN_EPS):
         M, d = x.shape
-        out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+        # a plan with text lengths leaves the rows of the dropped positions unwritten: they are exactly 0
+        full = M == plan.B * (plan.T + plan.P)
+        out = (torch.empty if full else torch.zeros)(out_shape, dtype=torch.float32, device=x.device)
         mean, rstd = torch.empty(M, device=x.device), torch.empty(M, device=x.device)
         hip.ln_fwd(x, w, b, out, mean, rstd, plan.rowmap, M, d, eps)
         ctx.plan = plan
@@ -961,8 +1070,12 @@ class EmbedFn(torch.autograd.Function):
         if T:
             xhat = torch.empty((pl.nt, d), dtype=torch.float32, device=dev)
             rstd = torch.empty((pl.nt,), dtype=torch.float32, device=dev)
-            hip.embed_txt_fwd(ids, word, tpos, btype[0], ln_w, ln_b, type_emb[0], x[:pl.nt], xhat, rstd, B, T, d,
-                              meta['txt_eps'], drop=drop, seed=seed + 1)
+            if pl.txt_lens is None:
+                hip.embed_txt_fwd(ids, word, tpos, btype[0], ln_w, ln_b, type_emb[0], x[:pl.nt], xhat, rstd, B, T, d,
+                                  meta['txt_eps'], drop=drop, seed=seed + 1)
+            else:
+                hip.embed_txt_rows_fwd(ids, pl.txt_src, word, tpos, btype[0], ln_w, ln_b, type_emb[0], x[:pl.nt], xhat,
+                                       rstd, pl.nt, T, d, meta['txt_eps'], drop=drop, seed=seed + 1)
             saved['txt'] = (xhat, rstd)
         if P:
             npatch = P - 1
@@ -1008,8 +1121,12 @@ class EmbedFn(torch.autograd.Function):
             xhat, rstd = saved['txt']
             dword, dtpos_full, dbtype, dlnw, dlnb = views[k:k + 5]
             k += 5
-            hip.embed_txt_bwd(dx[:pl.nt], meta['ids'], xhat, rstd, ln_w, dword, dtpos_full[:T], dbtype[0], dlnw, dlnb,
-                              dtype_emb[0], B, T, d, drop=drop, seed=seed + 1)
+            if pl.txt_lens is None:
+                hip.embed_txt_bwd(dx[:pl.nt], meta['ids'], xhat, rstd, ln_w, dword, dtpos_full[:T], dbtype[0], dlnw, dlnb,
+                                  dtype_emb[0], B, T, d, drop=drop, seed=seed + 1)
+            else:
+                hip.embed_txt_rows_bwd(dx[:pl.nt], meta['ids'], pl.txt_off, xhat, rstd, ln_w, dword, dtpos_full[:T],
+                                       dbtype[0], dlnw, dlnb, dtype_emb[0], B, T, pl.maxT, d, drop=drop, seed=seed + 1)
             g[6], g[7], g[8], g[9], g[10] = dword, dtpos_full, dbtype, dlnw, dlnb
         if P:
             patches = saved['img']

@@ -116,6 +116,8 @@ _SIGS = {
                            _u64, _vp],
     'vlmo_embed_txt_fwd': [_vp] * 10 + [_i32, _i32, _i32, _f32, _u32, _f32, _u64, _vp],
     'vlmo_embed_txt_bwd': [_vp] * 11 + [_i32, _i32, _i32, _u32, _f32, _u64, _vp],
+    'vlmo_embed_txt_rows_fwd': [_vp] * 11 + [_i32, _i32, _i32, _f32, _u32, _f32, _u64, _vp],
+    'vlmo_embed_txt_rows_bwd': [_vp] * 13 + [_i64, _i32, _i32, _i32, _i32, _u32, _f32, _u64, _vp],
     'vlmo_conv2d_nhwc': [_i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp,
                          ctypes.POINTER(Epilogue), _vp],
     'vlmo_dvae_im2col': [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
@@ -167,7 +169,7 @@ _SIGS = {
 }
 
 _lib = None
-ABI_VERSION = 13     # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
+ABI_VERSION = 14     # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
 
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is missing."""
@@ -196,6 +198,8 @@ def lib():
         L.vlmo_sim_topk_ws_bytes.argtypes = [_i32, _i32, _i32, _i32]
         L.vlmo_randaug_ws_bytes.restype = ctypes.c_int64
         L.vlmo_randaug_ws_bytes.argtypes = [_i32]
+        L.vlmo_embed_txt_rows_ws_bytes.restype = ctypes.c_int64
+        L.vlmo_embed_txt_rows_ws_bytes.argtypes = [_i32, _i32, _i32]
         for name, sig in _SIGS.items():
             fn = getattr(L, name)
             fn.argtypes = sig
@@ -206,7 +210,8 @@ def lib():
 
 def exported_symbols():
     return ['vlmo_last_error', 'vlmo_abi_version', 'vlmo_reduce_ws_bytes', 'vlmo_stack_bwd_ws_bytes',
-            'vlmo_gemm_tn_ws_bytes', 'vlmo_isda_ws_bytes', 'vlmo_sim_topk_ws_bytes', 'vlmo_randaug_ws_bytes'] + list(_SIGS)
+            'vlmo_gemm_tn_ws_bytes', 'vlmo_isda_ws_bytes', 'vlmo_sim_topk_ws_bytes', 'vlmo_randaug_ws_bytes',
+            'vlmo_embed_txt_rows_ws_bytes'] + list(_SIGS)
 
 
 def _check(rc, name):
@@ -438,6 +443,27 @@ def embed_txt_bwd(dx, ids, xhat, rstd, ln_w, dword, dpos, dbtype0, dln_w, dln_b,
                                   _p(dpos), _p(dbtype0), _p(dln_w), _p(dln_b), _p(dtype0), B, T, d,
                                   drop[0], drop[1], _seed64(seed), _stream())
     _check(rc, 'vlmo_embed_txt_bwd')
+
+
+def embed_txt_rows_fwd(ids, src, word, pos, btype0, ln_w, ln_b, type0, x, xhat, rstd, nrows, T, d, eps,
+                       drop=(0, 1.0), seed=0):
+    """Row-table form of embed_txt_fwd: packed row m embeds ids.view(-1)[src[m]] at position src[m] % T."""
+    rc = lib().vlmo_embed_txt_rows_fwd(_p(ids), _p(src), _p(word), _p(pos), _p(btype0), _p(ln_w), _p(ln_b),
+                                       _p(type0), _p(x), _p(xhat), _p(rstd), nrows, T, d, eps, drop[0],
+                                       drop[1], _seed64(seed), _stream())
+    _check(rc, 'vlmo_embed_txt_rows_fwd')
+
+
+def embed_txt_rows_bwd(dx, ids, off, xhat, rstd, ln_w, dword, dpos, dbtype0, dln_w, dln_b, dtype0, B, T, maxlen, d,
+                       drop=(0, 1.0), seed=0):
+    """Row-table form of embed_txt_bwd: off int32 [B + 1] (device) = prefix sums of the row counts, maxlen their
+    maximum (a host int).  The vector gradients are summed in a fixed order through a scratch of partial rows."""
+    nbytes = lib().vlmo_embed_txt_rows_ws_bytes(B, maxlen, d)
+    ws = _scratch('embed_txt_rows', dx.device, nbytes, 1 << 20)
+    rc = lib().vlmo_embed_txt_rows_bwd(_p(dx), _p(ids), _p(off), _p(xhat), _p(rstd), _p(ln_w), _p(dword),
+                                       _p(dpos), _p(dbtype0), _p(dln_w), _p(dln_b), _p(dtype0), _p(ws),
+                                       ws.numel() * 4, B, T, maxlen, d, drop[0], drop[1], _seed64(seed), _stream())
+    _check(rc, 'vlmo_embed_txt_rows_bwd')
 
 
 # ------------------------------------------------------------------ dVAE encoder / decoder

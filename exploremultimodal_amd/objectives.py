@@ -88,6 +88,27 @@ def attach_row_indices(batch):
     return batch
 
 
+def attach_text_lens(batch):
+    """Input hand-off companion for variable-length text (``config.train.ragged_text``, VLMO.forward_features'
+    ``txt_lens``): on the HOST copy of a batch, before its upload, read how many positions every text needs from
+    ``text_mask`` [B, T].  ``_txt_lens`` = a tuple of B python ints, 1 + the index of the last non-zero of the row (a
+    hole inside a text stays a masked key of the pass) and 1 for an all-zero row; it is not a tensor, so it stays on the
+    host through the upload as pack_images' 'table' does.  ``_txt_off`` = their prefix sums, int32 [B + 1], uploaded
+    with the batch.  A batch without the keys, or whose mask already lives on a device, runs at full width.  The keys
+    describe THIS batch's ``text_mask``: whoever edits it afterwards drops both."""
+    tm = batch.get('text_mask')
+    if torch.is_tensor(tm) and not tm.is_cuda and tm.dim() == 2:
+        T = tm.shape[1]
+        nz = tm != 0
+        last = T - 1 - nz.flip(1).to(torch.int64).argmax(1)
+        lens = torch.where(nz.any(1), last + 1, torch.ones_like(last))
+        batch['_txt_lens'] = tuple(int(n) for n in lens.tolist())
+        off = torch.zeros(tm.shape[0] + 1, dtype=torch.int32)
+        off[1:] = lens.cumsum(0)
+        batch['_txt_off'] = off
+    return batch
+
+
 def _vocab_head_loss(model, head, feats, labels, vocab):
     """Loss / logits / accuracy of a vocabulary head on gathered rows (objectives.py:57-68, 571-582).
 
@@ -199,9 +220,15 @@ def sample_itm_negatives(batch, sim_dict=None):
 def itm_negative_batch(batch, img_neg_idx, txt_neg_idx):
     """The 2B-pair negative batch of compute_itm (objectives.py:277-293): (negative image, text), (image, negative text)."""
     txt_ids, txt_mask, img = batch['text_ids'], batch['text_mask'], batch['image']
-    return {'text_ids': torch.cat([txt_ids, txt_ids[txt_neg_idx]], dim=0),
-            'text_mask': torch.cat([txt_mask, txt_mask[txt_neg_idx]], dim=0),
-            'image': torch.cat([img[img_neg_idx], img], dim=0)}
+    neg = {'text_ids': torch.cat([txt_ids, txt_ids[txt_neg_idx]], dim=0),
+           'text_mask': torch.cat([txt_mask, txt_mask[txt_neg_idx]], dim=0),
+           'image': torch.cat([img[img_neg_idx], img], dim=0)}
+    lens = batch.get('_txt_lens')
+    if lens is not None:
+        # variable-length text: the first B texts are the batch's own; the negative texts are gathered on the device, so
+        # the host does not know their lengths and they count the full width
+        neg['_txt_lens'] = tuple(lens) + (txt_ids.shape[1],) * txt_ids.shape[0]
+    return neg
 
 
 def compute_itm(model, batch, sim_dict=None):

@@ -116,8 +116,10 @@ class DataLoaderX(DataLoader):
         self.batch = next(self.iter, None)
         if isinstance(self.batch, dict):
             # rows the MLM / MIM heads will gather, listed while the masks are still host tensors (objectives.attach_row_indices)
-            from .objectives import attach_row_indices
+            from .objectives import attach_row_indices, attach_text_lens
             attach_row_indices(self.batch)
+            # ... and the row count of every text (objectives.attach_text_lens): used only under config.train.ragged_text
+            attach_text_lens(self.batch)
         if self.batch is not None and self._gpu:
             with torch.cuda.stream(self.stream):
                 self.batch = _walk(self.batch, self._to_device)

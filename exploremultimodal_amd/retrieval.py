@@ -21,7 +21,7 @@ def _itc_head(model):
     return head
 
 
-def _encode(model, n, chunk_batch, infer_mode, route, batch_size):
+def _encode(model, n, chunk_batch, infer_mode, route, batch_size, ragged=False):
     head = _itc_head(model)
     if batch_size < 1:
         raise ValueError('batch_size must be >= 1')
@@ -31,7 +31,8 @@ def _encode(model, n, chunk_batch, infer_mode, route, batch_size):
         with torch.no_grad():
             feats = []
             for b0 in range(0, n, batch_size):
-                co = model.infer(chunk_batch(b0, min(n, b0 + batch_size)), infer_mode=infer_mode)['co_feats']
+                co = model.infer(chunk_batch(b0, min(n, b0 + batch_size)), infer_mode=infer_mode,
+                                 ragged=ragged)['co_feats']
                 f = head(co[:, 0], route)               # unit rows (heads.ITCHead)
                 if f.dtype != torch.float32:            # half-precision head under autocast: unit length in fp32
                     f = torch.nn.functional.normalize(f.float(), dim=-1)
@@ -46,10 +47,25 @@ def encode_images(model, images, batch_size=64):
     return _encode(model, images.shape[0], lambda a, b: {'image': images[a:b]}, 'img_only', 'v', batch_size)
 
 
-def encode_texts(model, text_ids, text_mask, batch_size=256):
-    """text_ids, text_mask [N, T] -> L2-normalised fp32 ITC features [N, itc_dim] (eval mode, no gradients)."""
-    return _encode(model, text_ids.shape[0], lambda a, b: {'text_ids': text_ids[a:b], 'text_mask': text_mask[a:b]},
-                   'txt_only', 'l', batch_size)
+def encode_texts(model, text_ids, text_mask, batch_size=256, ragged=False):
+    """text_ids, text_mask [N, T] -> L2-normalised fp32 ITC features [N, itc_dim] (eval mode, no gradients).
+
+    ragged=True runs every text with the positions up to its last unmasked one only (VLMO.forward_features' txt_lens):
+    the [CLS] feature is the padded pass's up to the summation order inside attention.  The lengths come from the host
+    when text_mask is a CPU tensor (it is then uploaded chunk by chunk); a mask that lives on the device is read back ONCE per call (a device-to-host
+    synchronisation: this is an evaluation utility, not a training step)."""
+    lens = None
+    if ragged:
+        from .objectives import attach_text_lens
+        lens = attach_text_lens({'text_mask': text_mask.cpu()})['_txt_lens']
+
+    def chunk(a, b):
+        out = {'text_ids': text_ids[a:b], 'text_mask': text_mask[a:b].to(text_ids.device)}     # a host mask is uploaded
+        if lens is not None:
+            out['_txt_lens'] = lens[a:b]
+        return out
+
+    return _encode(model, text_ids.shape[0], chunk, 'txt_only', 'l', batch_size, ragged=ragged)
 
 
 def _sim_topk_cpu(q, g, k, scale, chunk_rows=None):
@@ -119,12 +135,12 @@ def recall_at_k(indices, txt2img, direction, ks=(1, 5, 10)):
 
 
 def evaluate_retrieval(model, images, text_ids, text_mask, txt2img, ks=(1, 5, 10), image_batch_size=64,
-                       text_batch_size=256, scale=1.0, splits=0):
+                       text_batch_size=256, scale=1.0, splits=0, ragged_text=False):
     """Recall of both directions for a gallery of images and captions -> {'ir_r<k>': text-to-image, 'tr_r<k>':
     image-to-text for k in ks, 'r_mean': their mean} (ViLT's / VLMo's metric names) as Python floats.  Two sim_topk calls,
-    one device-to-host read."""
+    one device-to-host read.  ragged_text: encode_texts' ``ragged`` (one more read when text_mask lives on the device)."""
     i_feat = encode_images(model, images, image_batch_size)
-    t_feat = encode_texts(model, text_ids, text_mask, text_batch_size)
+    t_feat = encode_texts(model, text_ids, text_mask, text_batch_size, ragged=ragged_text)
     return recall_from_features(i_feat, t_feat, txt2img, ks, scale, splits)
 
 

@@ -423,12 +423,27 @@ class VLMO(nn.Module):
         return h.view(B, N, self.embed_dim)
 
     def forward_features(self, img=None, txt=None, img_attn_masks=None, txt_attn_masks=None, bool_masked_pos=None,
-                         fusion_layer=None, img_token_type_idx=1):
-        """vlmo.py:357-414 -> (x fp32 [B, N, d], mask)."""
+                         fusion_layer=None, img_token_type_idx=1, txt_lens=None, txt_off=None):
+        """vlmo.py:357-414 -> (x fp32 [B, N, d], mask).
+
+        txt_lens (not a reference option; text-only and image-text passes): B python ints or a CPU integer tensor, the
+        row count of every text, each in [1, T].  Text b then runs with its first txt_lens[b] positions only: the
+        others are not embedded, are no keys and are in no GEMM; their output rows are exactly 0 and get no gradient.
+        The existing positions get what the padded pass gives whenever txt_attn_masks[b, t >= txt_lens[b]] == 0 (up to
+        the fp32 summation order inside attention; the dropout streams differ).  The returned mask is unchanged.
+        ValueError for a wrong count, a value outside [1, T] or a device tensor (engine.check_txt_lens): the lengths are
+        host values so that no pass asks the device (objectives.attach_text_lens).  txt_off: optionally their prefix
+        sums as an int32 [B + 1] tensor already on the device (attach_text_lens' ``_txt_off``)."""
         dev = self._check_inputs(img, txt, img_attn_masks, txt_attn_masks)
         seed = self._seed()
         L = len(self.blocks)
         P = self.patch_embed.num_patches + 1
+        if txt_lens is not None:
+            if txt is None:
+                raise ValueError('txt_lens needs a text input')
+            txt_lens = engine.check_txt_lens(txt_lens, txt.shape[0], txt.shape[1])
+        elif txt_off is not None:
+            raise ValueError('txt_off needs txt_lens')
         if txt is None:
             B = img.shape[0]
             plan = engine.Plan(B, 0, P, dev, None, img_attn_masks)
@@ -439,7 +454,7 @@ class VLMO(nn.Module):
             return out, img_attn_masks
         if img is None:
             B, T = txt.shape
-            plan = engine.Plan(B, T, 0, dev, txt_attn_masks, None)
+            plan = engine.Plan(B, T, 0, dev, txt_attn_masks, None, txt_lens, txt_off)
             x = self._embed(plan, None, txt, None, 1, seed)
             x = self._run_blocks(x, plan, 'l', 0, range(L), seed)
             out = engine.FinalNormFn.apply(x, self.norm.weight, self.norm.bias, plan, (B, T, self.embed_dim),
@@ -448,7 +463,7 @@ class VLMO(nn.Module):
         fusion_layer = fusion_layer or self.fusion_layer
         assert 0 <= fusion_layer <= self.bert_config.num_hidden_layers
         B, T = txt.shape
-        plan = engine.Plan(B, T, P, dev, txt_attn_masks, img_attn_masks)
+        plan = engine.Plan(B, T, P, dev, txt_attn_masks, img_attn_masks, txt_lens, txt_off)
         x = self._embed(plan, img, txt, bool_masked_pos, img_token_type_idx, seed)
         x = self._run_blocks(x, plan, 'vl', fusion_layer, range(L), seed)
         out = engine.FinalNormFn.apply(x, self.norm.weight, self.norm.bias, plan, (B, T + P, self.embed_dim),

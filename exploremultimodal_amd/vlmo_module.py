@@ -183,15 +183,31 @@ class VlmoModule(nn.Module):
         return matching, is_beit
 
     # ------------------------------------------------------------------ infer
+    def _text_lens(self, batch, ragged=None):
+        """(txt_lens, txt_off) for a pass over the batch's texts, or (None, None) = every text at full width.
+        ``config.train.ragged_text`` (not a reference option, default off) or ``ragged=True`` turns variable-length text
+        on; the lengths are those objectives.attach_text_lens put on the HOST batch (``_txt_lens``, a tuple of python
+        ints), so no pass asks the device.  A batch without them runs padded."""
+        if ragged is None:
+            ragged = bool(getattr(self.config.train, 'ragged_text', False))
+        lens = batch.get('_txt_lens') if ragged else None
+        if lens is None:
+            return None, None
+        off, ids = batch.get('_txt_off'), batch.get('text_ids')
+        if not (torch.is_tensor(off) and torch.is_tensor(ids) and off.device == ids.device):
+            off = None
+        return lens, off
+
     def infer(self, batch, infer_mode='img-txt', mask_txt=False, mask_img=False, image_token_type_idx=1,
-              momentum_mode=False):
-        """vlmo_module.py:321-393."""
+              momentum_mode=False, ragged=None):
+        """vlmo_module.py:321-393.  ``ragged``: see _text_lens (None = config.train.ragged_text)."""
         assert infer_mode in ['img_only', 'txt_only', 'img-txt']
         if momentum_mode:
             assert self.transformer_m is not None
         transformer = self.transformer
         img, img_attn_masks, bool_masked_pos = None, None, None
         txt_ids, txt_labels, txt_attn_masks = None, None, None
+        txt_lens, txt_off = None, None
         if 'img' in infer_mode:
             imgkey = f'image_{image_token_type_idx - 1}' if f'image_{image_token_type_idx - 1}' in batch else 'image'
             img = batch[imgkey]
@@ -204,9 +220,10 @@ class VlmoModule(nn.Module):
             txt_ids = batch[f'text_ids{do_mlm}']
             txt_labels = batch[f'text_labels{do_mlm}'] if mask_txt else None
             txt_attn_masks = batch['text_mask']
+            txt_lens, txt_off = self._text_lens(batch, ragged)
         co_feats, _ = transformer.forward_features(img=img, txt=txt_ids, img_attn_masks=img_attn_masks,
                                                    txt_attn_masks=txt_attn_masks, bool_masked_pos=bool_masked_pos,
-                                                   fusion_layer=None)
+                                                   fusion_layer=None, txt_lens=txt_lens, txt_off=txt_off)
         if txt_ids is not None:
             txt_feats, img_feats = (co_feats[:, :transformer.max_text_len], co_feats[:, transformer.max_text_len:])
         else:
@@ -308,8 +325,9 @@ class VlmoModule(nn.Module):
             ids2 = torch.cat([batch['text_ids'], batch['text_ids']], 0)
             tm2 = torch.cat([batch['text_mask'], batch['text_mask']], 0)
             ones = torch.ones([2 * B, tr.patch_embed.num_patches + 1], dtype=torch.int64, device=dev)
+            lens, _ = self._text_lens(batch)
             co, _ = tr.forward_features(img=img2, txt=ids2, img_attn_masks=ones, txt_attn_masks=tm2, bool_masked_pos=bmp2,
-                                        fusion_layer=depth)
+                                        fusion_layer=depth, txt_lens=lens + lens if lens is not None else None)
             img_itc, img_mim, txt_itc = co[:B, T:], co[B:, T:], co[:B, :T]
             batch['_itc_img_infer'] = {'txt_feats': None, 'img_feats': img_itc, 'co_feats': img_itc, 'cls_feats': None,
                                        'img_masks': ones[:B], 'img_bool_masked_pos': None, 'txt_labels': None,
@@ -347,8 +365,13 @@ class VlmoModule(nn.Module):
             ret.update(objectives.compute_itc(self, batch))
         # ---- VL pass
         vl_parts, ids, masks, imgs = [], [], [], []
+        # variable-length text: the parts' lengths side by side; the texts of the ITM negatives that are gathered on the
+        # device have no host length and count the full width
+        lens, _ = self._text_lens(batch)
+        part_lens = []
         if 'mlm' in names:
             vl_parts.append(('mlm', B))
+            part_lens.append(lens)
             ids.append(batch['text_ids_mlm'])
             masks.append(batch['text_mask'])
             imgs.append(batch['image'])
@@ -356,12 +379,15 @@ class VlmoModule(nn.Module):
             img_neg_idx, txt_neg_idx = objectives.sample_itm_negatives(batch, ret if 'itc' in names else None)
             neg = objectives.itm_negative_batch(batch, img_neg_idx, txt_neg_idx)
             vl_parts += [('itm_pos', B), ('itm_neg', 2 * B)]
+            part_lens += [lens, neg.get('_txt_lens')]
             ids += [batch['text_ids'], neg['text_ids']]
             masks += [batch['text_mask'], neg['text_mask']]
             imgs += [batch['image'], neg['image']]
         if vl_parts:
-            out = self.infer({'text_ids': torch.cat(ids, 0), 'text_mask': torch.cat(masks, 0), 'image': torch.cat(imgs, 0)},
-                             infer_mode='img-txt')
+            vb = {'text_ids': torch.cat(ids, 0), 'text_mask': torch.cat(masks, 0), 'image': torch.cat(imgs, 0)}
+            if lens is not None and all(pl is not None for pl in part_lens):
+                vb['_txt_lens'] = tuple(n for pl in part_lens for n in pl)
+            out = self.infer(vb, infer_mode='img-txt')
             pieces = dict(zip([p for p, _ in vl_parts], self._split_infer(out, [n for _, n in vl_parts])))
             if 'mlm' in pieces:
                 pieces['mlm']['txt_labels'] = batch['text_labels_mlm']

@@ -82,7 +82,7 @@ typedef struct VlmoEpilogue {
 const char* vlmo_last_error(void);
 /* Version of the struct layouts and signatures below; raised whenever one of them changes
  * (exploremultimodal_amd/hip.py mirrors it as ABI_VERSION and refuses any other). */
-#define VLMO_ABI_VERSION 13
+#define VLMO_ABI_VERSION 14
 int vlmo_abi_version(void);     /* = VLMO_ABI_VERSION of the header the library was built from */
 
 /* C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue.  tile: -1 = pick by shape, 0 = 128x128x64
@@ -275,6 +275,24 @@ int vlmo_embed_txt_bwd(const float* dx, const int64_t* ids, const float* xhat, c
                        const float* ln_w, float* dword, float* dpos, float* dbtype0, float* dln_w,
                        float* dln_b, float* dtype0, int B, int T, int d, uint32_t drop_thresh,
                        float inv_keep, uint64_t seed, hipStream_t stream);
+/* Row-table form of the text embedding, for batches whose texts have different row counts: sample b keeps its first
+ * len_b positions (1 <= len_b <= T) in packed rows off[b] .. off[b] + len_b - 1; the others are in no row.  Same
+ * arithmetic per row as the pair above; the dropout stream is indexed by the packed row.
+ *  fwd: src int32 [nrows], src[m] = b * T + t of packed row m; x / xhat [nrows, d], rstd [nrows].
+ *  bwd: off int32 [B + 1] = prefix sums of len_b, maxlen = max len_b (host value, <= T).  dpos, dbtype0, dln_w, dln_b
+ *       and dtype0 (each may be NULL) get += sums taken in a fixed order over a workspace of
+ *       vlmo_embed_txt_rows_ws_bytes(B, maxlen, d) bytes (a host function): two runs give the same bits.  dword is
+ *       scatter-added with float atomics as in vlmo_embed_txt_bwd; row 0 (padding_idx) gets nothing. */
+int vlmo_embed_txt_rows_fwd(const int64_t* ids, const int32_t* src, const float* word, const float* pos,
+                            const float* btype0, const float* ln_w, const float* ln_b, const float* type0,
+                            float* x, float* xhat, float* rstd, int nrows, int T, int d, float eps,
+                            uint32_t drop_thresh, float inv_keep, uint64_t seed, hipStream_t stream);
+int64_t vlmo_embed_txt_rows_ws_bytes(int B, int maxlen, int d);
+int vlmo_embed_txt_rows_bwd(const float* dx, const int64_t* ids, const int32_t* off, const float* xhat,
+                            const float* rstd, const float* ln_w, float* dword, float* dpos, float* dbtype0,
+                            float* dln_w, float* dln_b, float* dtype0, float* ws, int64_t ws_bytes, int B, int T,
+                            int maxlen, int d, uint32_t drop_thresh, float inv_keep, uint64_t seed,
+                            hipStream_t stream);
 
 /* Optional timing of the GEMM launches with HIP event pairs on their launch stream (bench.py's roofline).
  * stop() sums per tag: tag = epilogue id (+16 for the 256x256 tile, +48 for the 256x128 tile) for vlmo_gemm_nt, 32 + epilogue for
