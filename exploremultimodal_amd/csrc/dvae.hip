@@ -239,7 +239,9 @@ __global__ __launch_bounds__(256) void upsample2_kernel(const f16* __restrict__ 
 // fp32 NCHW.  Bound by the read of x: the weights sit in LDS as fp32, 8 lanes share a pixel (each 16-byte piece of the
 // row is read once, 128 contiguous bytes per pixel and pass), a wave covers 8 consecutive pixels; the 8 lanes' partial
 // sums meet in three butterfly steps and lane co of the group stores channel co.
-template <int CO>
+// RELU = false: the same head on x itself (the BEiT-style DiscreteVAE's last decoder layer, modeling_discrete_vae.py:135, has
+// no ReLU in front).
+template <int CO, bool RELU = true>
 __global__ __launch_bounds__(256) void out_head_kernel(const f16* __restrict__ x, const f16* __restrict__ w,
                                                        const float* __restrict__ bias, float* __restrict__ out, long M,
                                                        int HW, int C) {
@@ -254,7 +256,8 @@ __global__ __launch_bounds__(256) void out_head_kernel(const f16* __restrict__ x
         for (int co = 0; co < CO; ++co) acc[co] = 0.f;
         const f16* row = x + m * C;
         for (int c0 = sub * 8; c0 < C; c0 += 64) {
-            const f16x8 v = __builtin_elementwise_max(__builtin_nontemporal_load((const f16x8*)(row + c0)), z);
+            f16x8 v = __builtin_nontemporal_load((const f16x8*)(row + c0));
+            if constexpr (RELU) v = __builtin_elementwise_max(v, z);
 #pragma unroll
             for (int co = 0; co < CO; ++co) {
                 const f32x4 wa = *(const f32x4*)(wl + co * C + c0), wb = *(const f32x4*)(wl + co * C + c0 + 4);
@@ -275,6 +278,34 @@ __global__ __launch_bounds__(256) void out_head_kernel(const f16* __restrict__ x
             const long b = m / HW, pix = m - b * HW;
             out[(b * CO + sub) * HW + pix] = mine + bias[sub];
         }
+    }
+}
+
+// stem of the BEiT-style DiscreteVAE (Conv2d(3, hidden, 4, stride=2, padding=1), modeling_discrete_vae.py:114): x fp32 NCHW
+// [B,C,H,W] -> fp16 [B*(H/2)*(W/2), Kpad], column = c*16 + ky*4 + kx holds x[b, c, 2 oy - 1 + ky, 2 ox - 1 + kx] (zero outside
+// the image and beyond column C*16).  One thread = 8 consecutive columns = two kernel rows of one channel.
+__global__ __launch_bounds__(256) void patch4s2_kernel(const float* __restrict__ x, f16* __restrict__ out, int C, int H,
+                                                       int W, int Kpad, long total8) {
+    const int Ho = H / 2, Wo = W / 2, k8 = Kpad / 8, kreal = C * 16;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total8; i += (long)gridDim.x * 256) {
+        const long m = i / k8;
+        const int c0 = (int)(i - m * k8) * 8;
+        const int b = (int)(m / (Ho * Wo)), pix = (int)(m - (long)b * (Ho * Wo));
+        const int oy = pix / Wo, ox = pix - oy * Wo;
+        const float* xb = x + (size_t)b * C * H * W;
+        f16x8 v;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int col = c0 + j;
+            float val = 0.f;
+            if (col < kreal) {
+                const int c = col >> 4, ky = (col >> 2) & 3, kx = col & 3;
+                const int sy = 2 * oy - 1 + ky, sx = 2 * ox - 1 + kx;
+                if ((unsigned)sy < (unsigned)H && (unsigned)sx < (unsigned)W) val = xb[((size_t)c * H + sy) * W + sx];
+            }
+            v[j] = (f16)val;
+        }
+        *(f16x8*)(out + m * Kpad + c0) = v;
     }
 }
 
@@ -351,26 +382,52 @@ extern "C" int vlmo_upsample2_nhwc(const void* x, void* out, int B, int H, int W
     return 0;
 }
 
-extern "C" int vlmo_dvae_out_head(const void* x, const void* w, const float* bias, float* out, int B, int H, int W, int C,
-                                  int Cout, hipStream_t stream) {
-    VLMO_CHECK_ARG(x && w && bias && out, "vlmo_dvae_out_head: null pointer");
-    VLMO_CHECK_ARG(B > 0 && H > 0 && W > 0 && (long)H * W < 0x7fffffffL, "vlmo_dvae_out_head: bad geometry");
-    VLMO_CHECK_ARG(Cout >= 1 && Cout <= 8, "vlmo_dvae_out_head: 1 <= Cout <= 8 (got %d)", Cout);
-    VLMO_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 1024, "vlmo_dvae_out_head: C must be a multiple of 8, at most 1024 (got %d)", C);
+static int launch_out_head(const char* name, bool relu, const void* x, const void* w, const float* bias, float* out, int B,
+                           int H, int W, int C, int Cout, hipStream_t stream) {
+    VLMO_CHECK_ARG(x && w && bias && out, "%s: null pointer", name);
+    VLMO_CHECK_ARG(B > 0 && H > 0 && W > 0 && (long)H * W < 0x7fffffffL, "%s: bad geometry", name);
+    VLMO_CHECK_ARG(Cout >= 1 && Cout <= 8, "%s: 1 <= Cout <= 8 (got %d)", name, Cout);
+    VLMO_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 1024, "%s: C must be a multiple of 8, at most 1024 (got %d)", name, C);
     const long M = (long)B * H * W;
     const long blocks = (M + 31) / 32;
     const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
     const size_t lds = (size_t)Cout * C * sizeof(float);
-#define VLMO_OUT_HEAD(CO)                                                                                              \
-    case CO:                                                                                                           \
-        hipLaunchKernelGGL(out_head_kernel<CO>, grid, dim3(256), lds, stream, (const f16*)x, (const f16*)w, bias, out, \
-                           M, H * W, C);                                                                               \
+#define VLMO_OUT_HEAD(CO)                                                                                                  \
+    case CO:                                                                                                               \
+        if (relu)                                                                                                          \
+            hipLaunchKernelGGL((out_head_kernel<CO, true>), grid, dim3(256), lds, stream, (const f16*)x, (const f16*)w,    \
+                               bias, out, M, H * W, C);                                                                    \
+        else                                                                                                               \
+            hipLaunchKernelGGL((out_head_kernel<CO, false>), grid, dim3(256), lds, stream, (const f16*)x, (const f16*)w,   \
+                               bias, out, M, H * W, C);                                                                    \
         break;
     switch (Cout) {
         VLMO_OUT_HEAD(1) VLMO_OUT_HEAD(2) VLMO_OUT_HEAD(3) VLMO_OUT_HEAD(4)
         VLMO_OUT_HEAD(5) VLMO_OUT_HEAD(6) VLMO_OUT_HEAD(7) VLMO_OUT_HEAD(8)
     }
 #undef VLMO_OUT_HEAD
-    VLMO_CHECK_LAUNCH("vlmo_dvae_out_head");
+    VLMO_CHECK_LAUNCH(name);
+    return 0;
+}
+
+extern "C" int vlmo_dvae_out_head(const void* x, const void* w, const float* bias, float* out, int B, int H, int W, int C,
+                                  int Cout, hipStream_t stream) {
+    return launch_out_head("vlmo_dvae_out_head", true, x, w, bias, out, B, H, W, C, Cout, stream);
+}
+
+extern "C" int vlmo_dvae_out_head_linear(const void* x, const void* w, const float* bias, float* out, int B, int H, int W,
+                                         int C, int Cout, hipStream_t stream) {
+    return launch_out_head("vlmo_dvae_out_head_linear", false, x, w, bias, out, B, H, W, C, Cout, stream);
+}
+
+extern "C" int vlmo_dvae_patch4s2(const float* x, void* out, int B, int C, int H, int W, int Kpad, hipStream_t stream) {
+    VLMO_CHECK_ARG(x && out, "vlmo_dvae_patch4s2: null pointer");
+    VLMO_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "vlmo_dvae_patch4s2: H and W must be even");
+    VLMO_CHECK_ARG(Kpad % 8 == 0 && Kpad >= C * 16, "vlmo_dvae_patch4s2: Kpad must be a multiple of 8, at least 16 C");
+    VLMO_CHECK_ARG((long)B * (H / 2) * (W / 2) < 0x7fffffffL && (long)C * H * W < 0x7fffffffL, "vlmo_dvae_patch4s2: too large");
+    const long total8 = (long)B * (H / 2) * (W / 2) * (Kpad / 8);
+    hipLaunchKernelGGL(patch4s2_kernel, dim3(elementwise_grid(total8)), dim3(256), 0, stream, x, (f16*)out, C, H, W, Kpad,
+                       total8);
+    VLMO_CHECK_LAUNCH("vlmo_dvae_patch4s2");
     return 0;
 }

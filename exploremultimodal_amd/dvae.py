@@ -17,6 +17,10 @@ parameter planes of an image: the input convolution on a one-hot map is a row ga
 [B, 8192, h, w] one-hot tensor never exists), the DecoderBlock tail ``id + post_gain * conv_4(...)`` is the residual
 epilogue of the 3x3 convolution, the nearest-neighbour upsampling runs after the 1x1 convolutions of the block that
 follows it, and the six-channel output head writes fp32 NCHW directly.  Inference only: no autograd.
+
+``DiscreteVAE`` / ``ResBlock`` (models/modeling_discrete_vae.py:68-221) are BEiT's tokenizer, the reference's
+``discrete_vae_type = 'customized'``: the same engine plus a 4x4 stride-2 convolution and transposed convolution of its
+own (csrc/conv4s2.hip).
 """
 import math
 import os
@@ -507,12 +511,251 @@ class Dalle_VAE(nn.Module):
         return dec(z.permute(0, 3, 1, 2).float()).float()
 
 
-def create_d_vae(weight_path, d_vae_type, image_size, device, vocab_size=8192, with_decoder=False):
-    """objectives.py:595-607.  weight_path=None builds a randomly initialised encoder (synthetic runs) and, with
+# ---------------------------------------------------------------------------------------------------------------------
+# BEiT's DiscreteVAE (config.train.discrete_vae_type = 'customized'): models/modeling_discrete_vae.py:68-221
+
+def tap_major_shadow(w):
+    """Conv2d weight [Cout, Cin, k, k] -> fp16 [Cout, k*k*Cin], tap-major (k ky + kx), channel-minor: the layout of
+    vlmo_conv2d_nhwc, vlmo_conv4s2_nhwc and (k = 1) a plain GEMM."""
+    return w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1).to(torch.float16).contiguous()
+
+
+def convT4s2_shadow(w, cin_pad=None):
+    """ConvTranspose2d(4, stride 2, padding 1) weight [Cin, Cout, 4, 4] -> fp16 [4, Cout, 4*Cin_pad]: quarter p = 2 py + px
+    serves the output pixels of parity (py, px); its column (2 a + b) * Cin_pad + c holds w[c, n, 1 - py + 2 a,
+    1 - px + 2 b], the tap that input pixel (y + py - a, x + px - b) contributes to output (2 y + py, 2 x + px).
+    cin_pad > Cin adds zero columns (an input whose channel count is padded to a multiple of 64)."""
+    cin, cout = w.shape[:2]
+    cp = cin_pad or cin
+    s = torch.zeros((4, cout, 4, cp), dtype=torch.float16, device=w.device)
+    wd = w.detach()
+    for py in (0, 1):
+        for px in (0, 1):
+            for a in (0, 1):
+                for b in (0, 1):
+                    s[2 * py + px, :, 2 * a + b, :cin] = wd[:, :, 1 - py + 2 * a, 1 - px + 2 * b].t().to(torch.float16)
+    return s.reshape(4, cout, 4 * cp).contiguous()
+
+
+def _cached(mod, slot, params, build):
+    """A derived (shadow) tensor of ``mod``, rebuilt when one of ``params`` was written to or moved."""
+    ver = tuple((p._version, p.data_ptr()) for p in params)
+    hit = mod.__dict__.get(slot)
+    if hit is None or hit[0] != ver:
+        hit = (ver, build())
+        mod.__dict__[slot] = hit
+    return hit[1]
+
+
+def _conv_shadow(conv, build=None):
+    """(fp16 engine-layout weight, fp32 bias) of an nn.Conv2d / nn.ConvTranspose2d; ``build`` makes the weight where
+    it is not the tap-major one."""
+    if build is None:
+        build = lambda: tap_major_shadow(conv.weight)
+    return _cached(conv, '_vlmo_shadow', (conv.weight, conv.bias),
+                   lambda: (build(), conv.bias.detach().float().contiguous()))
+
+
+class ResBlock(nn.Module):
+    """modeling_discrete_vae.py:68-78: 3x3 + ReLU, 3x3 + ReLU, 1x1, plus the input."""
+
+    def __init__(self, chan_in, hidden_size, chan_out):
+        super().__init__()
+        self.net = nn.Sequential(nn.Conv2d(chan_in, hidden_size, 3, padding=1), nn.ReLU(),
+                                 nn.Conv2d(hidden_size, hidden_size, 3, padding=1), nn.ReLU(),
+                                 nn.Conv2d(hidden_size, chan_out, 1))
+
+    def run(self, x, B, h, w):
+        """x fp16 [B*h*w, C] -> net(x) + x; the sum is the 1x1 convolution's residual epilogue, rounded to fp16 once."""
+        c = x.shape[1]
+        M = B * h * w
+        t = x
+        for i in (0, 2):
+            wq, bq = _conv_shadow(self.net[i])
+            o = torch.empty((M, c), dtype=torch.float16, device=x.device)
+            hip.conv2d_nhwc(hip.EPI_BIAS, t, B, h, w, c, 3, wq, c, o, bias=bq, relu=True)
+            t = o
+        w4, b4 = _conv_shadow(self.net[4])
+        out = torch.empty((M, c), dtype=torch.float16, device=x.device)
+        hip.gemm_nt(hip.EPI_DUAL, t, w4, M, c, c, out, bias=b4, resid=x, beta=1.0)
+        return out
+
+
+class DiscreteVAE(nn.Module):
+    """modeling_discrete_vae.py:81-221 with the reference's module tree (=> its state-dict keys: ``codebook.weight``,
+    ``encoder.{2i}.0.*``, ``encoder.{2i+1}.net.{0,2,4}.*``, ``encoder.{2L}.*`` and the same under ``decoder.``) as a
+    parameter container; tokenising and decoding run on the HIP engine in fp16 NHWC.  Inference only (eval semantics, no
+    autograd): the Gumbel-softmax training pass of the tokenizer itself is not provided."""
+
+    def __init__(self, image_size=256, num_tokens=512, codebook_dim=512, num_layers=3, hidden_dim=64, channels=3,
+                 smooth_l1_loss=False, temperature=0.9, straight_through=False, kl_div_loss_weight=0.):
+        super().__init__()
+        if num_layers < 1:
+            raise ValueError('DiscreteVAE: number of layers must be greater than or equal to 1')
+        if hidden_dim < 64 or hidden_dim % 64 != 0:
+            raise NotImplementedError(f'DiscreteVAE: the implicit-GEMM kernels need hidden_dim to be a multiple of 64 '
+                                      f'(got {hidden_dim})')
+        if num_tokens < 64 or num_tokens % 64 != 0:
+            raise NotImplementedError(f'DiscreteVAE: the fused arg-max reduces 64-token chunks: num_tokens must be a '
+                                      f'multiple of 64 (got {num_tokens})')
+        if codebook_dim < 8 or codebook_dim % 8 != 0:
+            raise NotImplementedError(f'DiscreteVAE: the codebook lookup moves 8 channels per thread: codebook_dim must '
+                                      f'be a multiple of 8 (got {codebook_dim})')
+        if channels != 3:
+            raise NotImplementedError(f'DiscreteVAE: RGB images only (channels == 3, got {channels})')
+        if image_size < 2 ** num_layers or image_size % 2 ** num_layers != 0:
+            raise NotImplementedError(f'DiscreteVAE: image_size must be a multiple of 2**num_layers = {2 ** num_layers} '
+                                      f'(got {image_size})')
+        self.image_size, self.num_tokens, self.num_layers = image_size, num_tokens, num_layers
+        self.codebook_dim, self.hidden_dim, self.channels = codebook_dim, hidden_dim, channels
+        self.temperature, self.straight_through = temperature, straight_through
+        self.smooth_l1_loss, self.kl_div_loss_weight = smooth_l1_loss, kl_div_loss_weight
+        self.codebook = nn.Embedding(num_tokens, codebook_dim)
+        enc, dec = [], []
+        enc_in, dec_in = channels, codebook_dim
+        for _ in range(num_layers):
+            enc.append(nn.Sequential(nn.Conv2d(enc_in, hidden_dim, 4, stride=2, padding=1), nn.ReLU()))
+            enc.append(ResBlock(hidden_dim, hidden_dim, hidden_dim))
+            dec.append(nn.Sequential(nn.ConvTranspose2d(dec_in, hidden_dim, 4, stride=2, padding=1), nn.ReLU()))
+            dec.append(ResBlock(hidden_dim, hidden_dim, hidden_dim))
+            enc_in = dec_in = hidden_dim
+        enc.append(nn.Conv2d(hidden_dim, num_tokens, 1))
+        dec.append(nn.Conv2d(hidden_dim, channels, 1))
+        self.encoder = nn.Sequential(*enc)
+        self.decoder = nn.Sequential(*dec)
+
+    def get_image_size(self):
+        return self.image_size
+
+    def get_image_tokens_size(self):
+        return self.image_size // 8
+
+    # ------------------------------------------------------------------ engine
+    @staticmethod
+    def _need_cuda(t):
+        if t.device.type != 'cuda':
+            raise RuntimeError('exploremultimodal_amd runs on MI355X only: input must be on a cuda (ROCm) device')
+
+    def _features(self, img):
+        """-> the last ResBlock's output fp16 [B*h*w, hidden_dim], (B, h, w) with h = w = image_size / 2**num_layers."""
+        if img.dim() != 4 or img.shape[1] != self.channels:
+            raise ValueError(f'input shape {tuple(img.shape)} is not [B, {self.channels}, H, W]')
+        if img.shape[-1] != self.image_size or img.shape[-2] != self.image_size:
+            raise ValueError(f'input must have the correct image size {self.image_size}')
+        if img.dtype != torch.float32:
+            raise ValueError('input must have dtype torch.float32')
+        self._need_cuda(img)
+        B, dev, hid = img.shape[0], img.device, self.hidden_dim
+        h = w = self.image_size
+        x = img.contiguous()
+        t = None
+        for li in range(self.num_layers):
+            conv = self.encoder[2 * li][0]
+            M = B * (h // 2) * (w // 2)
+            o = torch.empty((M, hid), dtype=torch.float16, device=dev)
+            if li == 0:
+                # stem (3 input channels): explicit 4x4 stride-2 patches, K = 48 padded to 64, then a plain GEMM
+                ws, bs = _conv_shadow(conv, lambda: nn.functional.pad(
+                    conv.weight.detach().reshape(hid, -1), (0, 64 - 16 * self.channels)).to(torch.float16).contiguous())
+                cols = torch.empty((M, 64), dtype=torch.float16, device=dev)
+                hip.dvae_patch4s2(x, cols, 64)
+                hip.gemm_nt(hip.EPI_BIAS, cols, ws, M, hid, 64, o, bias=bs, relu=True)
+            else:
+                wq, bq = _conv_shadow(conv)
+                hip.conv4s2_nhwc(t, B, h, w, hid, wq, hid, o, bias=bq, relu=True)
+            h, w = h // 2, w // 2
+            t = self.encoder[2 * li + 1].run(o, B, h, w)
+        return t, (B, h, w)
+
+    @torch.no_grad()
+    def forward(self, img, return_loss=False, return_recons=False, return_logits=False, temp=None):
+        """modeling_discrete_vae.py:171-184 with return_logits=True -> fp32 logits [B, num_tokens, h, w]."""
+        if not return_logits:
+            raise NotImplementedError('DiscreteVAE.forward without return_logits is the Gumbel-softmax training pass of the '
+                                      'tokenizer itself (modeling_discrete_vae.py:186-221): this engine only tokenises '
+                                      '(get_codebook_indices, forward(..., return_logits=True)) and decodes (decode)')
+        feat, (B, h, w) = self._features(img)
+        wl, bl = _conv_shadow(self.encoder[2 * self.num_layers])
+        M = feat.shape[0]
+        logits = torch.empty((M, self.num_tokens), dtype=torch.float32, device=img.device)
+        hip.gemm_nt(hip.EPI_F32, feat, wl, M, self.num_tokens, self.hidden_dim, logits, bias=bl)
+        return logits.view(B, h, w, self.num_tokens).permute(0, 3, 1, 2)
+
+    @torch.no_grad()
+    def get_codebook_indices(self, images):
+        """argmax(forward(images, return_logits=True), dim=1) -> int64 [B, h, w] with the arg-max fused into the
+        vocabulary convolution: the [B, num_tokens, h, w] logits never exist."""
+        feat, (B, h, w) = self._features(images)
+        wl, bl = _conv_shadow(self.encoder[2 * self.num_layers])
+        M = feat.shape[0]
+        nchunk = self.num_tokens // 64
+        part = torch.empty((M, nchunk, 2), dtype=torch.float32, device=images.device)
+        hip.gemm_nt(hip.EPI_ARGMAX, feat, wl, M, self.num_tokens, self.hidden_dim, part, bias=bl, ldo=nchunk)
+        ids = torch.empty((M,), dtype=torch.int64, device=images.device)
+        hip.argmax_reduce(part, nchunk, ids, M)
+        return ids.view(B, h, w)
+
+    @torch.no_grad()
+    def get_codebook_probs(self, images):
+        return nn.Softmax(dim=1)(self.forward(images, return_logits=True))
+
+    def _codebook_table(self):
+        """fp32 codebook padded with zero columns to a multiple of 64 (the first transposed convolution's K chunks), and
+        the zero bias of the lookup kernel."""
+        cb = self.codebook.weight
+        dp = -(-self.codebook_dim // 64) * 64
+        return _cached(self.codebook, '_vlmo_shadow', (cb,), lambda: (
+            nn.functional.pad(cb.detach().float(), (0, dp - self.codebook_dim)).contiguous(),
+            torch.zeros(dp, dtype=torch.float32, device=cb.device)))
+
+    @torch.no_grad()
+    def decode(self, img_seq):
+        """modeling_discrete_vae.py:162-169: token ids int64 [B, n] (n a square) -> fp32 [B, channels, s, s] with
+        s = sqrt(n) * 2**num_layers.  Like ``Decoder.decode_ids`` an id outside [0, num_tokens) raises (one
+        device-to-host read)."""
+        if img_seq.dim() != 2:
+            raise ValueError(f'img_seq shape {tuple(img_seq.shape)} is not [B, n]')
+        if img_seq.dtype != torch.int64:
+            raise ValueError('img_seq must have dtype torch.int64')
+        self._need_cuda(img_seq)
+        B, n = img_seq.shape
+        h = w = math.isqrt(n)
+        if n == 0 or h * w != n:
+            raise ValueError(f'img_seq holds {n} ids per image, which is not a square grid')
+        lo, hi = int(img_seq.min()), int(img_seq.max())
+        if lo < 0 or hi >= self.num_tokens:
+            raise ValueError(f'ids must lie in [0, {self.num_tokens}): got values in [{lo}, {hi}]')
+        dev, hid = img_seq.device, self.hidden_dim
+        table, zbias = self._codebook_table()
+        cin = table.shape[1]
+        t = torch.empty((B * n, cin), dtype=torch.float16, device=dev)
+        hip.dvae_embed(img_seq.contiguous().view(-1), table, zbias, t)
+        for li in range(self.num_layers):
+            conv = self.decoder[2 * li][0]
+            wq, bq = _conv_shadow(conv, lambda: convT4s2_shadow(conv.weight, cin))
+            o = torch.empty((B * 4 * h * w, hid), dtype=torch.float16, device=dev)
+            hip.convT4s2_nhwc(t, B, h, w, cin, wq, hid, o, bias=bq, relu=True)
+            h, w, cin = 2 * h, 2 * w, hid
+            t = self.decoder[2 * li + 1].run(o, B, h, w)
+        wo, bo = _conv_shadow(self.decoder[2 * self.num_layers])
+        out = torch.empty((B, self.channels, h, w), dtype=torch.float32, device=dev)
+        hip.dvae_out_head_linear(t, wo, bo, out, B, h, w)
+        return out
+
+
+def create_d_vae(weight_path, d_vae_type, image_size, device, vocab_size=None, with_decoder=False):
+    """objectives.py:595-628.  'dall-e': weight_path=None builds a randomly initialised encoder (synthetic runs) and, with
     with_decoder=True, a randomly initialised decoder (44 M parameters that a pretraining model does not need: off by
-    default).  With a weight_path the decoder comes from <weight_path>/decoder.pkl when that file exists."""
+    default).  With a weight_path the decoder comes from <weight_path>/decoder.pkl when that file exists.
+    'customized' (get_d_vae, objectives.py:610-628): BEiT's DiscreteVAE with 3 layers, 8192 tokens, codebook width 512,
+    hidden width 256, loaded from <weight_path>/pytorch_model.bin['weights'].  The reference has no 'customized'
+    tokenizer without weights (get_d_vae joins the path unconditionally); weight_path=None WITH an explicit ``vocab_size``
+    builds a randomly initialised one of that many tokens for synthetic runs, and without one it is refused: that
+    call asks for the reference's tokenizer and names no weights to load.  ``vocab_size`` defaults to 8192 for 'dall-e'."""
     if d_vae_type == 'dall-e':
         vae = Dalle_VAE(image_size)
+        if vocab_size is None:
+            vocab_size = 8192
         if weight_path is None:
             vae.encoder = Encoder(device=torch.device(device), vocab_size=vocab_size)
             if with_decoder:
@@ -520,4 +763,18 @@ def create_d_vae(weight_path, d_vae_type, image_size, device, vocab_size=8192, w
         else:
             vae.load_model(model_dir=weight_path, device=device)
         return vae
-    raise NotImplementedError()
+    if d_vae_type == 'customized':
+        if weight_path is None:
+            if vocab_size is None:
+                raise NotImplementedError("create_d_vae(None, 'customized', ...): the customized tokenizer is loaded from "
+                                          "<weight_path>/pytorch_model.bin; without a weight_path pass vocab_size=... for "
+                                          'a randomly initialised one (synthetic runs)')
+            return DiscreteVAE(image_size=image_size, num_layers=3, num_tokens=vocab_size, codebook_dim=512,
+                               hidden_dim=256).to(device)
+        state_dict = torch.load(os.path.join(weight_path, 'pytorch_model.bin'), map_location='cpu')['weights']
+        model = DiscreteVAE(image_size=image_size, num_layers=3, num_tokens=8192, codebook_dim=512,
+                            hidden_dim=256).to(device)
+        model.load_state_dict(state_dict)
+        return model
+    raise NotImplementedError(f"discrete_vae_type {d_vae_type!r} is not one of 'dall-e', 'customized' "
+                              '(objectives.py:595-601)')

@@ -126,6 +126,10 @@ _SIGS = {
     'vlmo_dvae_embed': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
     'vlmo_upsample2_nhwc': [_vp, _vp, _i32, _i32, _i32, _i32, _vp],
     'vlmo_dvae_out_head': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    'vlmo_conv4s2_nhwc': [_i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, ctypes.POINTER(Epilogue), _vp],
+    'vlmo_convt4s2_nhwc': [_i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, ctypes.POINTER(Epilogue), _vp],
+    'vlmo_dvae_patch4s2': [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    'vlmo_dvae_out_head_linear': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     'vlmo_ce_reduce': [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
     'vlmo_stack_fwd': [ctypes.POINTER(StackDesc), _vp],
     'vlmo_stack_bwd': [ctypes.POINTER(StackDesc), _vp],
@@ -169,7 +173,7 @@ _SIGS = {
 }
 
 _lib = None
-ABI_VERSION = 14     # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
+ABI_VERSION = 15     # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
 
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is missing."""
@@ -516,6 +520,37 @@ def dvae_out_head(x, w, bias, out, B, H, W):
     """out f32 [B, Cout, H, W] = conv1x1(relu(x)) + bias; x f16 [B*H*W, C], w f16 [Cout, C], Cout <= 8."""
     Cout, C = w.shape
     _check(lib().vlmo_dvae_out_head(_p(x), _p(w), _p(bias), _p(out), B, H, W, C, Cout, _stream()), 'vlmo_dvae_out_head')
+
+
+def conv4s2_nhwc(x, B, H, W, Cin, w, Cout, out, *, bias=None, relu=False):
+    """Conv2d(Cin, Cout, 4, stride=2, padding=1): x f16 [B*H*W, Cin], w f16 [Cout, 16*Cin] (tap-major) ->
+    out f16 [B*(H/2)*(W/2), Cout], bias and optional ReLU fused."""
+    e = _epilogue(out, bias=bias, relu=int(relu))
+    rc = lib().vlmo_conv4s2_nhwc(_dt(x), _p(x), B, H, W, Cin, _p(w), Cout, _p(zero_page(x.device)), ctypes.byref(e),
+                                 _stream())
+    _check(rc, 'vlmo_conv4s2_nhwc')
+
+
+def convT4s2_nhwc(x, B, H, W, Cin, w, Cout, out, *, bias=None, relu=False):
+    """ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1): x f16 [B*H*W, Cin], w f16 [4, Cout, 4*Cin] (one quarter per
+    output parity, see include/vlmo_hip.h) -> out f16 [B*2H*2W, Cout], bias and optional ReLU fused."""
+    e = _epilogue(out, bias=bias, relu=int(relu))
+    rc = lib().vlmo_convt4s2_nhwc(_dt(x), _p(x), B, H, W, Cin, _p(w), Cout, _p(zero_page(x.device)), ctypes.byref(e),
+                                  _stream())
+    _check(rc, 'vlmo_convt4s2_nhwc')
+
+
+def dvae_patch4s2(x, out, Kpad):
+    """x f32 [B, C, H, W] -> out f16 [B*(H/2)*(W/2), Kpad]: the 4x4 stride-2 patches, column = c*16 + ky*4 + kx."""
+    B, C, H, W = x.shape
+    _check(lib().vlmo_dvae_patch4s2(_p(x), _p(out), B, C, H, W, Kpad, _stream()), 'vlmo_dvae_patch4s2')
+
+
+def dvae_out_head_linear(x, w, bias, out, B, H, W):
+    """out f32 [B, Cout, H, W] = conv1x1(x) + bias (no ReLU); x f16 [B*H*W, C], w f16 [Cout, C], Cout <= 8."""
+    Cout, C = w.shape
+    _check(lib().vlmo_dvae_out_head_linear(_p(x), _p(w), _p(bias), _p(out), B, H, W, C, Cout, _stream()),
+           'vlmo_dvae_out_head_linear')
 
 
 def gemm_tn_multi(problems, dtype=BF16):

@@ -82,7 +82,7 @@ typedef struct VlmoEpilogue {
 const char* vlmo_last_error(void);
 /* Version of the struct layouts and signatures below; raised whenever one of them changes
  * (exploremultimodal_amd/hip.py mirrors it as ABI_VERSION and refuses any other). */
-#define VLMO_ABI_VERSION 14
+#define VLMO_ABI_VERSION 15
 int vlmo_abi_version(void);     /* = VLMO_ABI_VERSION of the header the library was built from */
 
 /* C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue.  tile: -1 = pick by shape, 0 = 128x128x64
@@ -478,6 +478,30 @@ int vlmo_upsample2_nhwc(const void* x, void* out, int B, int H, int W, int C, hi
  * w f16 [Cout, C], 1 <= Cout <= 8, C % 8 == 0, C <= 1024. */
 int vlmo_dvae_out_head(const void* x, const void* w, const float* bias, float* out, int B, int H, int W, int C,
                        int Cout, hipStream_t stream);
+/* ---- BEiT-style DiscreteVAE (models/modeling_discrete_vae.py:81-221), fp16 NHWC activations; its 3x3 / 1x1 layers,
+ * the arg-max and the codebook lookup run on the entry points above ---- */
+
+/* Conv2d(Cin, Cout, 4, stride=2, padding=1) as implicit GEMM: x f16 [B*H*W, Cin] -> e->out f16 [B*(H/2)*(W/2), ldo];
+ * output pixel (oy, ox) reads input (2 oy - 1 + ky, 2 ox - 1 + kx), taps outside the image read zero_page (>= 128 zero
+ * bytes).  w f16 [Cout, 16*Cin], tap-major (4 ky + kx), channel-minor.  Epilogue: e->bias (may be NULL), e->relu bit 0.
+ * dtype VLMO_F16; H, W even; Cin % 64 == 0; Cout % 8 == 0; ldo % 8 == 0. */
+int vlmo_conv4s2_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, const void* w, int Cout,
+                      const void* zero_page, const VlmoEpilogue* e, hipStream_t stream);
+/* ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1): x f16 [B*H*W, Cin] -> e->out f16 [B*2H*2W, ldo]; the four output
+ * parities (oy & 1, ox & 1) are four 2x2 convolutions of one launch (no zero-stuffed input).  w f16 [4][Cout, 4*Cin]:
+ * quarter p = 2 py + px, column (2 a + b) * Cin + c holds weight[c, n, 1 - py + 2 a, 1 - px + 2 b] of the PyTorch layout
+ * [Cin, Cout, 4, 4], met by input pixel (y + py - a, x + px - b) for output pixel (2 y + py, 2 x + px).  Epilogue and
+ * limits as vlmo_conv4s2_nhwc (no parity condition on H, W). */
+int vlmo_convt4s2_nhwc(int dtype, const void* x, int B, int H, int W, int Cin, const void* w, int Cout,
+                       const void* zero_page, const VlmoEpilogue* e, hipStream_t stream);
+/* stem input of the 4x4 stride-2 convolution: image f32 NCHW -> f16 [B*(H/2)*(W/2), Kpad] patches, column = c*16 + ky*4 + kx
+ * (zero outside the image and beyond C*16).  H, W even; Kpad % 8 == 0, Kpad >= 16 C. */
+int vlmo_dvae_patch4s2(const float* x, void* out, int B, int C, int H, int W, int Kpad, hipStream_t stream);
+/* vlmo_dvae_out_head without the ReLU: out f32 NCHW [B, Cout, H, W] = conv1x1(x) + bias (modeling_discrete_vae.py:135).
+ * Same limits. */
+int vlmo_dvae_out_head_linear(const void* x, const void* w, const float* bias, float* out, int B, int H, int W, int C,
+                              int Cout, hipStream_t stream);
+
 /* finish of VLMO_EPI_CE: partial [M, nchunk, 4] -> lse [M], loss [M] (lse - label logit; 0 where
  * labels[m] == ignore_index; may be NULL), pred [M] (arg-max, first maximum wins; may be NULL). */
 int vlmo_ce_reduce(const float* partial, int nchunk, const int32_t* labels, int ignore_index, float* lse,
