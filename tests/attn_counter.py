@@ -6,6 +6,8 @@ where N is the SEQUENCE's own length: S(N) = 512 for N <= 512 (the counter of th
 import numpy as np
 import torch
 
+from tests.dropmask import hash32 as _hash32
+
 _M = np.uint64(0xFFFFFFFF)
 
 
@@ -16,14 +18,6 @@ def stride(n):
 def counter(q, key, n):
     """the 32-bit counter of (q, key) in a sequence of n tokens (numpy arrays or ints)"""
     return (np.asarray(q, dtype=np.uint64) * np.uint64(stride(n)) + np.asarray(key, dtype=np.uint64)) & _M
-
-
-def _hash32(x):
-    x = x ^ (x >> np.uint64(16))
-    x = (x * np.uint64(0x7feb352d)) & _M
-    x = x ^ (x >> np.uint64(15))
-    x = (x * np.uint64(0x846ca68b)) & _M
-    return x ^ (x >> np.uint64(16))
 
 
 def keep_mask(seed, lens, heads, thresh, npad=None, seq0=0):

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from exploremultimodal_amd import hip  # noqa: E402
+from tests.dropmask import hash32 as _hash32  # noqa: E402
 
 DEV = 'cuda'
 
@@ -296,16 +297,6 @@ def _attn_case(B, lenA, lenB, heads, seed=0, mask_frac=0.3):
             p0 = int(torch.randint(2, lenA, (1,), generator=g))
             keymask[b * lenA + p0:(b + 1) * lenA] = 0
     return qkv, seg.to(DEV), keymask.to(DEV), M, d
-
-
-def _hash32(x):
-    """host replica of csrc/common.h hash32 on uint64 arrays holding 32-bit values"""
-    m = np.uint64(0xFFFFFFFF)
-    x = x ^ (x >> np.uint64(16))
-    x = (x * np.uint64(0x7feb352d)) & m
-    x = x ^ (x >> np.uint64(15))
-    x = (x * np.uint64(0x846ca68b)) & m
-    return x ^ (x >> np.uint64(16))
 
 
 def _attn_keep_mask(seed, nseq, heads, N, thresh):
