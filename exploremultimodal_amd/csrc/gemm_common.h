@@ -640,7 +640,9 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_nt_kernel(const GemmNTGr
                         bi = oi;
                     }
                 }
-                if ((lane % LPR) == 0 && gm < p.M) {
+                // col_ok of the row's first lane = the wave's first column lies below N: a wave wholly past N (odd chunk
+                // count under an even tile) has no chunk, its index would be the next row's chunk 0
+                if ((lane % LPR) == 0 && gm < p.M && col_ok) {
                     const int chunk = (n0 + wn * (BN / WN)) / ROWF;
                     float* pv = (float*)p.e.out + ((size_t)gm * p.e.ldo + chunk) * 2;
                     pv[0] = best;
@@ -678,7 +680,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_nt_kernel(const GemmNTGr
                     if (gn + j < p.N) se += __builtin_amdgcn_exp2f((vv[j] - best) * 1.4426950408889634f);
 #pragma unroll
                 for (int o = 1; o < LPR; o <<= 1) se += __shfl_xor(se, o, 64);
-                if ((lane % LPR) == 0 && gm < p.M) {
+                if ((lane % LPR) == 0 && gm < p.M && col_ok) {      // as above: no chunk for a wave wholly past N
                     const int chunk = (n0 + wn * (BN / WN)) / ROWF;
                     float* pv = (float*)p.e.out + ((size_t)gm * p.e.ldo + chunk) * 4;
                     pv[0] = best;

@@ -1,10 +1,14 @@
 """Fused vocabulary-head loss (heads.LinearCrossEntropyFn: VLMO_EPI_CE / vlmo_ce_reduce / VLMO_EPI_CE_BWD) against
 plain PyTorch fp32 F.linear + F.cross_entropy on the same bf16-rounded operands (heads.py:86-112,
-objectives.py:57-68,571-582).  Tolerances: loss 1e-3 + 5e-4 relative (bf16 operands, fp32 accumulation and soft-max);
-gradients 2 % of their norm (the recomputed soft-max gradient is rounded to bf16 before the two gradient GEMMs)."""
+objectives.py:57-68,571-582).  Tolerances: the loss against fp64 within eight times the error of a plain fp32
+evaluation (measured on the CPU, tests/test_vocab_head_gpu.py; the operands are bf16-exact, so only fp32 accumulation and
+the soft-max remain); the prediction equal to the fp64 arg-max wherever its top-2 gap exceeds 1e-4; gradients 2 % of
+their norm (the recomputed soft-max gradient is rounded to bf16 before the two gradient GEMMs)."""
 import pytest
 import torch
 import torch.nn.functional as F
+
+from tests.test_vocab_head_gpu import LOSS_BOUND
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -27,9 +31,14 @@ def test_linear_cross_entropy_matches_torch(n, d, V, ignore):
     logits = F.linear(x, W, b)
     ref = F.cross_entropy(logits, labels, ignore_index=-100)
     (ref * 3.0).backward()
-    assert abs(loss.item() - ref.item()) <= 1e-3 + 5e-4 * abs(ref.item()), (loss.item(), ref.item())
-    agree = (pred.long() == logits.argmax(1)).float().mean().item()
-    assert agree >= 0.98, agree        # near-ties may flip under bf16 rounding of nothing: operands are already bf16
+    logits64 = F.linear(x.detach().double().cpu(), W.detach().double().cpu(), b.detach().double().cpu())
+    ref64 = F.cross_entropy(logits64, labels.cpu(), ignore_index=-100).item()
+    assert abs(loss.item() - ref64) <= LOSS_BOUND, (loss.item(), ref64)
+    # the prediction is the fp64 arg-max wherever that one is clear of fp32 rounding, which is almost everywhere
+    top2 = logits64.topk(2, dim=1).values
+    clear = (top2[:, 0] - top2[:, 1]) > 1e-4
+    assert clear.float().mean().item() >= 0.95
+    assert torch.equal(pred.long().cpu()[clear], logits64.argmax(1)[clear])
     for name, a, t in zip('xWb', got, (x, W, b)):
         rel = (a - t.grad).norm().item() / (t.grad.norm().item() + 1e-12)
         assert rel <= 2e-2, (name, rel)

@@ -87,6 +87,78 @@ def test_gemm_nt_tile4_small_integers(tile, M, N, K):
     assert torch.equal(out.float().cpu(), ref), (out.float().cpu() - ref).abs().max()
 
 
+@pytest.mark.parametrize('M', [77, 300])
+@pytest.mark.parametrize('N', [4, 68, 132, 196, 3136])
+def test_gemm_nt_column_edges_exact_integers(N, M):
+    """Widths that are no multiple of the tile, of a wave's 64 columns or (N = 4) of more than one 4-column group, as the
+    heads run them (3136 answers, N = hidden), with ldo = ld2 = N + 4 and two spare rows: operands in {-1, 0, 1}, K = 64,
+    so every output is a small integer, exact in bf16 and fp32.  Everything outside [M, N] is NaN before the launch --
+    outputs, the residual and aux inputs, the unused columns of a strided A -- and must be NaN after it, and no NaN may
+    reach a real element."""
+    K = 64
+    g = torch.Generator().manual_seed(N * 5 + M)
+    A = torch.randint(-1, 2, (M, K), generator=g).float()
+    B = torch.randint(-1, 2, (N, K), generator=g).float()
+    bias = (torch.arange(N) % 7 - 3).float()
+    acc = A @ B.t()
+    ref = acc + bias
+    Ad, Bd, biasd = A.to(DEV).bfloat16(), B.to(DEV).bfloat16(), bias.to(DEV)
+    ldo = N + 4
+
+    def guarded(dtype, fill=None):
+        t = torch.full((M + 2, ldo), float('nan'), dtype=dtype, device=DEV)
+        if fill is not None:
+            t[:M, :N] = fill.to(DEV).to(dtype)
+        return t
+
+    def real(t, what):
+        t = t.float().cpu()
+        assert torch.isnan(t[M:]).all() and torch.isnan(t[:M, N:]).all(), f'{what}: written outside [M, N]'
+        return t[:M, :N]
+
+    for tile in (0, 3, 4, 8, 313):
+        out = guarded(torch.bfloat16)
+        hip.gemm_nt(hip.EPI_BIAS, Ad, Bd, M, N, K, out, bias=biasd, tile=tile)
+        assert torch.equal(real(out, f'bias, tile {tile}'), ref), f'bias, tile {tile}'
+    prior = ((torch.arange(M)[:, None] * 3 + torch.arange(N)[None]) % 11 - 5).float()
+    resid = ((torch.arange(M)[:, None] + torch.arange(N)[None] * 2) % 9 - 4).float()
+    gamma = (torch.arange(N) % 3 - 1).float()
+    rs = (torch.arange(M) % 3).float()
+    x = ((torch.arange(M)[:, None] * 2 + torch.arange(N)[None]) % 5 - 2).float()
+    xg = x.clone().requires_grad_(True)
+    F.gelu(xg).backward(torch.ones_like(xg))
+    nblk = (M + 15) // 16
+    Awide = torch.full((M, K + 64), float('nan'), dtype=torch.bfloat16, device=DEV)
+    Awide[:, :K] = Ad
+    for tile in (0, 3):
+        out = guarded(torch.float32)
+        hip.gemm_nt(hip.EPI_F32, Ad, Bd, M, N, K, out, bias=biasd, tile=tile)
+        assert torch.equal(real(out, f'f32, tile {tile}'), ref), f'f32, tile {tile}'
+        out = guarded(torch.float32, prior)
+        hip.gemm_nt(hip.EPI_F32, Ad, Bd, M, N, K, out, bias=biasd, beta=1.0, tile=tile)
+        assert torch.equal(real(out, f'f32 beta, tile {tile}'), ref + prior), f'f32 beta = 1, tile {tile}'
+        out = guarded(torch.float32)
+        hip.gemm_nt(hip.EPI_F32, Awide, Bd, M, N, K, out, bias=biasd, tile=tile)
+        assert torch.equal(real(out, f'strided A, tile {tile}'), ref), f'lda = K + 64, tile {tile}'
+        u, h = guarded(torch.bfloat16), guarded(torch.bfloat16)
+        hip.gemm_nt(hip.EPI_BIAS_GELU, Ad, Bd, M, N, K, u, out2=h, bias=biasd, tile=tile)
+        assert torch.equal(real(u, f'gelu.u, tile {tile}'), ref), f'gelu.u, tile {tile}'
+        _close(real(h, f'gelu.h, tile {tile}'), F.gelu(ref), 1 / 128, 1e-2, f'gelu.h, tile {tile}')
+        xo, zd = guarded(torch.float32), guarded(torch.bfloat16)
+        hip.gemm_nt(hip.EPI_RESID, Ad, Bd, M, N, K, xo, out2=zd, bias=biasd, gamma=gamma.to(DEV),
+                    resid=guarded(torch.float32, resid), row_scale=rs.to(DEV), tile=tile)
+        assert torch.equal(real(zd, f'resid.zd, tile {tile}'), ref), f'resid.zd, tile {tile}'
+        assert torch.equal(real(xo, f'resid.out, tile {tile}'), resid + gamma * ref * rs[:, None]), f'resid.out, tile {tile}'
+        dg, cp = guarded(torch.bfloat16), torch.full((nblk + 1, N), float('nan'), device=DEV)
+        hip.gemm_nt(hip.EPI_DGELU, Ad, Bd, M, N, K, dg, aux=guarded(torch.bfloat16, x), colpart=cp, tile=tile)
+        want = acc * xg.grad
+        _close(real(dg, f'dgelu, tile {tile}'), want, 1 / 128, 1e-2, f'dgelu, tile {tile}')
+        cp = cp.cpu()
+        assert torch.isnan(cp[nblk]).all(), f'tile {tile}: partial rows beyond ceil(M/16) were written'
+        assert not torch.isnan(cp[:nblk]).any(), f'tile {tile}: a column partial was left unwritten or took a NaN'
+        _close(cp[:nblk].sum(0), want.sum(0), 2e-3, 2e-3 * want.sum(0).abs().max().item(), f'fold of the partials, tile {tile}')
+
+
 def test_gemm_nt_f16_dtype():
     M, N, K = 200, 128, 128
     A, B = _rand(M, K, seed=1, dtype=torch.float16), _rand(N, K, scale=0.1, seed=2, dtype=torch.float16)
