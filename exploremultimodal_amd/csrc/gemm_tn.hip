@@ -1,8 +1,7 @@
 // gemm_tn: C[N1,N2] += A[M,N1]^T . B[M,N2] (reduction over rows) = the weight gradients: gemm_tn_kernel (split over the
 // grid, fp32 atomics or slab + tn_reduce_kernel) and gemm_tn_multi_kernel (several problems in one launch).
 #include "gemm_common.h"
-#include <algorithm>
-#include <vector>
+#include "tn_multi_plan.h"
 
 namespace {
 
@@ -15,10 +14,9 @@ struct GemmTN {
     int kt_per_split, tiles;
     float alpha;
     float* slab;     // [splits, N1, N2] fp32 partial products (plain stores) or NULL (see mode)
-    int mode;        // without a slab: 0 = fp32 atomics into C, 1 = C += alpha * acc (this workgroup owns the
-                     // tile: no K split), 2 = C = alpha * acc
+    int mode;        // without a slab: TN_ATOMIC = fp32 atomics into C, TN_ACCUM = C += alpha * acc (this workgroup
+                     // owns the tile: no K split), TN_STORE = C = alpha * acc
 };
-enum { TN_ATOMIC = 0, TN_ACCUM = 1, TN_STORE = 2 };
 
 // 256 zero bytes: the staging source of token rows past the end of the reduction dimension
 __device__ __attribute__((aligned(256))) char tn_zero_page[256];
@@ -305,21 +303,15 @@ template <typename T, int BM, int BN, int WM, int WN, bool PP = false>
 __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_tn_kernel(const GemmTN p) {
     gemm_tn_body<T, BM, BN, WM, WN, PP>(p, xcd_remap(blockIdx.x, gridDim.x));
 }
+// dynamic LDS of the 256x256 ping-pong tile (both kernels): the ring of four 32 KB slices
+constexpr int TN_LDS_256 = 2 * 4 * 64 * 256;
 
 // Up to MAX_TN_PROBS weight-gradient problems in ONE launch of 256x256 tiles (the four to six linears of one or
-// two transformer blocks): problem q owns the logical workgroups [t0[q], t0[q+1]).  A single weight gradient of
-// VLMo-Base has 9-36 output tiles, so on its own it needs a 7-way split of the token dimension (slabs + a reduction
-// pass, or atomics) to occupy 256 CUs; the gradients of two blocks together have 216 tiles and need no split at all.
-constexpr int MAX_TN_PROBS = 16;
-// Workgroup b of the launch runs order[b] = (problem << 12) | (workgroup index inside the problem), or nothing
-// (TN_NOP).  The host fills the table so that the workgroups one XCD receives (b % 8 equal, dealt round-robin) are
-// a BALANCED mix: with problems of different reduction lengths in one launch (below the fusion layer: 261, 197 and
-// 64 K-tiles) contiguous XCD chunks gave one XCD 45 long tiles for its 32 CUs -- two rounds, 1 035 us instead of
-// 525 -- while another finished its 45 short ones in a quarter of the time.
-constexpr int MAX_TN_ORDER = 1024;
-constexpr uint16_t TN_NOP = 0xFFFF;
+// two transformer blocks).  A single weight gradient of VLMo-Base has 9-36 output tiles, so on its own it needs a
+// 7-way split of the token dimension (slabs + a reduction pass, or atomics) to occupy 256 CUs; the gradients of two
+// blocks together have 216 tiles and need no split at all.  Workgroup b runs order[b], which the host plans
+// (tn_multi_plan.h).
 struct GemmTNMulti {
-    int n;
     GemmTN p[MAX_TN_PROBS];
     uint16_t order[MAX_TN_ORDER];
 };
@@ -418,16 +410,15 @@ extern "C" int vlmo_gemm_tn(int dtype, const void* A, int lda, const void* B, in
     dim3 grid(pl.tiles * pl.splits);
     ProfScope prof(64 + (pl.big ? 8 : 0), 2.0 * M * N1 * N2, stream);
     if (pl.big) {
-        constexpr int LDS = 2 * 4 * 64 * 256;
         static DeviceOnce attr;
         if (attr.first()) {
-            (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<bf16, 256, 256, 2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<f16, 256, 256, 2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+            (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<bf16, 256, 256, 2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_256);
+            (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<f16, 256, 256, 2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_256);
         }
         if (dtype == VLMO_F16)
-            hipLaunchKernelGGL((gemm_tn_kernel<f16, 256, 256, 2, 4, true>), grid, dim3(512), LDS, stream, p);
+            hipLaunchKernelGGL((gemm_tn_kernel<f16, 256, 256, 2, 4, true>), grid, dim3(512), TN_LDS_256, stream, p);
         else
-            hipLaunchKernelGGL((gemm_tn_kernel<bf16, 256, 256, 2, 4, true>), grid, dim3(512), LDS, stream, p);
+            hipLaunchKernelGGL((gemm_tn_kernel<bf16, 256, 256, 2, 4, true>), grid, dim3(512), TN_LDS_256, stream, p);
     } else {
         if (dtype == VLMO_F16)
             hipLaunchKernelGGL((gemm_tn_kernel<f16, 128, 128, 2, 2>), grid, dim3(256), 65536, stream, p);
@@ -444,105 +435,65 @@ extern "C" int vlmo_gemm_tn(int dtype, const void* A, int lda, const void* B, in
     return 0;
 }
 
-// Weight gradients of several linears in one launch (see gemm_tn_multi_kernel).  Tiles are 256x256; when the
-// problems together have fewer than ~3/4 of the CUs' worth of tiles every problem's token dimension is split
-// (fp32 atomics), else each tile is owned by one workgroup and written / accumulated in place.
+// Weight gradients of several linears in as few launches as plan_tn_multi (tn_multi_plan.h) makes of them: validate every
+// problem, plan, then execute the plan.  Nothing is enqueued before the whole call is known to be good.
 extern "C" int vlmo_gemm_tn_multi(int dtype, const VlmoTnProblem* probs, int n, hipStream_t stream) {
     VLMO_CHECK_ARG(probs && n >= 1, "vlmo_gemm_tn_multi: no problems");
     VLMO_CHECK_ARG(dtype == VLMO_BF16 || dtype == VLMO_F16, "vlmo_gemm_tn_multi: dtype must be bf16 or f16");
+    for (int q = 0; q < n; ++q) {
+        const VlmoTnProblem& r = probs[q];
+        VLMO_CHECK_ARG(r.A && r.B && r.C, "vlmo_gemm_tn_multi: null operand in problem %d", q);
+        VLMO_CHECK_ARG(r.M > 0 && r.N1 >= 8 && r.N2 >= 8 && r.N1 % 8 == 0 && r.N2 % 8 == 0 && r.lda % 8 == 0 &&
+                           r.ldb % 8 == 0 && r.lda >= r.N1 && r.ldb >= r.N2 && r.ldc >= r.N2,
+                       "vlmo_gemm_tn_multi: bad shape in problem %d (M=%d N1=%d N2=%d)", q, r.M, r.N1, r.N2);
+    }
+    const TnMultiPlan plan = plan_tn_multi(probs, n);
+    VLMO_CHECK_ARG(plan.error.empty(), "%s", plan.error.c_str());
     static DeviceOnce attr;
     if (attr.first()) {
-        constexpr int LDS = 2 * 4 * 64 * 256;
-        (void)hipFuncSetAttribute((const void*)gemm_tn_multi_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm_tn_multi_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)gemm_tn_multi_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_256);
+        (void)hipFuncSetAttribute((const void*)gemm_tn_multi_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_256);
     }
-    for (int q0 = 0, nq = 0; q0 < n; q0 += nq) {
-        // one launch = as many of the remaining problems as fit the problem table and the placement table
-        nq = 0;
-        for (long tl = 0; q0 + nq < n && nq < MAX_TN_PROBS; ++nq) {
-            const VlmoTnProblem& r = probs[q0 + nq];
-            const long t = (long)((r.N1 + 255) / 256) * ((r.N2 + 255) / 256);
-            if (nq > 0 && tl + t > MAX_TN_ORDER - 64) break;
-            tl += t;
-        }
-        long tiles_all = 0;
-        int min_nk = 1 << 30;
-        double flops = 0;
-        for (int q = 0; q < nq; ++q) {
-            const VlmoTnProblem& r = probs[q0 + q];
-            VLMO_CHECK_ARG(r.A && r.B && r.C, "vlmo_gemm_tn_multi: null operand in problem %d", q0 + q);
-            VLMO_CHECK_ARG(r.M > 0 && r.N1 >= 8 && r.N2 >= 8 && r.N1 % 8 == 0 && r.N2 % 8 == 0 && r.lda % 8 == 0 &&
-                               r.ldb % 8 == 0 && r.lda >= r.N1 && r.ldb >= r.N2 && r.ldc >= r.N2,
-                           "vlmo_gemm_tn_multi: bad shape in problem %d (M=%d N1=%d N2=%d)", q0 + q, r.M, r.N1, r.N2);
-            tiles_all += (long)((r.N1 + 255) / 256) * ((r.N2 + 255) / 256);
-            const int nk = (r.M + 63) / 64;
-            if (nk < min_nk) min_nk = nk;
-            flops += 2.0 * r.M * r.N1 * r.N2;
-        }
-        int splits = 1;
-        if (tiles_all < 192) {
-            splits = (int)(256 / tiles_all);
-            if (splits > min_nk / 8) splits = min_nk / 8;
-            if (splits < 1) splits = 1;
-        }
+    for (const TnLaunchPlan& L : plan.launches) {
         GemmTNMulti mp{};
-        mp.n = nq;
-        struct Job {
-            uint16_t code;
-            int cost;
-        };
-        std::vector<Job> jobs;
-        for (int q = 0; q < nq; ++q) {
-            const VlmoTnProblem& r = probs[q0 + q];
-            const int tiles = ((r.N1 + 255) / 256) * ((r.N2 + 255) / 256);
-            const int nk = (r.M + 63) / 64;
-            int sp = splits > nk ? nk : splits;
-            const int per = (nk + sp - 1) / sp;
-            sp = (nk + per - 1) / per;
-            int mode = r.accumulate ? TN_ACCUM : TN_STORE;
-            if (sp > 1) {
-                mode = TN_ATOMIC;
-                if (!r.accumulate) {
-                    hipError_t rc = hipMemset2DAsync(r.C, (size_t)r.ldc * 4, 0, (size_t)r.N2 * 4, r.N1, stream);
-                    if (rc != hipSuccess) {
-                        vlmo_set_error("vlmo_gemm_tn_multi: memset failed: %s", hipGetErrorString(rc));
-                        return (int)rc;
-                    }
+        double flops = 0;
+        for (int q = 0; q < L.nq; ++q) {
+            const VlmoTnProblem& r = probs[L.q0 + q];
+            const VlmoTnProblemPlan& s = L.p[q];
+            if (s.zero_first) {
+                hipError_t rc = hipMemset2DAsync(r.C, (size_t)r.ldc * 4, 0, (size_t)r.N2 * 4, r.N1, stream);
+                if (rc != hipSuccess) {
+                    vlmo_set_error("vlmo_gemm_tn_multi: memset failed: %s", hipGetErrorString(rc));
+                    return (int)rc;
                 }
             }
-            VLMO_CHECK_ARG(tiles * sp <= 4096, "vlmo_gemm_tn_multi: problem %d has too many tiles", q0 + q);
-            mp.p[q] = GemmTN{r.A, r.B, r.C, r.M, r.N1, r.N2, r.lda, r.ldb, r.ldc, per, tiles, r.alpha, nullptr, mode};
-            for (int l = 0; l < tiles * sp; ++l) jobs.push_back(Job{(uint16_t)((q << 12) | l), per});
+            mp.p[q] = GemmTN{r.A, r.B, r.C, r.M, r.N1, r.N2, r.lda, r.ldb, r.ldc, s.kt_per_split, s.tiles, r.alpha, nullptr, s.mode};
+            flops += 2.0 * r.M * r.N1 * r.N2;
         }
-        // placement: classes of equal reduction length, longest first; every class is cut into 8 contiguous runs (a
-        // run = neighbouring tiles of one problem: they share operand panels through the XCD's L2) and XCD x takes run
-        // x of every class, so all XCDs get the same mix and, inside an XCD, long tiles are dispatched before short ones
-        std::stable_sort(jobs.begin(), jobs.end(), [](const Job& a, const Job& b) { return a.cost > b.cost; });
-        std::vector<uint16_t> bins[8];
-        for (size_t i = 0; i < jobs.size();) {
-            size_t j = i;
-            while (j < jobs.size() && jobs[j].cost == jobs[i].cost) ++j;
-            const size_t cnt = j - i;
-            for (int x = 0; x < 8; ++x)
-                for (size_t k = i + cnt * x / 8; k < i + cnt * (x + 1) / 8; ++k) bins[x].push_back(jobs[k].code);
-            i = j;
-        }
-        size_t deepest = 0;
-        for (int x = 0; x < 8; ++x) deepest = bins[x].size() > deepest ? bins[x].size() : deepest;
-        VLMO_CHECK_ARG(deepest * 8 <= (size_t)MAX_TN_ORDER, "vlmo_gemm_tn_multi: %zu workgroups exceed one launch (pass fewer problems per call)",
-                       jobs.size());
-        const int t = (int)deepest * 8;
-        for (int b = 0; b < t; ++b) {
-            const std::vector<uint16_t>& bin = bins[b & 7];
-            mp.order[b] = (size_t)(b >> 3) < bin.size() ? bin[b >> 3] : TN_NOP;
-        }
+        std::copy(L.order, L.order + L.grid, mp.order);
         ProfScope prof(73, flops, stream);
-        constexpr int LDS = 2 * 4 * 64 * 256;
         if (dtype == VLMO_F16)
-            hipLaunchKernelGGL((gemm_tn_multi_kernel<f16>), dim3(t), dim3(512), LDS, stream, mp);
+            hipLaunchKernelGGL((gemm_tn_multi_kernel<f16>), dim3(L.grid), dim3(512), TN_LDS_256, stream, mp);
         else
-            hipLaunchKernelGGL((gemm_tn_multi_kernel<bf16>), dim3(t), dim3(512), LDS, stream, mp);
+            hipLaunchKernelGGL((gemm_tn_multi_kernel<bf16>), dim3(L.grid), dim3(512), TN_LDS_256, stream, mp);
         VLMO_CHECK_LAUNCH("vlmo_gemm_tn_multi");
+    }
+    return 0;
+}
+
+extern "C" int vlmo_gemm_tn_multi_plan(const VlmoTnProblem* probs, int n, int32_t* n_launches, int32_t* launch_q0,
+                                       VlmoTnProblemPlan* prob, int32_t* grid, uint16_t* order) {
+    VLMO_CHECK_ARG(probs && n >= 1, "vlmo_gemm_tn_multi: no problems");
+    VLMO_CHECK_ARG(n_launches && launch_q0 && prob && grid && order, "vlmo_gemm_tn_multi_plan: null output");
+    const TnMultiPlan plan = plan_tn_multi(probs, n);
+    VLMO_CHECK_ARG(plan.error.empty(), "%s", plan.error.c_str());
+    *n_launches = (int32_t)plan.launches.size();
+    for (size_t k = 0; k < plan.launches.size(); ++k) {
+        const TnLaunchPlan& L = plan.launches[k];
+        launch_q0[k] = L.q0, launch_q0[k + 1] = L.q0 + L.nq;
+        std::copy(L.p, L.p + L.nq, prob + L.q0);
+        grid[k] = L.grid;
+        std::copy(L.order, L.order + L.grid, order + k * MAX_TN_ORDER);
     }
     return 0;
 }

@@ -69,6 +69,11 @@ class TnProblem(ctypes.Structure):
                 ('M', _i32), ('N1', _i32), ('N2', _i32), ('alpha', _f32), ('accumulate', _i32)]
 
 
+class TnProblemPlan(ctypes.Structure):
+    """Mirror of VlmoTnProblemPlan."""
+    _fields_ = [('tiles', _i32), ('splits', _i32), ('kt_per_split', _i32), ('mode', _i32), ('zero_first', _i32)]
+
+
 class ColJob(ctypes.Structure):
     """Mirror of VlmoColJob."""
     _fields_ = [('kind', _i32), ('ld', _i32), ('src', _vp), ('rows', _i32), ('ncols', _i32),
@@ -134,6 +139,8 @@ _SIGS = {
     'vlmo_stack_fwd': [ctypes.POINTER(StackDesc), _vp],
     'vlmo_stack_bwd': [ctypes.POINTER(StackDesc), _vp],
     'vlmo_gemm_tn_multi': [_i32, ctypes.POINTER(TnProblem), _i32, _vp],
+    'vlmo_gemm_tn_multi_plan': [ctypes.POINTER(TnProblem), _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32),
+                                ctypes.POINTER(TnProblemPlan), ctypes.POINTER(_i32), ctypes.POINTER(ctypes.c_uint16)],
     'vlmo_colwork_multi': [_i32, ctypes.POINTER(ColJob), _i32, _vp],
     'vlmo_event_create': [ctypes.POINTER(ctypes.c_void_p)],
     'vlmo_event_destroy': [_vp],
@@ -173,7 +180,7 @@ _SIGS = {
 }
 
 _lib = None
-ABI_VERSION = 15     # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
+ABI_VERSION = 16    # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
 
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is missing."""
@@ -560,6 +567,27 @@ def gemm_tn_multi(problems, dtype=BF16):
     for i, (A, B, C, M, N1, N2, acc) in enumerate(problems):
         arr[i] = TnProblem(_p(A), _p(B), _p(C), A.stride(0), B.stride(0), C.stride(0), M, N1, N2, 1.0, int(acc))
     _check(lib().vlmo_gemm_tn_multi(dtype, arr, n, _stream()), 'vlmo_gemm_tn_multi')
+
+
+TN_ORDER, TN_NOP = 1024, 0xFFFF      # a launch's placement table: entries, and the code of a workgroup that runs nothing
+
+
+def gemm_tn_multi_plan(shapes):
+    """What vlmo_gemm_tn_multi does with problems of these shapes (a host query: no GPU, no tensors).
+    shapes: [(M, N1, N2, accumulate)].  Returns one dict per launch: q0, nq (the problems it takes), problems
+    [(tiles, splits, kt_per_split, mode, zero_first)], grid and order (grid codes: (problem - q0) << 12 | workgroup
+    inside the problem, or TN_NOP; entry b runs on XCD b % 8)."""
+    n = len(shapes)
+    arr = (TnProblem * n)()
+    for i, (M, N1, N2, acc) in enumerate(shapes):
+        arr[i] = TnProblem(None, None, None, N1, N2, N2, M, N1, N2, 1.0, int(acc))
+    nl, q0 = _i32(0), (_i32 * (n + 1))()
+    pp, grid, order = (TnProblemPlan * n)(), (_i32 * n)(), (ctypes.c_uint16 * (n * TN_ORDER))()
+    _check(lib().vlmo_gemm_tn_multi_plan(arr, n, ctypes.byref(nl), q0, pp, grid, order), 'vlmo_gemm_tn_multi_plan')
+    return [dict(q0=q0[k], nq=q0[k + 1] - q0[k],
+                 problems=[(p.tiles, p.splits, p.kt_per_split, p.mode, p.zero_first) for p in pp[q0[k]:q0[k + 1]]],
+                 grid=grid[k], order=list(order[k * TN_ORDER:k * TN_ORDER + grid[k]]))
+            for k in range(nl.value)]
 
 
 def colwork_multi(jobs, dtype=BF16):

@@ -82,7 +82,7 @@ typedef struct VlmoEpilogue {
 const char* vlmo_last_error(void);
 /* Version of the struct layouts and signatures below; raised whenever one of them changes
  * (exploremultimodal_amd/hip.py mirrors it as ABI_VERSION and refuses any other). */
-#define VLMO_ABI_VERSION 15
+#define VLMO_ABI_VERSION 16
 int vlmo_abi_version(void);     /* = VLMO_ABI_VERSION of the header the library was built from */
 
 /* C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue.  tile: -1 = pick by shape, 0 = 128x128x64
@@ -124,10 +124,15 @@ int vlmo_gemm_tn(int dtype, const void* A, int lda, const void* B, int ldb, floa
                  int M, int N1, int N2, float alpha, int splits, float* ws, int64_t ws_bytes,
                  hipStream_t stream);
 
-/* Several weight gradients C_q[N1,N2] (+)= alpha * A_q[M,N1]^T . B_q[M,N2] in ONE launch of 256x256 tiles:
- * the qkv / proj / fc1 / fc2 gradients of one or two transformer blocks (autograd of vlmo.py:76-78,96,195-196)
- * together fill the chip without splitting the token dimension, so there are no partial slabs and no
- * reduction pass.  accumulate != 0: C += ..., else C = ...  No workspace. */
+/* Several weight gradients C_q[N1,N2] (+)= alpha * A_q[M,N1]^T . B_q[M,N2] in launches of 256x256 tiles: the
+ * qkv / proj / fc1 / fc2 gradients of one or two transformer blocks (autograd of vlmo.py:76-78,96,195-196).
+ * accumulate != 0: C += ..., else C = ...  No workspace.  A launch takes the next problems in the given order,
+ * at most 16 and at most 960 tiles together (a first problem is always taken).  From 192 tiles on (two VLMo-Base
+ * blocks have 216) the launch fills the chip as it is: every tile has one owner that stores or accumulates in place,
+ * no partial slabs, no reduction pass, bitwise reproducible.  Below 192 tiles the token dimension of every problem
+ * is split over up to 256 / tiles workgroups, which add into C with fp32 atomics (summation order varies); a
+ * non-accumulating output is zeroed first (a memset on `stream`).  Every argument of every problem is checked before
+ * anything is enqueued: after an argument error (< 0) no output has been touched. */
 typedef struct VlmoTnProblem {
     const void* A;
     const void* B;
@@ -138,6 +143,22 @@ typedef struct VlmoTnProblem {
     int32_t accumulate;
 } VlmoTnProblem;
 int vlmo_gemm_tn_multi(int dtype, const VlmoTnProblem* probs, int n, hipStream_t stream);
+/* What vlmo_gemm_tn_multi does with `probs`, from the one planner it executes.  A host function: no device, no stream;
+ * reads M, N1, N2 and accumulate of a problem and never its pointers or leading dimensions.  Launch k of *n_launches
+ * (<= n) takes the problems [launch_q0[k], launch_q0[k + 1]) and has grid[k] workgroups; workgroup b of it runs
+ * order[k * 1024 + b] = (problem index inside the launch << 12) | (workgroup index inside the problem: split * tiles +
+ * tile), or nothing (0xFFFF); b % 8 is the XCD.  Caller arrays: launch_q0 [n + 1], prob [n], grid [n], order [n * 1024]
+ * (entries past a launch's grid are not written).  Returns 0, or < 0 with nothing meaningful written when the call
+ * cannot be planned: vlmo_gemm_tn_multi then fails with the same message before it enqueues anything. */
+typedef struct VlmoTnProblemPlan {
+    int32_t tiles;          /* 256x256 output tiles                                                          */
+    int32_t splits;         /* workgroups per tile, each reducing kt_per_split 64-token K-tiles (the last: the rest) */
+    int32_t kt_per_split;
+    int32_t mode;           /* 0 = fp32 atomics into C (splits > 1), 1 = C += alpha * acc, 2 = C = alpha * acc */
+    int32_t zero_first;     /* C is zeroed before the launch (atomics into a non-accumulating output)        */
+} VlmoTnProblemPlan;
+int vlmo_gemm_tn_multi_plan(const VlmoTnProblem* probs, int n, int32_t* n_launches, int32_t* launch_q0,
+                            VlmoTnProblemPlan* prob, int32_t* grid, uint16_t* order);
 
 /* LayerNorm over the last dim (eps = 1e-12 in VLMo: vlmo_module.py:21-23; vlmo.py:188,192,413).
  * x fp32 [M,d] -> y (bf16, or fp32 when out_f32) at row rowmap[m] (or m), + mean/rstd [M]. */

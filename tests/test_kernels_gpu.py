@@ -716,6 +716,43 @@ def test_gemm_tn_multi_more_than_16_problems():
         assert torch.equal(p[2].cpu(), r)
 
 
+@pytest.mark.parametrize('good', [2, 16])
+def test_gemm_tn_multi_checks_every_problem_before_it_enqueues_anything(good):
+    """A malformed problem (lda < N1) behind `good` sound ones: the call fails and no output in front of it is touched.
+    Behind 16 the bad problem belongs to the second launch of the call; the first must not have gone out."""
+    M, N = 128, 256
+    A, B = torch.ones(M, N, device=DEV).bfloat16(), torch.ones(M, N, device=DEV).bfloat16()
+    Cs = [torch.full((N, N), -7.0, device=DEV) for _ in range(good + 1)]
+    arr = (hip.TnProblem * (good + 1))()
+    for i, C in enumerate(Cs):
+        arr[i] = hip.TnProblem(A.data_ptr(), B.data_ptr(), C.data_ptr(), N if i < good else N - 8, N, N, M, N, N, 1.0, i % 2)
+    assert hip.lib().vlmo_gemm_tn_multi(hip.BF16, arr, good + 1, torch.cuda.current_stream().cuda_stream) != 0
+    assert f'bad shape in problem {good}'.encode() in hip.lib().vlmo_last_error()
+    torch.cuda.synchronize()
+    for C in Cs:
+        assert torch.equal(C, torch.full_like(C, -7.0))
+
+
+def test_gemm_tn_multi_split_token_dimension_exact_integers():
+    """6 tiles and at least 21 K-tiles per problem: every problem's token dimension is split in two (ragged halves:
+    21 = 11 + 10, 47 = 24 + 23), the halves meet in fp32 atomics (exact and order-free on small integers) and the
+    non-accumulating output is zeroed first; its start values must not survive."""
+    g = torch.Generator().manual_seed(23)
+    shapes = [(2000, 256, 512, True), (1333, 96, 264, False), (3000, 512, 256, True)]
+    assert [p[1:] for p in hip.gemm_tn_multi_plan(shapes)[0]['problems']] == [(2, 16, 0, 0), (2, 11, 0, 1), (2, 24, 0, 0)]
+    probs, refs = [], []
+    for M, N1, N2, acc in shapes:
+        A = torch.randint(-2, 3, (M, N1), generator=g).float()
+        B = torch.randint(-2, 3, (M, N2), generator=g).float()
+        C0 = torch.randint(-4, 5, (N1, N2), generator=g).float()
+        probs.append((A.to(DEV).bfloat16(), B.to(DEV).bfloat16(), C0.to(DEV), M, N1, N2, acc))
+        refs.append(A.t() @ B + (C0 if acc else 0))
+    hip.gemm_tn_multi(probs)
+    torch.cuda.synchronize()
+    for p, r in zip(probs, refs):
+        assert torch.equal(p[2].cpu(), r), (p[2].cpu() - r).abs().max()
+
+
 def test_colwork_multi():
     """vlmo_colwork_multi: partial-row folds into up to four outputs and bf16 column sums, batched in one launch."""
     g = torch.Generator().manual_seed(3)
