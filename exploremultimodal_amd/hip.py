@@ -561,11 +561,13 @@ def dvae_out_head_linear(x, w, bias, out, B, H, W):
 
 
 def gemm_tn_multi(problems, dtype=BF16):
-    """problems: [(A, B, C, M, N1, N2, accumulate)] with A [M, >=N1], B [M, >=N2] bf16/f16 and C [N1, >=N2] fp32."""
+    """problems: [(A, B, C, M, N1, N2, accumulate[, alpha])] with A [M, >=N1], B [M, >=N2] bf16/f16 and C [N1, >=N2]
+    fp32: C (+)= alpha * A^T B, alpha 1 when the tuple leaves it out."""
     n = len(problems)
     arr = (TnProblem * n)()
-    for i, (A, B, C, M, N1, N2, acc) in enumerate(problems):
-        arr[i] = TnProblem(_p(A), _p(B), _p(C), A.stride(0), B.stride(0), C.stride(0), M, N1, N2, 1.0, int(acc))
+    for i, (A, B, C, M, N1, N2, acc, *alpha) in enumerate(problems):
+        arr[i] = TnProblem(_p(A), _p(B), _p(C), A.stride(0), B.stride(0), C.stride(0), M, N1, N2,
+                           float(alpha[0]) if alpha else 1.0, int(acc))
     _check(lib().vlmo_gemm_tn_multi(dtype, arr, n, _stream()), 'vlmo_gemm_tn_multi')
 
 

@@ -6,7 +6,7 @@ import torch
 
 from exploremultimodal_amd import hip
 from tests import attn_counter
-from tests.test_kernels_gpu import _attn_case, _attn_ref, _close, _rand
+from tests.kernel_refs import _attn_case, _attn_ref, _close, _rand
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'

@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 from exploremultimodal_amd import hip  # noqa: E402
 from tests import dropmask  # noqa: E402
-from tests.test_kernels_gpu import _close, _rand  # noqa: E402
+from tests.kernel_refs import _close, _rand  # noqa: E402
 
 DEV = 'cuda'
 P_DROP = 0.1

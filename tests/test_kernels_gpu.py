@@ -12,26 +12,9 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from exploremultimodal_amd import hip  # noqa: E402
-from tests.dropmask import hash32 as _hash32  # noqa: E402
+from tests.kernel_refs import _attn_case, _attn_keep_mask, _attn_ref, _close, _rand  # noqa: E402
 
 DEV = 'cuda'
-
-
-def _rand(*shape, scale=1.0, seed=0, dtype=torch.bfloat16):
-    g = torch.Generator(device='cpu').manual_seed(seed)
-    return (torch.randn(*shape, generator=g) * scale).to(DEV).to(dtype)
-
-
-def _close(got, ref, rtol, atol, what=''):
-    got, ref = got.float(), ref.float()
-    err = (got - ref).abs()
-    lim = atol + rtol * ref.abs()
-    bad = err > lim
-    if bad.any():
-        idx = bad.nonzero()[0].tolist()
-        raise AssertionError(
-            f'{what}: {int(bad.sum())}/{bad.numel()} mismatches, max err {err.max().item():.4g} '
-            f'first at {idx}: got {got[tuple(idx)].item():.6g} ref {ref[tuple(idx)].item():.6g}')
 
 
 @pytest.mark.parametrize('tile', [0, 3, 4])
@@ -66,7 +49,7 @@ def test_gemm_nt_bias_bf16_and_padding_rows(tile):
     _close(out2, ref.relu(), 1 / 128, 1e-2, 'bias+relu epilogue')
 
 
-@pytest.mark.parametrize('tile', [4, 8, 106, 110, 309, 310, 311, 312, 313, 315, 317, 319, 320])
+@pytest.mark.parametrize('tile', [4, 8, 106, 107, 108, 109, 110, 309, 310, 311, 312, 313, 314, 315, 316, 317, 318, 319, 320])
 @pytest.mark.parametrize('M,N,K', [(1000, 384, 768), (4099, 2304, 768), (77, 128, 192)])
 def test_gemm_nt_tile4_small_integers(tile, M, N, K):
     """The 256x128x32 and 192x256x64 tiles and the 16x16x32-MFMA tiles 309..320 ((16 * (tile - 300)) x 256, odd heights = wave groups of different size; 106..110 = 32 * (tile - 100) rows: a new fragment
@@ -239,7 +222,7 @@ def test_gemm_nt_dgelu_column_partials(M):
     want = (A.float() @ B.float().t()) * a.grad
     nblk = (M + 15) // 16
     ref16 = torch.stack([want[16 * b:16 * b + 16].sum(0) for b in range(nblk)])
-    for tile in (0, 3, 8, 106, 309, 310, 311, 312, 313, 315, 316, 317, 319, 320):
+    for tile in (0, 3, 8, 106, 107, 108, 109, 309, 310, 311, 312, 313, 314, 315, 316, 317, 318, 319, 320):
         cp = torch.full((nblk + 1, N), float('nan'), device=DEV)
         dg2 = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
         hip.gemm_nt(hip.EPI_DGELU, A, B, M, N, K, dg2, aux=aux, colpart=cp, tile=tile)
@@ -354,62 +337,6 @@ def test_layernorm_fwd_bwd(M, d):
     dx2 = torch.empty(M, d, device=DEV)
     hip.ln_bwd(dy32, perm, x, w, mean, rstd, None, dx2, None, None, M, d)
     _close(dx2, xr.grad, 1e-3, 1e-3, 'ln dx rowmap')
-
-
-def _attn_case(B, lenA, lenB, heads, seed=0, mask_frac=0.3):
-    """packed rows: all A segments, then all B segments."""
-    d = heads * 64
-    M = B * (lenA + lenB)
-    qkv = _rand(M, 3 * d, seed=seed, scale=1.0)
-    seg = torch.tensor([[b * lenA, lenA, B * lenA + b * lenB, lenB] for b in range(B)], dtype=torch.int32)
-    keymask = torch.ones(M, dtype=torch.int32)
-    g = torch.Generator().manual_seed(seed + 1)
-    for b in range(B):
-        if b % 2 == 1 and lenA > 4:
-            p0 = int(torch.randint(2, lenA, (1,), generator=g))
-            keymask[b * lenA + p0:(b + 1) * lenA] = 0
-    return qkv, seg.to(DEV), keymask.to(DEV), M, d
-
-
-def _attn_keep_mask(seed, nseq, heads, N, thresh):
-    """[nseq, heads, N(q), N(key)] bool: the keep mask of the attention kernels' counter-based dropout
-    (csrc/attention.hip att_key / att_mix): top 16 bits of mix((q * 512 + key) * G + key(seed, bh)) >= thresh."""
-    m = np.uint64(0xFFFFFFFF)
-    bh = (np.arange(nseq, dtype=np.uint64)[:, None] * np.uint64(heads) + np.arange(heads, dtype=np.uint64)[None, :])
-    lo, hi = np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32)
-    akey = (_hash32((lo ^ ((bh * np.uint64(0x9E3779B9)) & m)) & m) + hi) & m
-    q = np.arange(N, dtype=np.uint64)[None, None, :, None]
-    key = np.arange(N, dtype=np.uint64)[None, None, None, :]
-    x = ((((q * np.uint64(512) + key) & m) * np.uint64(0x9E3779B1)) + akey[:, :, None, None]) & m
-    x = x ^ (x >> np.uint64(15))
-    x = (x * np.uint64(0x7feb352d)) & m
-    return torch.from_numpy((x >> np.uint64(16)) >= np.uint64(thresh))
-
-
-def _attn_ref(qkv, seg, keymask, heads, d, dctx=None, keep=None, inv_keep=1.0):
-    """fp32 torch reference per sequence (vlmo.py:79-95); returns ctx (+ dqkv).  keep: optional dropout keep
-    mask [nseq, heads, N, N] applied to the probabilities (vlmo.py:93)."""
-    q = qkv.float().clone().requires_grad_(dctx is not None)
-    ctx = torch.zeros(q.shape[0], d, device=q.device)
-    outs = []
-    for si, s in enumerate(seg.tolist()):
-        rows = torch.cat([torch.arange(s[0], s[0] + s[1]), torch.arange(s[2], s[2] + s[3])]).to(q.device)
-        x = q[rows]
-        N = x.shape[0]
-        qq, kk, vv = [x[:, i * d:(i + 1) * d].reshape(N, heads, 64).transpose(0, 1) for i in range(3)]
-        att = (qq @ kk.transpose(-2, -1)) * 64 ** -0.5
-        att = att.masked_fill(~keymask[rows].bool()[None, None, :], float('-inf')).softmax(-1)
-        if keep is not None:
-            att = att * keep[si, :, :N, :N].to(att.device) * inv_keep
-        o = (att @ vv).transpose(0, 1).reshape(N, d)
-        outs.append((rows, o))
-    ctx = torch.zeros(q.shape[0], d, device=q.device)
-    for rows, o in outs:
-        ctx = ctx.index_add(0, rows, o)
-    if dctx is None:
-        return ctx.detach()
-    ctx.backward(dctx.float())
-    return ctx.detach(), q.grad
 
 
 @pytest.mark.parametrize('B,lenA,lenB,heads', [(3, 16, 17, 2), (2, 64, 0, 2), (2, 0, 197, 1),
