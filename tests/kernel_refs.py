@@ -80,3 +80,22 @@ def _attn_ref(qkv, seg, keymask, heads, d, dctx=None, keep=None, inv_keep=1.0):
         return ctx.detach()
     ctx.backward(dctx.float())
     return ctx.detach(), q.grad
+
+
+def _attn_lse_close(lse, qkv, seg, keymask, heads, d, what=''):
+    """the forward's log-sum-exp [nseq * heads, >= N] against fp64 torch per sequence and head, at the tolerance
+    a + b |lse| of tests/attn_cases.py (four times the error of an fp32 emulation of the kernels' formula)"""
+    from tests.attn_cases import lse_tol
+    x = qkv.double()
+    for si, s in enumerate(seg.tolist()):
+        rows = torch.cat([torch.arange(s[0], s[0] + s[1]), torch.arange(s[2], s[2] + s[3])]).to(x.device)
+        N = len(rows)
+        qq, kk = [x[rows][:, i * d:(i + 1) * d].reshape(N, heads, 64).transpose(0, 1) for i in range(2)]
+        att = (qq @ kk.transpose(-2, -1)) * 64 ** -0.5
+        want = att.masked_fill(~keymask[rows].bool()[None, None, :], float('-inf')).logsumexp(-1)
+        have = lse[si * heads:(si + 1) * heads, :N].double()
+        bad = ~((have - want).abs() <= lse_tol(want))             # a NaN left in lse is bad
+        if bad.any():
+            idx = bad.nonzero()[0].tolist()
+            raise AssertionError(f'attn lse {what}: sequence {si}, {int(bad.sum())}/{bad.numel()} mismatches, first at '
+                                 f'{idx}: got {have[tuple(idx)].item():.9g} ref {want[tuple(idx)].item():.9g}')

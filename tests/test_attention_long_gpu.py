@@ -6,7 +6,7 @@ import torch
 
 from exploremultimodal_amd import hip
 from tests import attn_counter
-from tests.kernel_refs import _attn_case, _attn_ref, _close, _rand
+from tests.kernel_refs import _attn_case, _attn_lse_close, _attn_ref, _close, _rand
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -39,9 +39,10 @@ def _fwd_bwd(qkv, seg, keymask, heads, d, max_len, dctx, drop=None, seed=0):
     return ctx, lse, dqkv, qv
 
 
-def _check(qkv, seg, keymask, heads, d, ctx, dqkv, qv, dctx, keep=None, inv_keep=1.0, what=''):
+def _check(qkv, seg, keymask, heads, d, ctx, dqkv, qv, dctx, keep=None, inv_keep=1.0, what='', *, lse):
     ref_ctx, ref_dqkv = _attn_ref(qkv, seg, keymask, heads, d, dctx, keep=keep, inv_keep=inv_keep)
     _close(ctx, ref_ctx, 1 / 64, 1e-2, f'attn ctx {what}')
+    _attn_lse_close(lse, qkv, seg, keymask, heads, d, what)
     scale = ref_dqkv.abs().max().item()
     _close(dqkv, ref_dqkv, 1 / 32, 2e-2 * scale, f'attn dqkv {what}')
     for si, sg in enumerate(seg.tolist()):
@@ -56,8 +57,8 @@ def test_long_attention_fwd_bwd(B, lenA, lenB, heads):
     qkv, seg, keymask, M, d = _attn_case(B, lenA, lenB, heads, seed=B + lenA + lenB)
     N = lenA + lenB
     dctx = _rand(M, d, seed=77)
-    ctx, _, dqkv, qv = _fwd_bwd(qkv, seg, keymask, heads, d, N, dctx)
-    _check(qkv, seg, keymask, heads, d, ctx, dqkv, qv, dctx, what=f'N={N}')
+    ctx, lse, dqkv, qv = _fwd_bwd(qkv, seg, keymask, heads, d, N, dctx)
+    _check(qkv, seg, keymask, heads, d, ctx, dqkv, qv, dctx, what=f'N={N}', lse=lse)
 
 
 def _mixed_case(heads=2, seed=21):
@@ -82,10 +83,10 @@ def test_long_attention_mixed_lengths_in_one_launch(dropout):
     drop = hip.drop_params(0.1, True) if dropout else None
     seed = 0x5EED5EED1
     dctx = _rand(M, d, seed=81)
-    ctx, _, dqkv, qv = _fwd_bwd(qkv, seg, keymask, heads, d, max(lens), dctx, drop=drop, seed=seed)
+    ctx, lse, dqkv, qv = _fwd_bwd(qkv, seg, keymask, heads, d, max(lens), dctx, drop=drop, seed=seed)
     keep = attn_counter.keep_mask(seed, lens, heads, drop[0]) if dropout else None
     _check(qkv, seg, keymask, heads, d, ctx, dqkv, qv, dctx, keep=keep, inv_keep=drop[1] if dropout else 1.0,
-           what='(mixed)')
+           what='(mixed)', lse=lse)
 
 
 @pytest.mark.parametrize('B,lenA,lenB,heads', [(2, 40, 577, 2), (1, 64, 901, 1), (1, 0, 289, 1), (2, 16, 497, 1)])
@@ -99,8 +100,8 @@ def test_long_attention_dropout_forward_and_backward_use_the_same_mask(B, lenA, 
     keep = attn_counter.keep_mask(seed, _lens(seg), heads, drop[0])
     assert abs(keep.float().mean().item() - 0.9) < 0.01
     dctx = _rand(M, d, seed=78)
-    ctx, _, dqkv, qv = _fwd_bwd(qkv, seg, keymask, heads, d, N, dctx, drop=drop, seed=seed)
-    _check(qkv, seg, keymask, heads, d, ctx, dqkv, qv, dctx, keep=keep, inv_keep=drop[1], what=f'(dropout, N={N})')
+    ctx, lse, dqkv, qv = _fwd_bwd(qkv, seg, keymask, heads, d, N, dctx, drop=drop, seed=seed)
+    _check(qkv, seg, keymask, heads, d, ctx, dqkv, qv, dctx, keep=keep, inv_keep=drop[1], what=f'(dropout, N={N})', lse=lse)
 
 
 def test_split_backward_of_a_shared_384px_launch_regenerates_the_forward_mask():
@@ -130,8 +131,8 @@ def test_split_backward_of_a_shared_384px_launch_regenerates_the_forward_mask():
                  qv_colsum=qv2[B:], mask_seq0=B, **kw)
     torch.cuda.synchronize()
     keep = attn_counter.keep_mask(seed, _lens(seg), heads, drop[0])
-    _check(qkv, seg, keymask, heads, d, ctx, dqkv1, qv1, dctx, keep=keep, inv_keep=drop[1], what='(one launch)')
-    _check(qkv, seg, keymask, heads, d, ctx, dqkv2, qv2, dctx, keep=keep, inv_keep=drop[1], what='(split)')
+    _check(qkv, seg, keymask, heads, d, ctx, dqkv1, qv1, dctx, keep=keep, inv_keep=drop[1], what='(one launch)', lse=lse)
+    _check(qkv, seg, keymask, heads, d, ctx, dqkv2, qv2, dctx, keep=keep, inv_keep=drop[1], what='(split)', lse=lse)
     # the image rows are the same kernels on the same operands: bit-identical; the text rows come from another kernel
     img = torch.arange(B * T, M, device=DEV)
     assert torch.equal(dqkv1[img], dqkv2[img])

@@ -12,7 +12,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from exploremultimodal_amd import hip  # noqa: E402
-from tests.kernel_refs import _attn_case, _attn_keep_mask, _attn_ref, _close, _rand  # noqa: E402
+from tests.kernel_refs import _attn_case, _attn_keep_mask, _attn_lse_close, _attn_ref, _close, _rand  # noqa: E402
 
 DEV = 'cuda'
 
@@ -351,6 +351,7 @@ def test_attention_fwd_bwd(B, lenA, lenB, heads):
     dctx = _rand(M, d, seed=77)
     ref_ctx, ref_dqkv = _attn_ref(qkv, seg, keymask, heads, d, dctx)
     _close(ctx, ref_ctx, 1 / 64, 1e-2, 'attn ctx')
+    _attn_lse_close(lse.view(B * heads, -1), qkv, seg, keymask, heads, d)
     dqkv = torch.zeros(M, 3 * d, device=DEV, dtype=torch.bfloat16)
     qv = torch.full((B, 2 * d), float('nan'), device=DEV)
     hip.attn_bwd(qkv, ctx, dctx, lse.view(B * heads, -1), seg, B, keymask, dqkv, heads, d, N, 64 ** -0.5, qv_colsum=qv)

@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 from exploremultimodal_amd import hip  # noqa: E402
 from tests import dropmask  # noqa: E402
-from tests.kernel_refs import _attn_keep_mask, _attn_ref, _close  # noqa: E402
+from tests.kernel_refs import _attn_keep_mask, _attn_lse_close, _attn_ref, _close  # noqa: E402
 
 DEV = 'cuda'
 DROP = hip.drop_params(0.1, True)            # (thresh, inv_keep)
@@ -674,6 +674,7 @@ def test_attention_with_four_workgroups_per_compute_unit(dropout):
     hip.attn_fwd(qkv, seg, nseq, keymask, ctx, lse, heads, d, N, 64 ** -0.5, **kw)
     ref_ctx, ref_dqkv = _attn_ref(qkv, seg, keymask, heads, d, dctx, keep=keep, inv_keep=drop[1] if drop else 1.0)
     _close(ctx, ref_ctx, 1 / 64, 1e-2, 'attn ctx (full chip)')
+    _attn_lse_close(lse, qkv, seg, keymask, heads, d, '(full chip)')
     dqkv = torch.full((M, 3 * d), float('nan'), device=DEV, dtype=torch.bfloat16)
     qv = torch.full((nseq, 2 * d), float('nan'), device=DEV)
     hip.attn_bwd(qkv, ctx, dctx, lse, seg, nseq, keymask, dqkv, heads, d, N, 64 ** -0.5, qv_colsum=qv, **kw)
