@@ -5,9 +5,10 @@
 // K and V sit in LDS (<= 36 KB each) and the scores of a 32-query tile never
 // leave registers: no N x N tensor in HBM (the reference materialises [B,h,N,N]
 // several times).  Forward: attn_fwd1_kernel (one wave per query tile, key
-// tiles one at a time with a lazily rescaled running maximum; sequences of up
-// to 288 tokens) and attn_fwd_kernel (128-key chunks with an exact running
-// maximum; up to 512).  Backward: attn_bwd1_kernel (single pass; up to 256
+// tiles one at a time with a lazily rescaled running maximum; up to 256 tokens
+// as it is, 257 - 288 in its FRINGE form: eight waves for the eight full query
+// tiles, the fringe queries split over them by key tile) and attn_fwd_kernel
+// (128-key chunks with an exact running maximum; up to 512).  Backward: attn_bwd1_kernel (single pass; up to 256
 // tokens as it is, 257 - 288 in its FRINGE form: eight full tiles + one
 // fringe tile).
 // Higher resolutions (384 / 480 px: 577 / 901 image tokens, up to 965 fused)
@@ -288,12 +289,34 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnArgs a, cons
 //   * the S^T product of tile t + 1 is issued before the soft-max arithmetic of tile t, whose P^T V products run under the
 //     next tile's arithmetic: the matrix pipe works while the wave issues vector instructions.
 // ~110 registers: four waves per SIMD, two workgroups per CU at 197 tokens.
-__global__ __launch_bounds__(576) void attn_fwd1_kernel(const AttnArgs a, const int NPAD) {
+//
+// FRINGE form, launches of 257 - 288 tokens (the fused layers at 64 text tokens: 261).  Nine waves are 576 threads: three
+// waves on one SIMD and one workgroup per CU.  Here EIGHT waves run the walk above for query tiles 0 - 7 over all nine
+// key tiles, then share the <= 32 fringe queries (tokens 256 ..) by KEY tile:
+//   * wave w forms S^T(key tile w, fringe queries), wave 0 key tile 8 as well; the row maxima of the nine tiles meet in
+//     LDS (one barrier), so every wave forms p = exp2(c S - c m*) against the FINAL maximum: no rescale, the result is
+//     a fixed function of the inputs; the row sums are written per key tile and added in key-tile order;
+//   * after dropout (the counter q * 512 + key of the walk, so the backward regenerates the same mask) a lane's packed
+//     P^T registers ARE the B operand a lane of the same index needs for O^T += V^T P^T, so they cross LDS lane-linear
+//     (16 bytes per lane and half tile: conflict-free ds_write_b128 / ds_read_b128, no transposed layout);
+//   * waves 6 and 7, one 32-feature half each, add the nine products in key-tile order.  The P^T tiles take turns in
+//     three 2 KB slots (key tiles 0-2, 3-5, 6-8, a barrier pair per group): no fp32 partial O tiles in LDS.
+// LDS: the K and V images hold NPAD = ceil(max_len / 8) * 8 rows, not 288; the 4 KB image of the fringe queries shares
+// the bytes of the P slots (every wave has its Q fragments in registers before the barrier that precedes the first P
+// write).  Key tile 8 reads 288 - NPAD rows past either image: past K lies V, past V lie the fringe Q rows and later
+// the P tiles -- finite values of the head's own data under a key bias of -inf (S = -inf, p = 0 exactly).
+// 2 * 128 NPAD + 6 KB slots + 3 * 1152 B (key bias, maxima, sums): 77 184 bytes at 261 tokens; two workgroups share a CU
+// (163 840 bytes, 4 waves per SIMD at <= 128 registers) up to NPAD = 280, i.e. max_len <= 280; 281 - 288 run one per CU.
+// Sequences of <= 256 tokens inside a FRINGE launch run the walk only, bit for bit what a 256-token launch gives them.
+#define ATT_F1_SLOTS 6144
+template <bool FRINGE>
+__global__ __launch_bounds__(FRINGE ? 512 : 576) void attn_fwd1_kernel(const AttnArgs a, const int NPAD) {
     const int IMG = NPAD * 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Kimg = smem;
     char* Vimg = smem + IMG;
-    float* kbias = (float*)(smem + 2 * IMG);
+    char* Pbuf = smem + 2 * IMG;                                 // FRINGE: fringe Q image, then the P^T slots
+    float* kbias = (float*)(smem + 2 * IMG + (FRINGE ? ATT_F1_SLOTS : 0));
 
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -313,7 +336,8 @@ __global__ __launch_bounds__(576) void attn_fwd1_kernel(const AttnArgs a, const 
 #pragma unroll
         for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qp + 16 * s);
     }
-    for (int ii = w; ii < nq * 4; ii += nw) {
+    const int ninstr = FRINGE ? min(nq * 4, NPAD >> 3) : nq * 4;
+    for (int ii = w; ii < ninstr; ii += nw) {
         const int chhi = lane >> 5, rowlo = (lane >> 2) & 7, pc = lane & 3;
         const int row = ii * 8 + rowlo;
         const int ch = chhi * 4 + (pc ^ ((row >> 2) & 3));
@@ -321,7 +345,13 @@ __global__ __launch_bounds__(576) void attn_fwd1_kernel(const AttnArgs a, const 
         glds16(a.qkv + r * ld + a.d + hd * 64 + ch * 8, Kimg + ii * 1024);
         glds16(a.qkv + r * ld + 2 * a.d + hd * 64 + ch * 8, Vimg + ii * 1024);
     }
-    for (int i = threadIdx.x; i < NPAD; i += blockDim.x) {
+    if (FRINGE && nq == 9 && w < 4) {        // the fringe queries' rows, same image layout (tokens past N: the last row)
+        const int chhi = lane >> 5, rowlo = (lane >> 2) & 7, pc = lane & 3;
+        const int row = w * 8 + rowlo;
+        const int ch = chhi * 4 + (pc ^ ((row >> 2) & 3));
+        glds16(a.qkv + (size_t)sr.row(256 + row) * ld + hd * 64 + ch * 8, Pbuf + w * 1024);
+    }
+    for (int i = threadIdx.x; i < (FRINGE ? 288 : NPAD); i += blockDim.x) {
         kbias[i] = key_bias(a.keymask, sr.row(i), i, N);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -429,6 +459,108 @@ __global__ __launch_bounds__(576) void attn_fwd1_kernel(const AttnArgs a, const 
     const float l_tot = l_run + other_half(l_run);
     // the reference maximum is in raw score units here
     if (qi < N) store_ctx(a, O, l_tot, (m_run * c2 + log2f(l_tot)) * LN2, bh, hd, qi, qrow, h);
+
+    if constexpr (FRINGE) {
+        if (nq < 9) return;                 // the whole workgroup: N <= 256
+        float* fmax = kbias + 288;          // [9][32] row maxima of the fringe queries per key tile, raw score units
+        float* fsum = fmax + 288;           // [9][32] row sums per key tile
+        bf16x8 qF[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) qF[s] = rfrag(Pbuf, s);
+        auto s_fringe = [&](int kt) -> f32x16 {
+            f32x16 acc;
+            const float* kb = kbias + kt * 32 + 4 * h;
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const f32x4 v = *(const f32x4*)(kb + 8 * g4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[4 * g4 + e] = v[e];
+            }
+            const char* kimg = Kimg + 4096 * kt;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc = Elem<bf16>::mfma(rfrag(kimg, s), qF[s], acc);
+            return acc;
+        };
+        auto tile_max = [&](const f32x16& S) -> float {
+            float mx = S[0];
+#pragma unroll
+            for (int i = 1; i < 16; ++i) mx = fmaxf(mx, S[i]);
+            return fmaxf(mx, other_half(mx));
+        };
+        const bool two = (w == 0);          // wave 0 takes key tile 8 as well
+        f32x16 SA = s_fringe(w), SB = SA;
+        if (two) SB = s_fringe(8);
+        {
+            const float ma = tile_max(SA), mb = tile_max(SB);
+            if (h == 0) {
+                fmax[w * 32 + l31] = ma;
+                if (two) fmax[8 * 32 + l31] = mb;
+            }
+        }
+        __syncthreads();                    // the maxima are complete; every wave holds its fringe Q fragments
+        float mstar = fmax[l31];
+#pragma unroll
+        for (int t = 1; t < 9; ++t) mstar = fmaxf(mstar, fmax[t * 32 + l31]);
+        const float msubF = (mstar == -INFINITY) ? 0.f : -mstar * c2;
+        const uint32_t rqF = ((uint32_t)(256 + l31) * 512u + 4u * h) * ATT_G + akey;
+        // p = exp2(c S - c m*) in place, the tile's row sum to fsum, dropout, bf16 pack: the B operands of the tile
+        auto soft_pack = [&](f32x16& S, int kt, bf16x8 (&pf)[2]) {
+            float l = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                S[i] = __builtin_amdgcn_exp2f(fmaf(S[i], c2, msubF));
+                l += S[i];
+            }
+            l += other_half(l);
+            if (h == 0) fsum[kt * 32 + l31] = l;
+            if (a.drop_thresh) S = drop_tile(S, rqF + (uint32_t)(kt * 32) * ATT_G, a.drop_cmp);
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pf[s2][j] = (bf16)S[8 * s2 + j];
+        };
+        bf16x8 pA[2], pB[2];
+        soft_pack(SA, w, pA);
+        if (two) soft_pack(SB, 8, pB);
+        const int dtF = w & 1;              // waves 6 / 7: features [0, 32) / [32, 64)
+        f32x16 OF = zero16();
+        for (int g = 0; g < 3; ++g) {
+            if (w / 3 == g) {
+                *(bf16x8*)(Pbuf + (w % 3) * 2048 + lane * 16) = pA[0];
+                *(bf16x8*)(Pbuf + (w % 3) * 2048 + 1024 + lane * 16) = pA[1];
+            }
+            if (g == 2 && two) {
+                *(bf16x8*)(Pbuf + 2 * 2048 + lane * 16) = pB[0];
+                *(bf16x8*)(Pbuf + 2 * 2048 + 1024 + lane * 16) = pB[1];
+            }
+            __syncthreads();
+            if (w >= 6) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+#pragma unroll
+                    for (int s2 = 0; s2 < 2; ++s2) {
+                        const bf16x8 pf = *(const bf16x8*)(Pbuf + j * 2048 + s2 * 1024 + lane * 16);
+                        OF = Elem<bf16>::mfma(tfrag(Vimg + 4096 * (3 * g + j) + 2048 * s2, dtF), pf, OF);
+                    }
+            }
+            if (g < 2) __syncthreads();     // the slots are free again
+        }
+        const int qiF = 256 + l31;
+        if (w >= 6 && qiF < N) {
+            float l = fsum[l31];
+#pragma unroll
+            for (int t = 1; t < 9; ++t) l += fsum[t * 32 + l31];
+            const float inv = a.inv_keep / l;
+            bf16* op = a.out + (size_t)sr.row(qiF) * a.d + hd * 64 + 4 * h + dtF * 32;
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                bf16x4 o = {(bf16)(OF[4 * g4 + 0] * inv), (bf16)(OF[4 * g4 + 1] * inv), (bf16)(OF[4 * g4 + 2] * inv),
+                            (bf16)(OF[4 * g4 + 3] * inv)};
+                *(bf16x4*)(op + 8 * g4) = o;
+            }
+            if (w == 6 && h == 0 && a.lse) a.lse[(size_t)bh * a.lse_stride + qiF] = (mstar * c2 + log2f(l)) * LN2;
+        }
+    }
 }
 
 // ------------------------------------------------------------------ backward
@@ -1596,7 +1728,12 @@ void launch_fwd(const AttnArgs& a, int nt, int nblocks, hipStream_t st) {
     launch<attn_fwd_kernel>(dim3(nblocks), 256, nt * 32 * 256 + nt * 32 * 8, st, a, nt * 32);
 }
 void launch_fwd1(const AttnArgs& a, int nt, int nblocks, hipStream_t st) {
-    launch<attn_fwd1_kernel>(dim3(nblocks), nt * 64, nt * 32 * 256 + nt * 32 * 4, st, a, nt * 32);
+    launch<attn_fwd1_kernel<false>>(dim3(nblocks), nt * 64, nt * 32 * 256 + nt * 32 * 4, st, a, nt * 32);
+}
+// 257 - 288 tokens: eight waves, images of ceil(max_len / 8) * 8 rows (attn_fwd1_kernel, FRINGE form)
+void launch_fwd1_fringe(const AttnArgs& a, int max_len, int nblocks, hipStream_t st) {
+    const int rows = (max_len + 7) / 8 * 8;
+    launch<attn_fwd1_kernel<true>>(dim3(nblocks), 512, rows * 256 + ATT_F1_SLOTS + 3 * 288 * 4, st, a, rows);
 }
 template <bool FRINGE>
 int launch_bwd1(const AttnArgs& a, int nt, int nblocks, hipStream_t st) {
@@ -1685,7 +1822,8 @@ extern "C" int vlmo_attn_fwd(const void* qkv, const int32_t* seg, int num_seq, c
         VLMO_CHECK_LAUNCH("vlmo_attn_fwd(long)");
         return 0;
     }
-    if (nt <= 9) launch_fwd1(a, nt, nb, stream);
+    if (nt == 9) launch_fwd1_fringe(a, max_len, nb, stream);
+    else if (nt < 9) launch_fwd1(a, nt, nb, stream);
     else launch_fwd(a, nt, nb, stream);
     VLMO_CHECK_LAUNCH("vlmo_attn_fwd");
     return 0;

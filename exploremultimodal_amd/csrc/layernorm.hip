@@ -100,6 +100,53 @@ struct ResidArgs {
     uint64_t seed1;
 };
 
+// Row ring of ln_bwd_kernel: what a row needs from HBM waits in LDS, not in registers.  One slot = the row's dy, x,
+// dres and zd pieces, each a linear copy of the global bytes filled by LDS-DMA (one wave-instruction = 1 KB: lane l
+// brings bytes [16 l, 16 l + 16) of its KB; the lanes past a piece's end repeat the piece's last 16 bytes, which land
+// in the padding up to the next whole KB).  The lane reads its vectors back at j * 1024 + 16 lane (fp32 pieces,
+// ds_read_b128) or j * 512 + 8 lane (bf16 pieces, ds_read_b64).  tests/test_ln_ring_layout.py restates this on the host.
+// A workgroup of 4 waves with two slots per wave stays within 80 KB (two workgroups per CU) up to VPL = 3, d <= 768:
+// 10 KB per slot in the fused form.  VPL = 4 (d <= 1024) has 12 KB slots and one of them per wave, 48 KB; there the 64 KB
+// of the column fold set the workgroup's LDS, as before.
+template <int VPL, bool DY_F32, bool RESID> struct LnRing {
+    static constexpr int HALF = ((VPL + 1) / 2) * 1024;      // a bf16 piece: whole LDS-DMA instructions
+    static constexpr int FULL = VPL * 1024;                  // an fp32 piece
+    static constexpr int DY = 0, X = DY_F32 ? FULL : HALF, DR = X + FULL, Z = DR + FULL;
+    static constexpr int SLOT = Z + (RESID ? HALF : 0);
+    static constexpr int NSLOT = (8 * SLOT <= 80 * 1024) ? 2 : 1;
+    static constexpr int BYTES = 4 * NSLOT * SLOT;
+    static constexpr int STORES = VPL * (RESID ? 2 : 1);     // vector stores per row: dx (, dz)
+};
+
+// s_waitcnt vmcnt(n), n wave-uniform (the instruction takes an immediate)
+__device__ __forceinline__ void wait_vmcnt(int n) {
+#define VLMO_VMCNT_CASE(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
+    switch (n) {
+        VLMO_VMCNT_CASE(1) VLMO_VMCNT_CASE(2) VLMO_VMCNT_CASE(3) VLMO_VMCNT_CASE(4) VLMO_VMCNT_CASE(5) VLMO_VMCNT_CASE(6)
+        VLMO_VMCNT_CASE(7) VLMO_VMCNT_CASE(8) VLMO_VMCNT_CASE(9) VLMO_VMCNT_CASE(10) VLMO_VMCNT_CASE(11) VLMO_VMCNT_CASE(12)
+        VLMO_VMCNT_CASE(13) VLMO_VMCNT_CASE(14) VLMO_VMCNT_CASE(15) VLMO_VMCNT_CASE(16) VLMO_VMCNT_CASE(17) VLMO_VMCNT_CASE(18)
+        VLMO_VMCNT_CASE(19) VLMO_VMCNT_CASE(20) VLMO_VMCNT_CASE(21) VLMO_VMCNT_CASE(22) VLMO_VMCNT_CASE(23) VLMO_VMCNT_CASE(24)
+        VLMO_VMCNT_CASE(25) VLMO_VMCNT_CASE(26) VLMO_VMCNT_CASE(27) VLMO_VMCNT_CASE(28) VLMO_VMCNT_CASE(29) VLMO_VMCNT_CASE(30)
+        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    }
+#undef VLMO_VMCNT_CASE
+}
+
+// A 32-bit word at a wave-uniform address through the scalar cache (read-only inputs only).  The pointers inside
+// ResidArgs carry no no-alias promise, so hipcc reads through them with vector loads, and beside an LDS-DMA in flight it
+// waits vmcnt(0) at the use of any vector load's result: the ring would drain once per row.
+__device__ __forceinline__ uint32_t scalar_load32(const void* p) {
+    uint32_t v;
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
+    return v;
+}
+
+// one piece of a slot: NI LDS-DMA instructions over nb bytes (a multiple of 16) at src
+template <int NI> __device__ __forceinline__ void ring_piece(const char* src, int nb, char* dst, int lane) {
+#pragma unroll
+    for (int jj = 0; jj < NI; ++jj) glds16(src + min(jj * 1024 + lane * 16, nb - 16), dst + jj * 1024);
+}
+
 template <int VPL, bool DY_F32, bool RESID>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy, const int32_t* __restrict__ rowmap,
                                                      const float* __restrict__ x, const float* __restrict__ w,
@@ -108,8 +155,13 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
                                                      float* __restrict__ ws, int M, int d, int rows_per_block,
                                                      const ResidArgs ra) {
     constexpr int NCOL = RESID ? 4 : 2;      // column partials per block: dw, db (, dgamma, dbias)
-    __shared__ float red[4][NCOL][VPL * 256];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    typedef LnRing<VPL, DY_F32, RESID> Ring;
+    constexpr int NSLOT = Ring::NSLOT;
+    constexpr int RED_BYTES = 4 * NCOL * VPL * 256 * 4;
+    // ONE LDS array: the row ring during the loop, the cross-wave fold of the column sums after it
+    __shared__ __attribute__((aligned(16))) char smem[Ring::BYTES > RED_BYTES ? Ring::BYTES : RED_BYTES];
+    float(*red)[NCOL][VPL * 256] = (float(*)[NCOL][VPL * 256]) smem;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nv = d >> 2;
     f32x4 aw[VPL], ab[VPL], ww[VPL], ag[VPL], az[VPL], gg[VPL];
 #pragma unroll
@@ -135,40 +187,79 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
             drop_row0 = ra.seg;
         }
     }
-    // Everything a row needs from HBM (dy, x, the incoming residual gradient, mean/rstd) is fetched one row
-    // AHEAD of the arithmetic: beside the weight-gradient GEMMs of the side stream this kernel gets one or two
-    // waves per SIMD, so its speed is (bytes in flight per wave) / latency, not occupancy.
+    // Everything a row needs from HBM (dy, x, the incoming residual gradient, mean/rstd) is fetched AHEAD of the
+    // arithmetic: beside the weight-gradient GEMMs of the side stream this kernel gets one or two waves per SIMD, so
+    // its speed is (bytes in flight per wave) / latency, not occupancy.  The rows in flight wait in the wave's own ring
+    // of NSLOT slots in LDS (LnRing): while row k is worked on, rows k + 1 .. k + NSLOT of the wave (4 apart in the
+    // matrix) are on their way.  No barrier in the loop: a slot is written and read by one wave only.
     struct Row {
         f32x4 dy[VPL], x[VPL], dr[VPL];
         bf16x4 z[VPL];
         float mu, rs, scale;
     };
-    auto fetch = [&](int m, Row& r) {
+    char* const ring = smem + wave * (NSLOT * Ring::SLOT);
+    // LDS-DMA instructions of one row's fetch
+    const int nfetch = (DY_F32 ? VPL : (VPL + 1) / 2) + VPL + (dres ? VPL : 0) + (RESID ? (VPL + 1) / 2 : 0);
+    float mu_s[NSLOT], rs_s[NSLOT], sc_s[NSLOT];
+    auto fetch = [&](int m, int s) {
         const int sm = rowmap ? rowmap[m] : m;
-        r.mu = mean[m];
-        r.rs = rstd[m];
-        if constexpr (RESID) r.scale = ra.row_scale ? ra.row_scale[ra.row_index ? ra.row_index[m] : m] : 1.f;
-#pragma unroll
-        for (int j = 0; j < VPL; ++j) {
-            const int i = lane + 64 * j;
-            if (i < nv) {
-                if constexpr (DY_F32) {
-                    r.dy[j] = ((const f32x4*)((const float*)dy + (size_t)sm * d))[i];
-                } else {
-                    const bf16x4 t = ((const bf16x4*)((const bf16*)dy + (size_t)sm * d))[i];
-                    r.dy[j] = f32x4{(float)t[0], (float)t[1], (float)t[2], (float)t[3]};
-                }
-                r.x[j] = ((const f32x4*)(x + (size_t)m * d))[i];
-                r.dr[j] = dres ? ((const f32x4*)(dres + (size_t)m * d))[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-                if constexpr (RESID) r.z[j] = ((const bf16x4*)(ra.zd + (size_t)m * d))[i];
+        mu_s[s] = mean[m];
+        rs_s[s] = rstd[m];
+        sc_s[s] = 1.f;
+        if constexpr (RESID) {
+            if (ra.row_scale) {
+                const int ri = ra.row_index ? (int)scalar_load32(ra.row_index + m) : m;
+                sc_s[s] = __builtin_bit_cast(float, scalar_load32(ra.row_scale + ri));
             }
         }
+        char* slot = ring + s * Ring::SLOT;
+        if constexpr (DY_F32)
+            ring_piece<VPL>((const char*)dy + (size_t)sm * d * 4, 4 * d, slot + Ring::DY, lane);
+        else
+            ring_piece<(VPL + 1) / 2>((const char*)dy + (size_t)sm * d * 2, 2 * d, slot + Ring::DY, lane);
+        ring_piece<VPL>((const char*)(x + (size_t)m * d), 4 * d, slot + Ring::X, lane);
+        if (dres) ring_piece<VPL>((const char*)(dres + (size_t)m * d), 4 * d, slot + Ring::DR, lane);
+        if constexpr (RESID) ring_piece<(VPL + 1) / 2>((const char*)(ra.zd + (size_t)m * d), 2 * d, slot + Ring::Z, lane);
     };
-    Row cur, nxt;
-    int m = r0 + wave;
-    if (m < r1) fetch(m, cur);
-    for (; m < r1; m += 4) {
-        if (m + 4 < r1) fetch(m + 4, nxt);
+    const int m0 = r0 + wave;
+    const int nrow = m0 < r1 ? (r1 - m0 + 3) >> 2 : 0;      // rows of this wave: m0 + 4 k
+#pragma unroll
+    for (int s = 0; s < NSLOT; ++s)
+        if (s < nrow) fetch(m0 + 4 * s, s);
+    for (int k0 = 0; k0 < nrow; k0 += NSLOT)
+#pragma unroll
+    for (int s = 0; s < NSLOT; ++s) {
+        const int kr = k0 + s, m = m0 + 4 * kr;      // row kr of the wave
+        if (kr >= nrow) break;
+        // Wait for row kr's slot only.  The vector-memory operations issued AFTER its fetch, all of which may stay in
+        // flight: the fetches of rows kr + 1 .. kr + NSLOT - 1 (those that exist) and the stores of the min(kr, NSLOT)
+        // rows before kr (a row's fetch is issued ahead of the arithmetic of the row NSLOT before it).
+        // (gfx9: loads, LDS-DMA and stores share vmcnt and retire in issue order.)
+        int younger = min(kr, NSLOT) * Ring::STORES;
+#pragma unroll
+        for (int t = 1; t < NSLOT; ++t)
+            if (kr + t < nrow) younger += nfetch;
+        wait_vmcnt(younger);
+        Row cur;
+        cur.mu = mu_s[s], cur.rs = rs_s[s], cur.scale = sc_s[s];
+        {
+            const char* slot = ring + s * Ring::SLOT;
+#pragma unroll
+            for (int j = 0; j < VPL; ++j) {      // lanes without a column read padding and never use it
+                if constexpr (DY_F32) {
+                    cur.dy[j] = *(const f32x4*)(slot + Ring::DY + j * 1024 + lane * 16);
+                } else {
+                    const bf16x4 t = *(const bf16x4*)(slot + Ring::DY + j * 512 + lane * 8);
+                    cur.dy[j] = f32x4{(float)t[0], (float)t[1], (float)t[2], (float)t[3]};
+                }
+                cur.x[j] = *(const f32x4*)(slot + Ring::X + j * 1024 + lane * 16);
+                cur.dr[j] = dres ? *(const f32x4*)(slot + Ring::DR + j * 1024 + lane * 16) : f32x4{0.f, 0.f, 0.f, 0.f};
+                if constexpr (RESID) cur.z[j] = *(const bf16x4*)(slot + Ring::Z + j * 512 + lane * 8);
+            }
+        }
+        // the slot is free once its reads have returned
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (kr + NSLOT < nrow) fetch(m + 4 * NSLOT, s);
         const float mu = cur.mu, rs = cur.rs;
         f32x4 g[VPL], xh[VPL];
         float s1 = 0.f, s2 = 0.f;
@@ -219,8 +310,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
                 }
             }
         }
-        cur = nxt;
     }
+    __syncthreads();      // every slot has been read: the ring's bytes become red[][]
     // cross-wave reduction of the column sums, then one atomic per column per block
 #pragma unroll
     for (int j = 0; j < VPL; ++j)
@@ -284,7 +375,8 @@ int ln_bwd_launch(const void* dy, int dy_f32, const int32_t* rowmap, const float
                   const float* rstd, const float* dres, float* dx, float* dw, float* db, int M, int d, float* ws,
                   int64_t ws_bytes, ResidArgs* ra, float* dgamma, float* dbias, VlmoColJob* fold, hipStream_t stream) {
     VLMO_CHECK_ARG(dy && x && w && mean && rstd && dx, "vlmo_ln_bwd: null pointer");
-    VLMO_CHECK_ARG(M > 0 && d > 0 && d % 4 == 0 && d <= 1024, "vlmo_ln_bwd: need 0 < d <= 1024, d %% 4 == 0 (d=%d, M=%d)", d, M);
+    // d % 8: the bf16 pieces of a row (dy, zd) go to LDS in 16-byte units (LnRing)
+    VLMO_CHECK_ARG(M > 0 && d > 0 && d % 8 == 0 && d <= 1024, "vlmo_ln_bwd: need 0 < d <= 1024, d %% 8 == 0 (d=%d, M=%d)", d, M);
     const int ncol = ra ? 4 : 2;
     const bool need_w = dw || db || ra;
     VLMO_CHECK_ARG(!need_w || (ws && ws_bytes >= reduce_ws_need(ncol * d)),
