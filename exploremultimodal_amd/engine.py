@@ -12,6 +12,7 @@ The residual stream is fp32 (as under the reference's autocast), GEMM operands
 bf16 with fp32 accumulation, parameters fp32 masters with cached bf16 shadows.
 """
 import ctypes
+import functools
 import os as _os
 import sys
 from collections import namedtuple
@@ -106,6 +107,11 @@ class ShadowCache:
         self._c.clear()
 
 
+def _seg(a0, la, b0, lb, device):
+    """Segment descriptors {rowA, lenA, rowB, lenB} of a launch's sequences, int32 [sequences, 4] on `device`."""
+    return torch.stack([a0, la, b0, lb], 1).to(device=device, dtype=torch.int32).contiguous()
+
+
 class _PlanStatic:
     """Shape-only part of a plan (segment descriptors, row maps): built once per (B, T, P, device).
     Building it copies a few small host tensors to the device, which would stall the host every pass."""
@@ -124,14 +130,10 @@ class _PlanStatic:
         nt = B * T
         ar = torch.arange(B, dtype=torch.int32)
         z = torch.zeros(B, dtype=torch.int32)
-
-        def seg(a0, la, b0, lb):
-            return torch.stack([a0, la, b0, lb], 1).contiguous().to(device)
-
         tl, pl = torch.full((B,), T, dtype=torch.int32), torch.full((B,), P, dtype=torch.int32)
-        self.seg_txt = seg(ar * T, tl, z, z) if T else None
-        self.seg_img = seg(nt + ar * P, pl, z, z) if P else None
-        self.seg_vl = seg(ar * T, tl, nt + ar * P, pl) if (T and P) else None
+        self.seg_txt = _seg(ar * T, tl, z, z, device) if T else None
+        self.seg_img = _seg(nt + ar * P, pl, z, z, device) if P else None
+        self.seg_vl = _seg(ar * T, tl, nt + ar * P, pl, device) if (T and P) else None
         # below the fusion layer text and image sequences attend separately but in ONE launch (longest first:
         # the workgroups of the short text sequences fill the tail of the image ones)
         self.seg_sep = torch.cat([self.seg_img, self.seg_txt]).contiguous() if (T and P) else None
@@ -210,15 +212,11 @@ class _PlanRagged:
         ar = torch.arange(B, dtype=i32, device=dev)
         z = torch.zeros(B, dtype=i32, device=dev)
         row0, ln = off[:-1], off[1:] - off[:-1]
-
-        def seg(a0, la, b0, lb):
-            return torch.stack([a0, la, b0, lb], 1).to(i32).contiguous()
-
         pl = torch.full((B,), P, dtype=i32, device=dev)
         img0 = nt + ar * P
-        self.seg_txt = seg(row0, ln, z, z)
-        self.seg_img = seg(img0, pl, z, z) if P else None
-        self.seg_vl = seg(row0, ln, img0, pl) if P else None
+        self.seg_txt = _seg(row0, ln, z, z, dev)
+        self.seg_img = _seg(img0, pl, z, z, dev) if P else None
+        self.seg_vl = _seg(row0, ln, img0, pl, dev) if P else None
         self.seg_sep = torch.cat([self.seg_img, self.seg_txt]).contiguous() if P else None
         # sample and in-sequence position of every packed text row
         rb = torch.repeat_interleave(torch.arange(B, device=dev), ln.long(), output_size=nt)
@@ -246,32 +244,22 @@ class Plan:
         if txt_lens is not None:
             assert T > 0
             st = _PlanRagged.get(B, T, P, device, txt_lens, txt_off)
-            self.nt, self.ni, self.maxT = st.nt, B * P, st.maxT
-            self.M = self.nt + self.ni
-            self.seg_txt, self.seg_img, self.seg_vl, self.seg_sep = st.seg_txt, st.seg_img, st.seg_vl, st.seg_sep
-            self.rowmap, self.row_group = st.rowmap, st.row_group
-            self.txt_src, self.txt_off = st.src, st.off
-            parts = [txt_mask.reshape(-1).to(torch.int32)[st.src.long()] if txt_mask is not None
-                     else torch.ones(self.nt, dtype=torch.int32, device=device)]
-            if P:
-                parts.append(img_mask.reshape(-1).to(torch.int32) if img_mask is not None
-                             else torch.ones(self.ni, dtype=torch.int32, device=device))
-            self.keymask = torch.cat(parts).contiguous() if (txt_mask is not None or img_mask is not None) else None
-            return
-        self.nt, self.ni, self.maxT = B * T, B * P, T
+            self.nt, self.maxT, self.txt_src, self.txt_off = st.nt, st.maxT, st.src, st.off
+        else:
+            st = _PlanStatic.get(B, T, P, device)
+            self.nt, self.maxT = B * T, T
+        self.ni = B * P
         self.M = self.nt + self.ni
-        st = _PlanStatic.get(B, T, P, device)
         self.seg_txt, self.seg_img, self.seg_vl, self.seg_sep = st.seg_txt, st.seg_img, st.seg_vl, st.seg_sep
         self.rowmap, self.row_group = st.rowmap, st.row_group
-        # key-padding mask over packed rows (vlmo.py:89-91); None = all valid
-        parts = []
-        if T:
-            parts.append(txt_mask.reshape(-1).to(torch.int32) if txt_mask is not None
-                         else torch.ones(self.nt, dtype=torch.int32, device=device))
-        if P:
-            parts.append(img_mask.reshape(-1).to(torch.int32) if img_mask is not None
-                         else torch.ones(self.ni, dtype=torch.int32, device=device))
-        self.keymask = torch.cat(parts).contiguous() if (txt_mask is not None or img_mask is not None) else None
+        # key-padding mask over packed rows (vlmo.py:89-91); None = all valid.  A missing mask counts as all ones (an
+        # empty one when the pass has no such rows); with text lengths the text part keeps the packed positions only
+        # (st.src: packed text row -> element of the [B, T] mask).
+        self.keymask = None
+        if txt_mask is not None or img_mask is not None:
+            txt, img = (m.reshape(-1).to(torch.int32) if n and m is not None else torch.ones(n, dtype=torch.int32, device=device)
+                        for n, m in ((B * T, txt_mask), (self.ni, img_mask)))
+            self.keymask = torch.cat([txt if txt_lens is None else txt[st.src.long()], img]).contiguous()
 
     def attn_launches(self, fused):
         # the maximum a launch reports picks its attention kernel: with text lengths it is the batch's true maximum
@@ -397,17 +385,109 @@ def block_groups(bp):
     return [Group(tuple(bp[lo:hi]), lo, hi) for lo, hi in zip(cuts, cuts[1:])]
 
 
+# ---- the buffers behind a VlmoBlockDesc's pointers ----------------------------------------------------------------
+# Each layout is declared HERE and nowhere else; sizes, pointers and views are derived (_layouts).  Widths are named:
+# 'd', '3d', 'hid' (the FFN width, BlockMeta.hidden) and '1'.
+# Row tables, (descriptor field, columns): a buffer of M rows holds field after field, each an [M, columns] matrix.
+#   the saved activations of one block, bf16 ...
+SLAB_BF16 = (('y1', 'd'), ('qkv', '3d'), ('ctx', 'd'), ('zd1', 'd'), ('y2', 'd'), ('u', 'hid'), ('h', 'hid'), ('zd2', 'd'))
+#   ... and fp32, followed by the log-sum-exp rows of the block's attention launches (_lse_layout)
+SLAB_F32 = (('x1', 'd'), ('mean1', '1'), ('rstd1', '1'), ('mean2', '1'), ('rstd2', '1'))
+#   one set of the rotating backward temporaries, bf16; '=f': the field shares the matrix of field f (_run_captures
+#   says why dctx may live in dy2)
+TEMPS_BF16 = (('dz2', 'd'), ('du', 'hid'), ('dy2', 'd'), ('dctx', '=dy2'), ('dz1', 'd'), ('dqkv', '3d'), ('dy1', 'd'))
+# Bucket tables, (descriptor field, shape, parameter): the flat fp32 gradient bucket of a parameter group holds tensor
+# after tensor; parameter = index in the group (per-block order) of the parameter whose gradient the tensor is.  A
+# field of None continues the buffer of the field before it: dqkv_b is [3d] = q_bias | k (constant zero: no parameter)
+# | v_bias.
+SHARED_GRADS = (('dg1', ('d',), 0), ('dg2', ('d',), 1), ('dn1w', ('d',), 2), ('dn1b', ('d',), 3), ('dn2w', ('d',), 9),
+                ('dn2b', ('d',), 10), ('dqkv_w', ('3d', 'd'), QKV_W), ('dproj_w', ('d', 'd'), PROJ_W), ('dproj_b', ('d',), 8),
+                ('dqkv_b', ('d',), 5), (None, ('d',), None), (None, ('d',), 6))
+EXPERT_GRADS = (('dw1', ('hid', 'd'), FC1_W), ('db1', ('hid',), 1), ('dw2', ('d', 'hid'), FC2_W), ('db2', ('d',), 3))
+
+
+class _Rows:
+    """A row table at one (d, hid): at = {field: (first column, columns)}, cols = the columns of a whole row.  In a
+    buffer of M rows the field is the [M, columns] matrix that starts at element M * first column."""
+
+    def __init__(self, table, width):
+        self.at, self.cols = {}, 0
+        for name, w in table:
+            self.at[name] = self.at[w[1:]] if w[0] == '=' else (self.cols, width[w])
+            self.cols = max(self.cols, sum(self.at[name]))      # a shared matrix ends inside the row: no new columns
+
+    def wire(self, D, base, M, itemsize):
+        """The descriptor pointers of a buffer of M rows at address `base`."""
+        for name, (c0, _) in self.at.items():
+            setattr(D, name, base + c0 * M * itemsize)
+
+    def view(self, buf, i, M, name):
+        """Field `name` of the i-th M-row buffer of the flat tensor `buf` (buffer after buffer), as [M, columns]."""
+        c0, n = self.at[name]
+        return buf[(i * self.cols + c0) * M:(i * self.cols + c0 + n) * M].view(M, n)
+
+
+class _Bucket:
+    """A bucket table at one (d, hid): entries = ((field, shape, offset, numel, parameter), ...), numel of the whole
+    bucket, and vectors = ((lo, hi), ...), the maximal runs of 1-D tensors (the column folds ACCUMULATE into those)."""
+
+    def __init__(self, table, width):
+        ent, vec, off = [], [], 0
+        for field, shape, par in table:
+            shape = tuple(width[w] for w in shape)
+            n = shape[0] * (shape[1] if len(shape) > 1 else 1)
+            ent.append((field, shape, off, n, par))
+            if len(shape) == 1:
+                lo = vec.pop()[0] if vec and vec[-1][1] == off else off     # extends the run that ends here
+                vec.append((lo, off + n))
+            off += n
+        self.entries, self.vectors, self.numel = tuple(ent), tuple(vec), off
+
+
+_Layouts = namedtuple('_Layouts', 'slab f32 temps buckets')
+
+
+@functools.lru_cache(maxsize=None)
+def _layouts(d, hid):
+    """The tables above as plain integers, resolved once per (d, hid); buckets[is_expert] = the group kind's bucket."""
+    width = {'1': 1, 'd': d, '3d': 3 * d, 'hid': hid}
+    return _Layouts(_Rows(SLAB_BF16, width), _Rows(SLAB_F32, width), _Rows(TEMPS_BF16, width),
+                    (_Bucket(SHARED_GRADS, width), _Bucket(EXPERT_GRADS, width)))
+
+
+def _lse_layout(launches, heads):
+    """[(row stride, elements)] of the fp32 log-sum-exp buffers of a block's attention launches (Plan.attn_launches): one
+    row of ceil32(longest sequence) per (sequence, head)."""
+    strides = [((ml + 31) // 32) * 32 for _, _, ml in launches]
+    return [(s, nseq * heads * s) for s, (_, nseq, _) in zip(strides, launches)]
+
+
 def group_numel(g, d, hid):
     """Elements of the group's flat gradient bucket (what _fill_grads carves; the shared one includes the k-bias hole)."""
-    return 2 * hid * d + hid + d if g.lo else 6 * d + 3 * d * d + d * d + d + 3 * d
+    return _layouts(d, hid).buckets[g.lo > 0].numel
 
 
 def group_layout(g, d, hid):
-    """[(parameter, offset)] of the group inside its flat gradient bucket."""
-    return expert_layout(g.params, d, hid) if g.lo else shared_layout(g.params, d)
+    """[(parameter, offset)] of the group inside its flat gradient bucket, in bucket order."""
+    return [(g.params[par], off) for _, _, off, _, par in _layouts(d, hid).buckets[g.lo > 0].entries if par is not None]
 
 
-def _fill_forward(D, meta, groups, launches, lse_sizes, M, pb, pf, need_bwd, keep):
+def _wire_slabs(D, pb, pf, M, d, hid, heads, launches):
+    """Saved-activation pointers and attention launches of a VlmoBlockDesc: the bf16 slab at address pb, the fp32 slab
+    at pf with the launches' log-sum-exp buffers behind its rows."""
+    L = _layouts(d, hid)
+    L.slab.wire(D, pb, M, 2)
+    L.f32.wire(D, pf, M, 4)
+    off = pf + L.f32.cols * M * 4
+    D.n_attn = len(launches)
+    for i, ((seg, nseq, ml), (stride, n)) in enumerate(zip(launches, _lse_layout(launches, heads))):
+        D.seg[i], D.nseq[i], D.maxlen[i] = seg.data_ptr(), nseq, ml
+        D.lse_stride[i], D.lse[i] = stride, off
+        D.attn_seed_idx[i], D.attn_seq0[i] = i, 0
+        off += n * 4
+
+
+def _fill_forward(D, meta, groups, launches, M, pb, pf, need_bwd, keep):
     """Forward part of a VlmoBlockDesc: geometry, parameters (fp32 vectors, bf16 weight shadows) and the saved-
     activation slabs at pb (bf16) / pf (fp32).  groups: block_groups() of the block's parameters; x / x2 are set by
     the caller."""
@@ -420,20 +500,7 @@ def _fill_forward(D, meta, groups, launches, lse_sizes, M, pb, pf, need_bwd, kee
     D.n_experts = nexp
     for i, (r0, n) in enumerate(meta.expert_ranges):
         D.exp_row0[i], D.exp_rows[i] = r0, n
-    D.n_attn = len(launches)
-    md2 = M * d * 2
-    D.y1, D.qkv, D.ctx, D.zd1, D.y2 = pb, pb + md2, pb + 4 * md2, pb + 5 * md2, pb + 6 * md2
-    D.u, D.h, D.zd2 = pb + 7 * md2, pb + 11 * md2, pb + 15 * md2
-    D.x1 = pf
-    st = pf + M * d * 4
-    D.mean1, D.rstd1, D.mean2, D.rstd2 = st, st + 4 * M, st + 8 * M, st + 12 * M
-    off = st + 16 * M
-    for i, ((seg, nseq, ml), sz) in enumerate(zip(launches, lse_sizes)):
-        D.seg[i], D.nseq[i], D.maxlen[i] = seg.data_ptr(), nseq, ml
-        D.lse_stride[i] = ((ml + 31) // 32) * 32
-        D.lse[i] = off
-        D.attn_seed_idx[i], D.attn_seq0[i] = i, 0
-        off += sz * 4
+    _wire_slabs(D, pb, pf, M, d, hid, H, launches)
     D.keymask = hip._p(pl.keymask)
     D.eps = meta.eps
     D.drop_thresh, D.inv_keep = meta.drop
@@ -444,13 +511,9 @@ def _fill_forward(D, meta, groups, launches, lse_sizes, M, pb, pf, need_bwd, kee
     D.tile, D.need_bwd = meta.tile, int(need_bwd)
     D.g1, D.g2, D.n1w, D.n1b, D.n2w, D.n2b = (t.data_ptr() for t in (g1, g2, n1w, n1b, n2w, n2b))
     D.qkv_bias, D.proj_b = qkv_bias.data_ptr(), proj_b.data_ptr()
-    keep.append(qkv_bias)
-    w, wt = sh.get(qkv_w)
-    D.qkv_w, D.qkv_wT = w.data_ptr(), wt.data_ptr()
-    keep += [w, wt]
-    w, wt = sh.get(proj_w)
-    D.proj_w, D.proj_wT = w.data_ptr(), wt.data_ptr()
-    keep += [w, wt]
+    (a, at), (c, ct) = sh.get(qkv_w), sh.get(proj_w)
+    D.qkv_w, D.qkv_wT, D.proj_w, D.proj_wT = a.data_ptr(), at.data_ptr(), c.data_ptr(), ct.data_ptr()
+    keep += [qkv_bias, a, at, c, ct]
     for i, g in enumerate(groups[1:]):
         w1, b1, w2, b2 = g.params
         a, at = sh.get(w1)
@@ -486,50 +549,22 @@ def _split_backward_attention(D, meta):
     D.lse[1] = D.lse[0] + pl.B * meta.heads * stride * 4
 
 
-def _carve(flat, shapes):
-    out, off = [], 0
-    for shp in shapes:
-        n = 1
-        for s_ in shp:
-            n *= s_
-        out.append(flat[off:off + n].view(*shp))
-        off += n
-    return out
-
-
-def shared_layout(params, d):
-    """[(parameter, offset)] of a block's shared-parameter group inside its flat gradient bucket (the carve order of
-    _fill_grads; params in per-block order).  q_bias / v_bias sit at the two ends of the 3d-wide qkv-bias slot."""
-    (g1, g2, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b) = params[:N_SHARED]
-    o = 6 * d
-    out = [(g1, 0), (g2, d), (n1w, 2 * d), (n1b, 3 * d), (n2w, 4 * d), (n2b, 5 * d), (qkv_w, o)]
-    o += 3 * d * d
-    out.append((proj_w, o))
-    o += d * d
-    out.append((proj_b, o))
-    o += d
-    out += [(q_bias, o), (v_bias, o + 2 * d)]
-    return out
-
-
-def expert_layout(params, d, hid):
-    w1, b1, w2, b2 = params
-    return [(w1, 0), (b1, hid * d), (w2, hid * d + hid), (b2, 2 * hid * d + hid)]
-
-
 def _fill_grads(D, flats, d, hid, nexp):
     """Parameter-gradient pointers of a VlmoBlockDesc from flat fp32 storage (flats[0]: shared parameters,
     flats[1 + e]: expert e) -> gradient tensors in per-block parameter order."""
-    (dg1, dg2, dn1w, dn1b, dn2w, dn2b, dqkv_w, dproj_w, dproj_b, dqkv_b) = _carve(
-        flats[0], [(d,)] * 6 + [(3 * d, d), (d, d), (d,), (3 * d,)])
-    D.dg1, D.dg2, D.dn1w, D.dn1b, D.dn2w, D.dn2b = (t.data_ptr() for t in (dg1, dg2, dn1w, dn1b, dn2w, dn2b))
-    D.dqkv_w, D.dproj_w, D.dproj_b, D.dqkv_b = (t.data_ptr() for t in (dqkv_w, dproj_w, dproj_b, dqkv_b))
-    dexp = []
-    for i in range(nexp):
-        dw1, db1, dw2, db2 = _carve(flats[1 + i], [(hid, d), (hid,), (d, hid), (d,)])
-        D.dw1[i], D.db1[i], D.dw2[i], D.db2[i] = dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr()
-        dexp += [dw1, db1, dw2, db2]
-    return [dg1, dg2, dn1w, dn1b, dqkv_w, dqkv_b[:d], dqkv_b[2 * d:], dproj_w, dproj_b, dn2w, dn2b] + dexp
+    buckets = _layouts(d, hid).buckets
+    grads = [None] * (N_SHARED + N_EXPERT * nexp)
+    for gi, flat in enumerate(flats[:1 + nexp]):
+        p0 = flat.data_ptr()
+        first = N_SHARED + N_EXPERT * (gi - 1) if gi else 0         # the group's first parameter in per-block order
+        for field, shape, off, n, par in buckets[gi > 0].entries:
+            if field is not None and gi:
+                getattr(D, field)[gi - 1] = p0 + off * 4
+            elif field is not None:
+                setattr(D, field, p0 + off * 4)
+            if par is not None:
+                grads[first + par] = flat[off:off + n].view(shape)
+    return grads
 
 
 def _released(ctx_field):
@@ -753,18 +788,16 @@ _Scratch = namedtuple('_Scratch', 'nsets batch tb ws ws_n dxs')
 
 def _backward_scratch(dev, nb, M, d, hid, B):
     """Scratch sizing: how many sets of backward temporaries rotate (nsets) and how many blocks share one deferred
-    weight-gradient launch (batch), and the three persistent buffers: tb, the bf16 temporaries
-    (dz2 | du(4) | dy2=dctx | dz1 | dqkv(3) | dy1), one set per block in flight; ws, per set the column workspace of a
-    block with up to 2 B attention sequences (ws_n fp32 each, laid out by vlmo_stack_bwd_ws_bytes); dxs, the dx
-    ping-pong and dx1."""
+    weight-gradient launch (batch), and the three persistent buffers: tb, the bf16 temporaries (TEMPS_BF16), one set
+    per block in flight; ws, per set the column workspace of a block with up to 2 B attention sequences (ws_n fp32
+    each, laid out by vlmo_stack_bwd_ws_bytes); dxs, the dx ping-pong and dx1."""
     want = wgrad_batch_for(d, hid)
     nsets = max(1, min(max(TMP_SETS, want + 1), nb))
     batch = max(1, min(want, nsets - 1)) if nb > nsets else max(1, want)
-    md = M * d
-    tb = _persist(dev, 'tb', nsets * 11 * md, torch.bfloat16)
+    tb = _persist(dev, 'tb', nsets * _layouts(d, hid).temps.cols * M, torch.bfloat16)
     ws_n = hip.lib().vlmo_stack_bwd_ws_bytes(M, d, hid, 2 * B) // 4
     ws = _persist(dev, 'ws', nsets * ws_n, torch.float32)
-    dxs = _persist(dev, 'dx', 3 * md, torch.float32)
+    dxs = _persist(dev, 'dx', 3 * M * d, torch.float32)
     return _Scratch(nsets, batch, tb, ws, ws_n, dxs)
 
 
@@ -831,15 +864,12 @@ def _fresh_storage(numel, dev):
     return storage
 
 
-def _wire_temporaries(D, k, nb, md, sc, dxo, dx_in):
+def _wire_temporaries(D, k, nb, M, d, hid, sc, dxo, dx_in):
     """Temporaries of the k-th block the backward processes: its set of the rotating bf16 temporaries and workspaces,
     and the dx chain (dx2 = incoming: dxo for the first, else the previous block's dx0; dx0 = outgoing: dx_in for the
     last, else the other half of the ping-pong)."""
-    st_ = k % sc.nsets
-    pb = sc.tb.data_ptr() + st_ * 11 * md * 2
-    md2 = md * 2
-    D.dz2, D.du, D.dy2, D.dz1, D.dqkv, D.dy1 = pb, pb + md2, pb + 5 * md2, pb + 6 * md2, pb + 7 * md2, pb + 10 * md2
-    D.dctx = D.dy2
+    st_, md, T = k % sc.nsets, M * d, _layouts(d, hid).temps
+    T.wire(D, sc.tb.data_ptr() + st_ * T.cols * M * 2, M, 2)
     D.ws_main, D.ws_bytes = sc.ws.data_ptr() + st_ * sc.ws_n * 4, sc.ws_n * 4
     D.dx1 = sc.dxs.data_ptr() + 2 * md * 4
     D.dx2 = dxo.data_ptr() if k == 0 else sc.dxs.data_ptr() + ((k - 1) % 2) * md * 4
@@ -849,13 +879,11 @@ def _wire_temporaries(D, k, nb, md, sc, dxo, dx_in):
 def _zero_buckets(acquired, store_ok, d, hid):
     """Zeroing.  acquired: (flat, fresh, is_expert) of every bucket of the pass.  In store mode (every bucket fresh) the
     deferred launches WRITE the weight-gradient matrices, so only the vector gradients (accumulated with atomics by the
-    column folds) are zeroed, in one multi-tensor fill: [g1 g2 n1w n1b n2w n2b | qkv_w proj_w | proj_b qkv_b] and
-    [w1 | b1 | w2 | b2].  Otherwise the launches accumulate, and the fresh buckets are zeroed whole."""
+    column folds) are zeroed, in one multi-tensor fill: the vector runs of SHARED_GRADS / EXPERT_GRADS (two per
+    bucket).  Otherwise the launches accumulate, and the fresh buckets are zeroed whole."""
     if store_ok:
-        vecs = []
-        for f_, _, is_exp in acquired:
-            vecs += [f_[hid * d:hid * d + hid], f_[2 * hid * d + hid:]] if is_exp else [f_[:6 * d], f_[6 * d + 4 * d * d:]]
-        torch._foreach_zero_(vecs)
+        buckets = _layouts(d, hid).buckets
+        torch._foreach_zero_([f_[lo:hi] for f_, _, is_exp in acquired for lo, hi in buckets[is_exp].vectors])
     else:
         for f_, fr, _ in acquired:
             if fr:
@@ -878,14 +906,14 @@ def _hand_to_sink(sink, groups, spans, grads_all, evs):
         sink.release_all([g.params for g in groups[i]], ready_event=evs[i] if evs is not None else None)
 
 
-def _run_captures(metas, SB, sc, M, d):
+def _run_captures(metas, SB, sc, M, d, hid):
     """BlockMeta.capture of the blocks that asked for one, after vlmo_stack_bwd: views (no copy) of the block's saved qkv
     rows in the forward slab SB and of its dctx in the rotating temporaries.  Nothing in a block's backward writes
     dy2 = dctx after the attention backward has read it (block.hip: the fc2 backward writes dy2, the LayerNorm backward
     reads it, the proj backward overwrites it with dctx), so the set of the k-th processed block holds its dctx until
     block k + nsets takes the set: a captured block must be among the last nsets processed -- a one-block StackFn always
     is, which is how VLMO.attention_gradcam runs the layers it is asked for."""
-    nb, md = len(metas), M * d
+    nb, L = len(metas), _layouts(d, hid)
     for k in range(nb):
         i = nb - 1 - k
         if metas[i].capture is None:
@@ -893,9 +921,7 @@ def _run_captures(metas, SB, sc, M, d):
         if k + sc.nsets < nb:
             raise RuntimeError(f'the backward temporaries of block {i} of this {nb}-block stack were reused before its '
                                f'capture could run ({sc.nsets} sets rotate): run a captured block as a one-block StackFn')
-        qkv = SB[(i * 16 + 1) * md:(i * 16 + 4) * md].view(M, 3 * d)
-        st_ = k % sc.nsets
-        dctx = sc.tb[(st_ * 11 + 5) * md:(st_ * 11 + 6) * md].view(M, d)
+        qkv, dctx = L.slab.view(SB, i, M, 'qkv'), L.temps.view(sc.tb, k % sc.nsets, M, 'dctx')
         metas[i].capture(qkv, dctx, metas[i].plan, metas[i].fused)
 
 
@@ -912,23 +938,22 @@ class StackFn(torch.autograd.Function):
         M, dev = x.shape[0], x.device
         need_bwd = any(ctx.needs_input_grad)
         x = x.contiguous()
-        md = M * d
+        # every buffer of the layouts starts 128-byte aligned then (the GEMMs need K % 64 == 0 anyway)
+        assert d % 64 == 0 and hid % 64 == 0, (d, hid)
         spans, groups, pofs = [], [], 0     # per block: (offset, count) in params, and its parameter groups
         for mt in metas:
             npar = N_SHARED + N_EXPERT * len(mt.expert_ranges)
             spans.append((pofs, npar))
             groups.append(block_groups(params[pofs:pofs + npar]))
             pofs += npar
-        # per block: one bf16 slab  y1 | qkv(3) | ctx | zd1 | y2 | u(4) | h(4) | zd2  (units of M*d) and one fp32
-        # slab  x1 | mean1 rstd1 mean2 rstd2 | lse...  ; the blocks' outputs x2 (= the next block's saved input)
-        lse_sizes, launches = [], []
-        for mt in metas:
-            ln = pl.attn_launches(mt.fused)
-            launches.append(ln)
-            lse_sizes.append([nseq * H * (((ml + 31) // 32) * 32) for _, nseq, ml in ln])
-        sf_n = [md + 4 * M + sum(ls) for ls in lse_sizes]
+        # per block: one bf16 slab (SLAB_BF16) and one fp32 slab (SLAB_F32, then the log-sum-exp rows); the blocks'
+        # outputs x2 (= the next block's saved input)
+        L = _layouts(d, hid)
+        launches = [pl.attn_launches(mt.fused) for mt in metas]
+        sb_n = L.slab.cols * M
+        sf_n = [L.f32.cols * M + sum(n for _, n in _lse_layout(ln, H)) for ln in launches]
         live = nb if need_bwd else 1        # without a backward every block reuses the first block's slabs
-        SB = torch.empty(live * 16 * md, dtype=torch.bfloat16, device=dev)
+        SB = torch.empty(live * sb_n, dtype=torch.bfloat16, device=dev)
         SF = torch.empty(sum(sf_n[:live]) if need_bwd else max(sf_n), dtype=torch.float32, device=dev)
         X2 = torch.empty((nb if need_bwd else min(nb, 2), M, d), dtype=torch.float32, device=dev)
         descs = (hip.BlockDesc * nb)()
@@ -942,11 +967,11 @@ class StackFn(torch.autograd.Function):
         xin = x.data_ptr()
         for i, mt in enumerate(metas):
             D = descs[i]
-            pb = SB.data_ptr() + (i * 16 * md * 2 if need_bwd else 0)
+            pb = SB.data_ptr() + (i * sb_n * 2 if need_bwd else 0)
             pf = SF.data_ptr() + (sf_off * 4 if need_bwd else 0)
             sf_off += sf_n[i]
             x2 = X2[i if need_bwd else i % 2]
-            _fill_forward(D, mt, groups[i], launches[i], lse_sizes[i], M, pb, pf, need_bwd, keep)
+            _fill_forward(D, mt, groups[i], launches[i], M, pb, pf, need_bwd, keep)
             D.x, D.x2 = xin, x2.data_ptr()
             xin = x2.data_ptr()
         S = hip.StackDesc()
@@ -1004,7 +1029,7 @@ class StackFn(torch.autograd.Function):
                 if fr or sink is not None:  # groups accumulated in place hand nothing to autograd
                     grads_all[o + g.lo:o + g.hi] = grads[g.lo:g.hi]
             _split_backward_attention(D, metas[i])
-            _wire_temporaries(D, k, nb, M * d, sc, dxo, dx_in)
+            _wire_temporaries(D, k, nb, M, d, hid, sc, dxo, dx_in)
         _zero_buckets(acquired, store_ok, d, hid)
         S = hip.StackDesc()
         S.n_blocks, S.wgrad_batch, S.n_tmp_sets, S.wgrad_store = nb, sc.batch, sc.nsets, int(store_ok)
@@ -1018,7 +1043,7 @@ class StackFn(torch.autograd.Function):
             S.grad_ready = ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p))
         hip.stack_bwd(S)
         if any(mt.capture is not None for mt in metas):
-            _run_captures(metas, ctx.keep[0], sc, M, d)
+            _run_captures(metas, ctx.keep[0], sc, M, d, hid)
         ctx.descs = ctx.keep = None
         if sink is not None:
             _hand_to_sink(sink, groups, spans, grads_all, evs)

@@ -399,12 +399,15 @@ typedef struct VlmoBlockDesc {
     const void *qkv_w, *qkv_wT, *proj_w, *proj_wT;
     const float *b1[2], *b2[2];
     const void *w1[2], *w1T[2], *w2[2], *w2T[2];
-    /* forward activations (saved for backward) */
+    /* forward activations (saved for backward).  fp32 [M, d]: x (input), x1 (after the attention branch), x2 (output).
+     * bf16: y1, ctx, zd1, y2, zd2 [M, d]; qkv [M, 3 d]; u, h [M, hidden] (pre- / post-GELU).
+     * fp32: mean1, rstd1, mean2, rstd2 [M]; lse[a] [nseq[a] * heads, lse_stride[a]]. */
     const float* x;
     float *x1, *x2;
     void *y1, *qkv, *ctx, *zd1, *y2, *u, *h, *zd2;
     float *mean1, *rstd1, *mean2, *rstd2, *lse[2];
-    /* backward */
+    /* backward.  fp32 [M, d]: dx2 (incoming), dx1, dx0 (outgoing).
+     * bf16: dz2, dy2, dz1, dctx, dy1 [M, d]; du [M, hidden]; dqkv [M, 3 d].  dctx may be the buffer of dy2. */
     const float* dx2;
     float *dx1, *dx0;
     void *dz2, *du, *dy2, *dz1, *dctx, *dqkv, *dy1;

@@ -309,6 +309,8 @@ def main():
         'backbone_small': lambda: run_backbone_case('backbone_small', 'small', B=2),
         # the optional branches of the reference: no q/v bias (vlmo.py:57-62), no layer-scale (vlmo.py:185-192)
         'backbone_mini_plain': lambda: run_backbone_case('backbone_mini_plain', 'mini', B=3, qkv_bias=False, init_values=None),
+        # an FFN width other than 4 d (hidden = 768 at d = 128)
+        'backbone_mini_mlp6': lambda: run_backbone_case('backbone_mini_mlp6', 'mini', B=3, mlp_ratio=6),
         'backbone_debug': lambda: run_backbone_case('backbone_debug', 'debug', B=2),
         'backbone_base_b2': lambda: run_backbone_case('backbone_base_b2', 'base', B=2, full_out=False),
         # VLMo-Large (conf/model/vlmo_large.yaml:14-28: d=1024, L=24, h=16, F=12); the synthetic layer-scale stays

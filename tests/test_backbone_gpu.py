@@ -21,6 +21,7 @@ DEV = 'cuda'
 
 
 PLAIN = dict(qkv_bias=False, init_values=None)      # the reference's optional branches (vlmo.py:57-62, 185-192)
+MLP6 = dict(mlp_ratio=6)                            # an FFN width other than 4 d
 
 
 def build(preset, model_over=None, **over):
@@ -53,14 +54,18 @@ def modes(mc, batch, B):
 
 @pytest.mark.parametrize('name,preset', [('backbone_mini', 'mini'), ('backbone_small', 'small'),
                                          ('backbone_base_b2', 'base'), ('backbone_large_b2', 'large'),
-                                         ('backbone_mini_plain', 'mini')])
+                                         ('backbone_mini_plain', 'mini'), ('backbone_mini_mlp6', 'mini')])
 def test_forward_backward_matches_reference(golden_dir, name, preset):
-    """backbone_mini_plain: qkv_bias=False and init_values=None (no q/v bias, no layer-scale parameters)."""
+    """backbone_mini_plain: qkv_bias=False and init_values=None (no q/v bias, no layer-scale parameters).
+    backbone_mini_mlp6: mlp_ratio=6, an FFN of 768 columns at d = 128 -- the saved-activation slabs and the backward
+    temporaries are sized by the FFN width, not by 4 d."""
     g = np.load(os.path.join(golden_dir, name + '.npz'))
     B = int(g['meta.B'])
-    model, mc = build(preset, PLAIN if name.endswith('_plain') else None)
+    model, mc = build(preset, PLAIN if name.endswith('_plain') else MLP6 if name.endswith('_mlp6') else None)
     if name.endswith('_plain'):
         assert not any('gamma_' in k or 'q_bias' in k or 'v_bias' in k for k in model.state_dict())
+    if name.endswith('_mlp6'):
+        assert model.blocks[0].mlp_hidden_dim == 6 * mc.embed_dim == 768
     model.eval()
     batch = synth.synth_batch(mc, B, seed=1234)
     report = []
@@ -293,8 +298,8 @@ def test_stack_bwd_refuses_a_short_column_workspace(monkeypatch):
     slot = L.vlmo_reduce_ws_bytes(2 * mc.embed_dim)
     wire, seen = engine._wire_temporaries, {}
 
-    def short_wire(D, k, nb, md, sc, dxo, dx_in):
-        wire(D, k, nb, md, sc, dxo, dx_in)
+    def short_wire(D, k, nb, M, d, hid, sc, dxo, dx_in):
+        wire(D, k, nb, M, d, hid, sc, dxo, dx_in)
         nseq = sum(D.nseq[a] for a in range(D.n_attn))
         assert D.ws_bytes == L.vlmo_stack_bwd_ws_bytes(D.M, D.d, D.hidden, 2 * B)
         seen.setdefault('need', []).append(L.vlmo_stack_bwd_ws_bytes(D.M, D.d, D.hidden, nseq))

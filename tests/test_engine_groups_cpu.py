@@ -1,7 +1,6 @@
 """Host logic of engine.StackFn that needs no GPU: the split of a block's parameter list into its groups
-(engine.block_groups / group_numel / group_layout), which must agree with what engine._fill_grads carves and
-shared_layout / expert_layout advertise, and the choice of a group's gradient bucket on the local route
-(engine._local_bucket), one case per outcome."""
+(engine.block_groups / group_numel / group_layout), which must agree with what engine._fill_grads carves, and the
+choice of a group's gradient bucket on the local route (engine._local_bucket), one case per outcome."""
 import pytest
 import torch
 
@@ -47,9 +46,15 @@ def test_block_groups_agree_with_the_carved_gradients(nexp):
     assert sizes[0] == sum(p.numel() for p in shared) + D
     assert sizes[1:] == [sum(p.numel() for p in e) for e in experts]
     # layouts: the dispatch, and the offsets against the gradients _fill_grads carves out of buckets of these sizes
-    assert engine.group_layout(groups[0], D, HID) == engine.shared_layout(shared, D)
-    for g, e in zip(groups[1:], experts):
-        assert engine.group_layout(g, D, HID) == engine.expert_layout(e, D, HID)
+    g1, g2, n1w, n1b, qkv_w, q_bias, v_bias, proj_w, proj_b, n2w, n2b = shared
+    o = 6 * D + 4 * D * D
+    want = [(g1, 0), (g2, D), (n1w, 2 * D), (n1b, 3 * D), (n2w, 4 * D), (n2b, 5 * D), (qkv_w, 6 * D),
+            (proj_w, 6 * D + 3 * D * D), (proj_b, o), (q_bias, o + D), (v_bias, o + 3 * D)]
+    got = engine.group_layout(groups[0], D, HID)
+    assert [(id(p), off) for p, off in got] == [(id(p), off) for p, off in want]
+    for g, (w1, b1, w2, b2) in zip(groups[1:], experts):
+        want = [(w1, 0), (b1, HID * D), (w2, HID * D + HID), (b2, 2 * HID * D + HID)]
+        assert [(id(p), off) for p, off in engine.group_layout(g, D, HID)] == [(id(p), off) for p, off in want]
     flats = [torch.arange(n, dtype=torch.float32) + 10000 * gi for gi, n in enumerate(sizes)]
     grads = engine._fill_grads(_Desc(nexp), flats, D, HID, nexp)
     assert len(grads) == len(bp)
