@@ -29,11 +29,48 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import derived, hip
 
 logit_laplace_eps = 0.1
 # measurement switch: 0 = the output convolution as one launch whatever its last dispatch round looks like
 OUTPUT_ROW_SPLIT = os.environ.get('VLMO_DVAE_OUT_SPLIT', '1') != '0'
+
+
+def _need_cuda(device):
+    if device.type != 'cuda':
+        raise RuntimeError('exploremultimodal_amd runs on MI355X only: input must be on a cuda (ROCm) device')
+
+
+def _check_id_range(ids, vocab, name):
+    """Token ids before a table lookup: not empty and, like the reference's F.one_hot, inside [0, vocab) (one
+    device-to-host read)."""
+    if ids.numel() == 0:
+        raise ValueError(f'{name} is empty')
+    lo, hi = int(ids.min()), int(ids.max())
+    if lo < 0 or hi >= vocab:
+        raise ValueError(f'ids must lie in [0, {vocab}): got values in [{lo}, {hi}]')
+
+
+def _vocab_head(epi, feat, w, bias, N, parts, k1=0):
+    """The vocabulary convolution (a plain GEMM) of feat fp16 [M, C] over the row ranges ``parts`` [(r0, r1, tile)]:
+    EPI_F32 -> fp32 logits [M, N]; EPI_ARGMAX -> their arg-max per row, int64 [M], reduced from per-64-column partials
+    so the logits never reach HBM.  ``k1`` > 0: w = [w_hi | w_lo] (Conv2d.shadow_split) as a two-segment reduction whose
+    second segment reads the same activations (no doubled copy in HBM)."""
+    M, dev = feat.shape[0], feat.device
+    if epi == hip.EPI_ARGMAX:
+        nchunk = (N + 63) // 64
+        out, ldo = torch.empty((M, nchunk, 2), dtype=torch.float32, device=dev), nchunk
+    else:
+        out, ldo = torch.empty((M, N), dtype=torch.float32, device=dev), None
+    for r0, r1, tile in parts:
+        a = feat[r0:r1]
+        hip.gemm_nt(epi, a, w, r1 - r0, N, w.shape[1], out[r0:r1], bias=bias, ldo=ldo, tile=tile,
+                    A2=a if k1 else None, k1=k1)
+    if epi != hip.EPI_ARGMAX:
+        return out
+    ids = torch.empty((M,), dtype=torch.int64, device=dev)
+    hip.argmax_reduce(out, nchunk, ids, M)
+    return ids
 
 
 def map_pixels(x):
@@ -65,20 +102,19 @@ class Conv2d(nn.Module):
         b = torch.zeros((n_out,), dtype=torch.float32, device=device)
         self.w = nn.Parameter(w, requires_grad=requires_grad)
         self.b = nn.Parameter(b, requires_grad=requires_grad)
-        self._shadow = None
+
+    def _derived(self, slot, weight):
+        """(``weight()``, fp32 bias), one slot per layout, each rebuilt when ``w`` or ``b`` was written to or moved."""
+        return derived.of(self).get(slot, (self.w, self.b), lambda: (weight(), self.b.detach().float().contiguous()))
 
     def shadow_embed(self):
         """Decoder input layer (kw = 1, use_float16=False, dall_e/decoder.py:77-78) applied to a one-hot map: the fp32
         weight transposed to [n_in, n_out] = one row per token id, and the fp32 bias."""
-        ver = (self.w._version, self.w.data_ptr(), self.b._version, 'embed')
-        cached = self.__dict__.get('_embed')
-        if cached is None or cached[0] != ver:
+        def table():
             if self.kw != 1:
                 raise ValueError('shadow_embed: a 1x1 convolution only')
-            cached = (ver, self.w.detach().float().reshape(self.n_out, self.n_in).t().contiguous(),
-                      self.b.detach().float().contiguous())
-            self.__dict__['_embed'] = cached
-        return cached[1], cached[2]
+            return self.w.detach().float().reshape(self.n_out, self.n_in).t().contiguous()
+        return self._derived('embed', table)
 
     def shadow_split(self):
         """use_float16=False layers (the output conv, dall_e/encoder.py:116-119 + dall_e/utils.py:37-48: fp32 weights
@@ -86,19 +122,17 @@ class Conv2d(nn.Module):
         w_lo = fp16(w - w_hi) (~22 significant bits together), multiplied against the activations repeated twice
         along K.  The fp16 MFMA products are exact in the fp32 accumulator, so the arg-max-deciding logits see the
         reference's weight precision, not a 11-bit rounding of it."""
-        ver = (self.w._version, self.w.data_ptr(), 'split')
-        if self._shadow is None or self._shadow[0] != ver:
+        def split():
             w = self.w.detach().permute(0, 2, 3, 1).reshape(self.n_out, -1).float()
             hi = w.to(torch.float16)
             lo = (w - hi.float()).to(torch.float16)
-            self._shadow = (ver, torch.cat([hi, lo], 1).contiguous(), self.b.detach().float().contiguous())
-        return self._shadow[1], self._shadow[2]
+            return torch.cat([hi, lo], 1).contiguous()
+        return self._derived('split', split)
 
     def shadow(self):
         """fp16 weight in the engine's layout [n_out, kw*kw*n_in] (tap-major, channel-minor; the 3-channel
         stem keeps (c, ky, kx) order and is zero-padded to a multiple of 64 columns)."""
-        ver = (self.w._version, self.w.data_ptr())
-        if self._shadow is None or self._shadow[0] != ver:
+        def engine_layout():
             w = self.w.detach()
             if self.n_in % 64 == 0:
                 s = w.permute(0, 2, 3, 1).reshape(self.n_out, -1)
@@ -106,8 +140,8 @@ class Conv2d(nn.Module):
                 s = w.reshape(self.n_out, -1)
                 pad = (-s.shape[1]) % 64
                 s = torch.nn.functional.pad(s, (0, pad))
-            self._shadow = (ver, s.to(torch.float16).contiguous(), self.b.detach().float().contiguous())
-        return self._shadow[1], self._shadow[2]
+            return s.to(torch.float16).contiguous()
+        return self._derived('shadow', engine_layout)
 
 
 class EncoderBlock(nn.Module):
@@ -127,18 +161,17 @@ class EncoderBlock(nn.Module):
             ('relu_2', nn.ReLU()), ('conv_2', mk(self.n_hid, self.n_hid, 3)),
             ('relu_3', nn.ReLU()), ('conv_3', mk(self.n_hid, self.n_hid, 3)),
             ('relu_4', nn.ReLU()), ('conv_4', mk(self.n_hid, n_out, 1))]))
-        self._tail = None
 
     def tail_shadow(self):
         """Convolutional id_path: [conv_4.w | id_path.w] as ONE fp16 matrix [n_out, n_hid + n_in] and the combined bias
         post_gain * conv_4.b + id_path.b, for the block tail as a single two-segment GEMM (encoder.py:45-46)."""
         c4, idp = self.res_path.conv_4, self.id_path
-        ver = (c4.w._version, c4.w.data_ptr(), idp.w._version, idp.w.data_ptr(), c4.b._version, idp.b._version)
-        if getattr(self, '_tail', None) is None or self._tail[0] != ver:
+
+        def tail():
             w4, b4 = c4.shadow()
             wi, bi = idp.shadow()
-            self._tail = (ver, torch.cat([w4, wi], 1).contiguous(), (self.post_gain * b4 + bi).contiguous())
-        return self._tail[1], self._tail[2]
+            return torch.cat([w4, wi], 1).contiguous(), (self.post_gain * b4 + bi).contiguous()
+        return derived.of(self).get('tail', (c4.w, c4.b, idp.w, idp.b), tail)
 
 
 class Encoder(nn.Module):
@@ -180,8 +213,7 @@ class Encoder(nn.Module):
             raise ValueError(f'input has {x.shape[1]} channels but model built for {self.input_channels}')
         if x.dtype != torch.float32:
             raise ValueError('input must have dtype torch.float32')
-        if x.device.type != 'cuda':
-            raise RuntimeError('exploremultimodal_amd runs on MI355X only: input must be on a cuda (ROCm) device')
+        _need_cuda(x.device)
         if self.n_hid % 256 != 0:
             raise NotImplementedError('the implicit-GEMM kernels need n_hid to be a multiple of 256 '
                                       '(bottleneck width n_hid/4 must be a multiple of 64)')
@@ -249,31 +281,22 @@ class Encoder(nn.Module):
         r = (full * 256 // nt) * 256
         return [(0, r, 3), (r, M, 0)] if 0 < r < M else [(0, M, -1)]
 
-    def forward(self, x):
-        """encoder.py:123-133 -> logits fp32 [B, vocab, H/8, W/8]."""
-        rel, (B, h, w) = self._features(x)
+    def _head(self, epi, x):
+        """[x | x] against [w_hi | w_lo] of the output convolution, over its row parts."""
+        rel, dims = self._features(x)
         wo, bo = self.blocks.output.conv.shadow_split()
         M, C = rel.shape
-        logits = torch.empty((M, self.vocab_size), dtype=torch.float32, device=x.device)
-        # [x | x] against [w_hi | w_lo]: the activations are the second segment's source too (no doubled copy in HBM)
-        for r0, r1, tile in self._row_parts(M, self.vocab_size):
-            hip.gemm_nt(hip.EPI_F32, rel[r0:r1], wo, r1 - r0, self.vocab_size, 2 * C, logits[r0:r1], bias=bo,
-                        A2=rel[r0:r1], k1=C, tile=tile)
+        return _vocab_head(epi, rel, wo, bo, self.vocab_size, self._row_parts(M, self.vocab_size), k1=C), dims
+
+    def forward(self, x):
+        """encoder.py:123-133 -> logits fp32 [B, vocab, H/8, W/8]."""
+        logits, (B, h, w) = self._head(hip.EPI_F32, x)
         return logits.view(B, h, w, self.vocab_size).permute(0, 3, 1, 2)
 
     def codebook_indices(self, x):
         """argmax(forward(x), dim=1) without materialising the logits -> int64 [B, H/8, W/8]."""
-        rel, (B, h, w) = self._features(x)
-        M, C = rel.shape
-        nchunk = (self.vocab_size + 63) // 64
-        part = torch.empty((M, nchunk, 2), dtype=torch.float32, device=x.device)
-        wo, bo = self.blocks.output.conv.shadow_split()
-        for r0, r1, tile in self._row_parts(M, self.vocab_size):
-            hip.gemm_nt(hip.EPI_ARGMAX, rel[r0:r1], wo, r1 - r0, self.vocab_size, 2 * C, part[r0:r1], bias=bo,
-                        ldo=nchunk, A2=rel[r0:r1], k1=C, tile=tile)
-        ids = torch.empty((M,), dtype=torch.int64, device=x.device)
-        hip.argmax_reduce(part, nchunk, ids, M)
-        return ids.view(B, h, w)
+        ids, dims = self._head(hip.EPI_ARGMAX, x)
+        return ids.view(dims)
 
 
 class DecoderBlock(nn.Module):
@@ -336,8 +359,7 @@ class Decoder(nn.Module):
 
     # ------------------------------------------------------------------ engine
     def _check_engine(self, device):
-        if device.type != 'cuda':
-            raise RuntimeError('exploremultimodal_amd runs on MI355X only: input must be on a cuda (ROCm) device')
+        _need_cuda(device)
         if self.n_hid % 256 != 0:
             raise NotImplementedError('the implicit-GEMM kernels need n_hid to be a multiple of 256 '
                                       '(bottleneck width n_hid/4 must be a multiple of 64)')
@@ -399,11 +421,7 @@ class Decoder(nn.Module):
             raise ValueError('ids must have dtype torch.int64')
         self._check_engine(ids.device)
         B, h, w = ids.shape
-        if ids.numel() == 0:
-            raise ValueError('ids is empty')
-        lo, hi = int(ids.min()), int(ids.max())
-        if lo < 0 or hi >= self.vocab_size:
-            raise ValueError(f'ids must lie in [0, {self.vocab_size}): got values in [{lo}, {hi}]')
+        _check_id_range(ids, self.vocab_size, 'ids')
         table, bias = self.blocks.input.shadow_embed()
         raw = torch.empty((B * h * w, self.n_init), dtype=torch.float16, device=ids.device)
         hip.dvae_embed(ids.contiguous().view(-1), table, bias, raw)
@@ -455,11 +473,6 @@ def load_model(path, device=None):
     finally:
         for name in fake:
             sys.modules.pop(name, None)
-    # unpickling restores the reference objects' __dict__ without running this module's constructors: add the
-    # engine-side state they do not carry
-    for m in enc.modules():
-        if isinstance(m, Conv2d) and '_shadow' not in m.__dict__:
-            m._shadow = None
     return enc
 
 
@@ -537,23 +550,13 @@ def convT4s2_shadow(w, cin_pad=None):
     return s.reshape(4, cout, 4 * cp).contiguous()
 
 
-def _cached(mod, slot, params, build):
-    """A derived (shadow) tensor of ``mod``, rebuilt when one of ``params`` was written to or moved."""
-    ver = tuple((p._version, p.data_ptr()) for p in params)
-    hit = mod.__dict__.get(slot)
-    if hit is None or hit[0] != ver:
-        hit = (ver, build())
-        mod.__dict__[slot] = hit
-    return hit[1]
-
-
 def _conv_shadow(conv, build=None):
     """(fp16 engine-layout weight, fp32 bias) of an nn.Conv2d / nn.ConvTranspose2d; ``build`` makes the weight where
     it is not the tap-major one."""
     if build is None:
         build = lambda: tap_major_shadow(conv.weight)
-    return _cached(conv, '_vlmo_shadow', (conv.weight, conv.bias),
-                   lambda: (build(), conv.bias.detach().float().contiguous()))
+    return derived.of(conv).get('shadow', (conv.weight, conv.bias),
+                                lambda: (build(), conv.bias.detach().float().contiguous()))
 
 
 class ResBlock(nn.Module):
@@ -631,11 +634,6 @@ class DiscreteVAE(nn.Module):
         return self.image_size // 8
 
     # ------------------------------------------------------------------ engine
-    @staticmethod
-    def _need_cuda(t):
-        if t.device.type != 'cuda':
-            raise RuntimeError('exploremultimodal_amd runs on MI355X only: input must be on a cuda (ROCm) device')
-
     def _features(self, img):
         """-> the last ResBlock's output fp16 [B*h*w, hidden_dim], (B, h, w) with h = w = image_size / 2**num_layers."""
         if img.dim() != 4 or img.shape[1] != self.channels:
@@ -644,7 +642,7 @@ class DiscreteVAE(nn.Module):
             raise ValueError(f'input must have the correct image size {self.image_size}')
         if img.dtype != torch.float32:
             raise ValueError('input must have dtype torch.float32')
-        self._need_cuda(img)
+        _need_cuda(img.device)
         B, dev, hid = img.shape[0], img.device, self.hidden_dim
         h = w = self.image_size
         x = img.contiguous()
@@ -667,6 +665,12 @@ class DiscreteVAE(nn.Module):
             t = self.encoder[2 * li + 1].run(o, B, h, w)
         return t, (B, h, w)
 
+    def _head(self, epi, img):
+        """The vocabulary convolution (1x1, hidden_dim -> num_tokens) on the features, as one launch."""
+        feat, dims = self._features(img)
+        wl, bl = _conv_shadow(self.encoder[2 * self.num_layers])
+        return _vocab_head(epi, feat, wl, bl, self.num_tokens, [(0, feat.shape[0], -1)]), dims
+
     @torch.no_grad()
     def forward(self, img, return_loss=False, return_recons=False, return_logits=False, temp=None):
         """modeling_discrete_vae.py:171-184 with return_logits=True -> fp32 logits [B, num_tokens, h, w]."""
@@ -674,26 +678,15 @@ class DiscreteVAE(nn.Module):
             raise NotImplementedError('DiscreteVAE.forward without return_logits is the Gumbel-softmax training pass of the '
                                       'tokenizer itself (modeling_discrete_vae.py:186-221): this engine only tokenises '
                                       '(get_codebook_indices, forward(..., return_logits=True)) and decodes (decode)')
-        feat, (B, h, w) = self._features(img)
-        wl, bl = _conv_shadow(self.encoder[2 * self.num_layers])
-        M = feat.shape[0]
-        logits = torch.empty((M, self.num_tokens), dtype=torch.float32, device=img.device)
-        hip.gemm_nt(hip.EPI_F32, feat, wl, M, self.num_tokens, self.hidden_dim, logits, bias=bl)
+        logits, (B, h, w) = self._head(hip.EPI_F32, img)
         return logits.view(B, h, w, self.num_tokens).permute(0, 3, 1, 2)
 
     @torch.no_grad()
     def get_codebook_indices(self, images):
         """argmax(forward(images, return_logits=True), dim=1) -> int64 [B, h, w] with the arg-max fused into the
         vocabulary convolution: the [B, num_tokens, h, w] logits never exist."""
-        feat, (B, h, w) = self._features(images)
-        wl, bl = _conv_shadow(self.encoder[2 * self.num_layers])
-        M = feat.shape[0]
-        nchunk = self.num_tokens // 64
-        part = torch.empty((M, nchunk, 2), dtype=torch.float32, device=images.device)
-        hip.gemm_nt(hip.EPI_ARGMAX, feat, wl, M, self.num_tokens, self.hidden_dim, part, bias=bl, ldo=nchunk)
-        ids = torch.empty((M,), dtype=torch.int64, device=images.device)
-        hip.argmax_reduce(part, nchunk, ids, M)
-        return ids.view(B, h, w)
+        ids, dims = self._head(hip.EPI_ARGMAX, images)
+        return ids.view(dims)
 
     @torch.no_grad()
     def get_codebook_probs(self, images):
@@ -704,7 +697,7 @@ class DiscreteVAE(nn.Module):
         the zero bias of the lookup kernel."""
         cb = self.codebook.weight
         dp = -(-self.codebook_dim // 64) * 64
-        return _cached(self.codebook, '_vlmo_shadow', (cb,), lambda: (
+        return derived.of(self.codebook).get('table', (cb,), lambda: (
             nn.functional.pad(cb.detach().float(), (0, dp - self.codebook_dim)).contiguous(),
             torch.zeros(dp, dtype=torch.float32, device=cb.device)))
 
@@ -717,14 +710,12 @@ class DiscreteVAE(nn.Module):
             raise ValueError(f'img_seq shape {tuple(img_seq.shape)} is not [B, n]')
         if img_seq.dtype != torch.int64:
             raise ValueError('img_seq must have dtype torch.int64')
-        self._need_cuda(img_seq)
+        _need_cuda(img_seq.device)
         B, n = img_seq.shape
         h = w = math.isqrt(n)
         if n == 0 or h * w != n:
             raise ValueError(f'img_seq holds {n} ids per image, which is not a square grid')
-        lo, hi = int(img_seq.min()), int(img_seq.max())
-        if lo < 0 or hi >= self.num_tokens:
-            raise ValueError(f'ids must lie in [0, {self.num_tokens}): got values in [{lo}, {hi}]')
+        _check_id_range(img_seq, self.num_tokens, 'img_seq')
         dev, hid = img_seq.device, self.hidden_dim
         table, zbias = self._codebook_table()
         cin = table.shape[1]

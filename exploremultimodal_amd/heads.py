@@ -20,62 +20,40 @@ tensors.
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import derived, hip
 
 
 def _pad64(n):
     return (n + 63) // 64 * 64
 
 
-def lazy_attr(obj, name, factory):
-    """``obj.<name>``, made by ``factory()`` on first use; set past nn.Module.__setattr__ (a cache, not a submodule)."""
-    if not hasattr(obj, name):
-        object.__setattr__(obj, name, factory())
-    return getattr(obj, name)
+# former names of the per-head cache classes: code written against them gets the plain holder.  Construct derived.Holder().
+_PaddedShadows = _VQAShadows = derived.Holder
 
 
-class _Shadows:
-    """Copies derived from parameters by ``_build``, rebuilt when a parameter's (version counter, data pointer) changes
-    (once per optimizer step)."""
-
-    def __init__(self):
-        self.key, self.val = None, None
-
-    def _cached(self, *params):
-        key = tuple(None if t is None else (t._version, t.data_ptr()) for t in params)
-        if self.key != key:
-            self.key, self.val = key, self._build(*params)
-        return self.val
-
-
-class _PaddedShadows(_Shadows):
+def _pad_vocab_head(weight, bias):
     """bf16 copies of a vocabulary head's weight padded to a multiple of 64 rows (W [Vp, d], W^T [d, Vp]) and its fp32
     bias padded with -1e30 (so padded columns vanish from the soft-max)."""
-
-    def get(self, weight, bias):
-        return self._cached(weight, bias)
-
-    @staticmethod
-    def _build(weight, bias):
-        V, d = weight.shape
-        Vp = _pad64(V)
-        w = torch.zeros((Vp, d), dtype=torch.bfloat16, device=weight.device)
-        w[:V] = weight.detach()
-        wt = w.t().contiguous()
-        b = torch.full((Vp,), -1e30, dtype=torch.float32, device=weight.device)
-        b[:V] = bias.detach() if bias is not None else 0.0
-        return w, wt, b, Vp
+    V, d = weight.shape
+    Vp = _pad64(V)
+    w = torch.zeros((Vp, d), dtype=torch.bfloat16, device=weight.device)
+    w[:V] = weight.detach()
+    wt = w.t().contiguous()
+    b = torch.full((Vp,), -1e30, dtype=torch.float32, device=weight.device)
+    b[:V] = bias.detach() if bias is not None else 0.0
+    return w, wt, b, Vp
 
 
 class LinearCrossEntropyFn(torch.autograd.Function):
     """mean cross-entropy of ``x @ W^T + b`` against ``labels`` (rows with ``ignore_index`` excluded) and the
-    arg-max prediction per row, without materialising the logits (heads.py:86-112 + objectives.py:57-68,571-582)."""
+    arg-max prediction per row, without materialising the logits (heads.py:86-112 + objectives.py:57-68,571-582).
+    ``shadows``: the ``derived.Holder`` that keeps the padded bf16 copies (rebuilt once per optimizer step)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, labels, ignore_index, shadows):
         n, d = x.shape
         V = weight.shape[0]
-        w, wt, b, Vp = shadows.get(weight, bias)
+        w, wt, b, Vp = shadows.get('ce', (weight, bias), lambda: _pad_vocab_head(weight, bias))
         xb = x.detach().to(torch.bfloat16).contiguous()
         lab = labels.to(torch.int32).contiguous()
         nch = Vp // 64
@@ -117,29 +95,23 @@ class LinearCrossEntropyFn(torch.autograd.Function):
         return dx.to(xd), dw[:V].to(wd), (db.to(bd) if db is not None else None), None, None, None
 
 
-class _VQAShadows(_Shadows):
+def _pad_vqa_head(w1, w2, b2):
     """bf16 copies of the VQA classifier's two weight matrices, zero-padded for the GEMMs (reduction dimensions to a
     multiple of 64, the 3129 answers to 3136), each with its transpose, and the zero-padded fp32 output bias."""
-
-    def get(self, w1, w2, b2):
-        return self._cached(w1, w2, b2)
-
-    @staticmethod
-    def _build(w1, w2, b2):
-        h2, hs = w1.shape
-        vs = w2.shape[0]
-        k0, k1, npad = _pad64(hs), _pad64(h2), _pad64(vs)
-        dev = w1.device
-        w1s = torch.zeros((h2, k0), dtype=torch.bfloat16, device=dev)
-        w1s[:, :hs] = w1.detach()
-        w1t = torch.zeros((hs, k1), dtype=torch.bfloat16, device=dev)
-        w1t[:, :h2] = w1.detach().t()
-        w2s = torch.zeros((npad, k1), dtype=torch.bfloat16, device=dev)
-        w2s[:vs, :h2] = w2.detach()
-        w2t = w2s.t().contiguous()
-        b2p = torch.zeros(npad, dtype=torch.float32, device=dev)
-        b2p[:vs] = b2.detach()
-        return w1s, w1t, w2s, w2t, b2p
+    h2, hs = w1.shape
+    vs = w2.shape[0]
+    k0, k1, npad = _pad64(hs), _pad64(h2), _pad64(vs)
+    dev = w1.device
+    w1s = torch.zeros((h2, k0), dtype=torch.bfloat16, device=dev)
+    w1s[:, :hs] = w1.detach()
+    w1t = torch.zeros((hs, k1), dtype=torch.bfloat16, device=dev)
+    w1t[:, :h2] = w1.detach().t()
+    w2s = torch.zeros((npad, k1), dtype=torch.bfloat16, device=dev)
+    w2s[:vs, :h2] = w2.detach()
+    w2t = w2s.t().contiguous()
+    b2p = torch.zeros(npad, dtype=torch.float32, device=dev)
+    b2p[:vs] = b2.detach()
+    return w1s, w1t, w2s, w2t, b2p
 
 
 def _f32(t):
@@ -152,7 +124,7 @@ def _mlp_fwd(x, w1, b1, ln_w, ln_b, w2, b2, eps, shadows):
     tensors for ``_mlp_bwd``: z, xb, u, h, mean, rstd, gf, bf, w1t, w2t; dims (B, hs, h2, n); the seven input dtypes)."""
     B, hs = x.shape
     h2, n = w1.shape[0], w2.shape[0]
-    w1s, w1t, w2s, w2t, b2p = shadows.get(w1, w2, b2)
+    w1s, w1t, w2s, w2t, b2p = shadows.get('vqa', (w1, w2, b2), lambda: _pad_vqa_head(w1, w2, b2))
     k0, k1, npad = w1s.shape[1], w2s.shape[1], w2s.shape[0]
     dev = x.device
     xb = torch.zeros((B, k0), dtype=torch.bfloat16, device=dev) if k0 != hs else torch.empty((B, k0), dtype=torch.bfloat16, device=dev)
@@ -396,7 +368,7 @@ class MLMHead(nn.Module):
     def loss_and_pred(self, x, labels, ignore_index=-100):
         """fused decoder + cross-entropy: (mean loss over rows whose label is not ignore_index, arg-max [n])."""
         return LinearCrossEntropyFn.apply(self.transform(x), self.decoder.weight, self.bias, labels, ignore_index,
-                                          lazy_attr(self, '_ce_shadows', _PaddedShadows))
+                                          derived.of(self))
 
 
 class MIMHead(nn.Module):
@@ -410,8 +382,7 @@ class MIMHead(nn.Module):
         return self.fc(x)
 
     def loss_and_pred(self, x, labels, ignore_index=-100):
-        return LinearCrossEntropyFn.apply(x, self.fc.weight, self.fc.bias, labels, ignore_index,
-                                          lazy_attr(self, '_ce_shadows', _PaddedShadows))
+        return LinearCrossEntropyFn.apply(x, self.fc.weight, self.fc.bias, labels, ignore_index, derived.of(self))
 
 
 class ITCHead(nn.Module):

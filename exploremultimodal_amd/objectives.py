@@ -309,10 +309,11 @@ def _vqa_head(model, feats, targets, isda=False):
     head = model.vqa_classifier
     last = model.vqa_last
     if feats.is_cuda:
-        from .heads import VQAHeadFn, VQAIsdaHeadFn, _VQAShadows, lazy_attr
+        from . import derived
+        from .heads import VQAHeadFn, VQAIsdaHeadFn
         fc1, ln = head[0], head[1]
         fc2 = head[3] if last is None else last
-        shadows = lazy_attr(model, '_vqa_shadows', _VQAShadows)
+        shadows = derived.of(model)
         out_dtype = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else torch.float32
         if isda:
             est = model.isda_head.estimator

@@ -16,14 +16,15 @@ DEV = 'cuda'
 
 @pytest.mark.parametrize('n,d,V,ignore', [(27, 128, 1000, 0), (300, 768, 8192, 0), (146, 256, 30522, 5), (1, 64, 70, 0)])
 def test_linear_cross_entropy_matches_torch(n, d, V, ignore):
-    from exploremultimodal_amd.heads import LinearCrossEntropyFn, _PaddedShadows
+    from exploremultimodal_amd.derived import Holder
+    from exploremultimodal_amd.heads import LinearCrossEntropyFn
     g = torch.Generator().manual_seed(n + V)
     x = (torch.randn(n, d, generator=g)).to(DEV).bfloat16().float().requires_grad_(True)
     W = (torch.randn(V, d, generator=g) * 0.05).to(DEV).bfloat16().float().requires_grad_(True)
     b = (torch.randn(V, generator=g) * 0.1).to(DEV).requires_grad_(True)
     labels = torch.randint(0, V, (n,), generator=g).to(DEV)
     labels[:ignore] = -100
-    loss, pred = LinearCrossEntropyFn.apply(x, W, b, labels, -100, _PaddedShadows())
+    loss, pred = LinearCrossEntropyFn.apply(x, W, b, labels, -100, Holder())
     (loss * 3.0).backward()
     got = [t.grad.clone() for t in (x, W, b)]
     for t in (x, W, b):

@@ -7,7 +7,8 @@ import torch
 import torch.nn.functional as F
 
 from exploremultimodal_amd import hip
-from exploremultimodal_amd.heads import VQAHeadFn, VQAIsdaHeadFn, _VQAShadows
+from exploremultimodal_amd.derived import Holder
+from exploremultimodal_amd.heads import VQAHeadFn, VQAIsdaHeadFn
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -139,7 +140,7 @@ def _head_inputs(B, hs, seed, vs=VS):
 def _run_isda(params, y, est, ratio, dlogits_seed=None):
     ps = [p.clone().requires_grad_(True) for p in params]
     count, mean, cov = (t.clone() for t in est)
-    logits, loss, arg, score = VQAIsdaHeadFn.apply(*ps, y, 1e-12, torch.float32, _VQAShadows(), count, mean, cov, ratio)
+    logits, loss, arg, score = VQAIsdaHeadFn.apply(*ps, y, 1e-12, torch.float32, Holder(), count, mean, cov, ratio)
     total = loss
     if dlogits_seed is not None:
         gl = torch.Generator(device=DEV).manual_seed(dlogits_seed)
@@ -208,7 +209,7 @@ def test_isda_ratio_zero_is_the_plain_head():
     est = _estimator(VS, 256, 2)
     logits, loss, arg, score, grads, (count, _, _) = _run_isda(params, y, est, 0.0, dlogits_seed=5)
     ps = [p.clone().requires_grad_(True) for p in params]
-    l2, loss2, arg2, score2 = VQAHeadFn.apply(*ps, y, 1e-12, torch.float32, _VQAShadows())
+    l2, loss2, arg2, score2 = VQAHeadFn.apply(*ps, y, 1e-12, torch.float32, Holder())
     gl = torch.Generator(device=DEV).manual_seed(5)
     (loss2 + (l2 * torch.randn(l2.shape, device=DEV, generator=gl) * 1e-3).sum()).backward()
     assert torch.equal(logits, l2.detach()) and torch.equal(loss, loss2.detach())
@@ -242,6 +243,6 @@ def test_isda_bad_arguments():
         hip.isda_update(torch.zeros(B, A, device=DEV), y, B, VS, A, count, mean.half(), cov, k)
     params, yy = _head_inputs(B, 256, seed=1)
     with pytest.raises(ValueError, match='targets'):
-        VQAIsdaHeadFn.apply(*params, yy[:, :100], 1e-12, torch.float32, _VQAShadows(), count, mean, cov, 1.0)
+        VQAIsdaHeadFn.apply(*params, yy[:, :100], 1e-12, torch.float32, Holder(), count, mean, cov, 1.0)
     with pytest.raises(ValueError, match='buffers'):
-        VQAIsdaHeadFn.apply(*params, yy, 1e-12, torch.float32, _VQAShadows(), count, mean, cov, 1.0)   # buffers 256 wide, head 512
+        VQAIsdaHeadFn.apply(*params, yy, 1e-12, torch.float32, Holder(), count, mean, cov, 1.0)   # buffers 256 wide, head 512

@@ -140,7 +140,8 @@ def test_isda_autocast_step(golden, amp_dtype):
 def test_isda_peak_memory_at_base_widths():
     """Head alone at VLMo-Base widths (hs 768, 2hs 1536, 3129 answers), B 64: the ISDA step may hold at most 64 MB
     more than the plain head (the reference form needs > 1.2 GB for one [B, vs, 2hs] fp32 tensor)."""
-    from exploremultimodal_amd.heads import VQAHeadFn, VQAIsdaHeadFn, _VQAShadows
+    from exploremultimodal_amd.derived import Holder
+    from exploremultimodal_amd.heads import VQAHeadFn, VQAIsdaHeadFn
     B, hs, vs = 64, 768, 3129
     g = torch.Generator(device=DEV).manual_seed(0)
     x = torch.randn(B, hs, device=DEV, generator=g)
@@ -167,7 +168,7 @@ def test_isda_peak_memory_at_base_widths():
         torch.cuda.synchronize()
         return torch.cuda.max_memory_allocated() - base
 
-    sh1, sh2 = _VQAShadows(), _VQAShadows()
+    sh1, sh2 = Holder(), Holder()
     plain = peak(lambda: VQAHeadFn.apply(x, *params, y, 1e-12, torch.float32, sh1)[1].backward())
     isda = peak(lambda: VQAIsdaHeadFn.apply(x, *params, y, 1e-12, torch.float32, sh2, count, mean, cov, 3.75)[1].backward())
     print(f'peak plain {plain / 2**20:.1f} MB, isda {isda / 2**20:.1f} MB')

@@ -25,7 +25,7 @@ from exploremultimodal_amd import hip  # noqa: E402
 
 K = 64
 POOL = 146                  # rows of a case's pool; the M-row cases take its first M rows
-PAD = 6                     # the CE cases leave the last 6 columns to the padding of _PaddedShadows (30 522 -> 30 528)
+PAD = 6                     # the CE cases leave the last 6 columns to the padding of the bf16 head copies (30 522 -> 30 528)
 SPARE = 4                   # guard rows behind a partial buffer (>= one 256-wide tile of chunks even at ldo = 1)
 SENTINEL = 0x7FC0DEAD       # a quiet-NaN bit pattern no kernel result can equal (not a column index, not a sum)
 CE_SHAPES = [(N, M) for N in (64, 192, 320, 4160, 128) for M in (1, 5, 130)] + [(30528, 146)]
@@ -332,11 +332,12 @@ def _e2e_check(x, W, b, lab, shadows=None, scale=3.0):
     """Loss within LOSS_BOUND of fp64.  Gradients element by element, relative to the gradient's largest element:
     GRAD_FLOOR plus the bf16 rounding of dlogits (2^-8) times sqrt(reduction length); and, tighter, within what that
     rounding can do to this very element at worst, 2^-8 * sum |dlogits| |other operand|.  -> the loss."""
-    from exploremultimodal_amd.heads import LinearCrossEntropyFn, _PaddedShadows
+    from exploremultimodal_amd.derived import Holder
+    from exploremultimodal_amd.heads import LinearCrossEntropyFn
     n, V = x.shape[0], W.shape[0]
     xd, Wd = x.to(DEV).requires_grad_(True), W.to(DEV).requires_grad_(True)
     bd = None if b is None else b.to(DEV).requires_grad_(True)
-    loss, pred = LinearCrossEntropyFn.apply(xd, Wd, bd, lab.to(DEV), -100, shadows or _PaddedShadows())
+    loss, pred = LinearCrossEntropyFn.apply(xd, Wd, bd, lab.to(DEV), -100, shadows or Holder())
     (loss * scale).backward()
     ref_loss, rdx, rdW, rdb, adl = _e2e_reference(x, W, b, lab, scale)
     err = abs(loss.item() - ref_loss.item())
@@ -376,10 +377,11 @@ def test_linear_cross_entropy_without_bias(V):
 
 @pytest.mark.parametrize('V', [70, 30522])
 def test_linear_cross_entropy_all_rows_ignored(V):
-    from exploremultimodal_amd.heads import LinearCrossEntropyFn, _PaddedShadows
+    from exploremultimodal_amd.derived import Holder
+    from exploremultimodal_amd.heads import LinearCrossEntropyFn
     x, W, b, lab = _e2e_case(V)
     xd, Wd, bd = (t.to(DEV).requires_grad_(True) for t in (x, W, b))
-    loss, _ = LinearCrossEntropyFn.apply(xd, Wd, bd, torch.full_like(lab, -100).to(DEV), -100, _PaddedShadows())
+    loss, _ = LinearCrossEntropyFn.apply(xd, Wd, bd, torch.full_like(lab, -100).to(DEV), -100, Holder())
     (loss * 3.0).backward()
     assert loss.item() == 0.0
     for name, t in zip(('dx', 'dW', 'db'), (xd, Wd, bd)):
@@ -389,9 +391,10 @@ def test_linear_cross_entropy_all_rows_ignored(V):
 def test_linear_cross_entropy_follows_an_in_place_weight_update():
     """The bf16 shadow copies are keyed by the parameters' version counters: after W.mul_ the same shadow object must
     serve the new weights."""
-    from exploremultimodal_amd.heads import LinearCrossEntropyFn, _PaddedShadows
+    from exploremultimodal_amd.derived import Holder
+    from exploremultimodal_amd.heads import LinearCrossEntropyFn
     x, W, b, lab = _e2e_case(190)
-    sh = _PaddedShadows()
+    sh = Holder()
     Wd, bd = W.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
     labd, xd = lab.to(DEV), x.to(DEV)
     first, _ = LinearCrossEntropyFn.apply(xd, Wd, bd, labd, -100, sh)

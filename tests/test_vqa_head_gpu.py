@@ -148,10 +148,11 @@ def _head(hs, seed=0):
 
 
 def _head_apply(head, x, y, out_dtype=torch.float32):
-    from exploremultimodal_amd.heads import VQAHeadFn, _VQAShadows
+    from exploremultimodal_amd.derived import Holder
+    from exploremultimodal_amd.heads import VQAHeadFn
     fc1, ln, _, fc2 = head
     if not hasattr(head, '_sh'):
-        object.__setattr__(head, '_sh', _VQAShadows())
+        object.__setattr__(head, '_sh', Holder())
     return VQAHeadFn.apply(x, fc1.weight, fc1.bias, ln.weight, ln.bias, fc2.weight, fc2.bias, y, ln.eps, out_dtype,
                            head._sh)
 

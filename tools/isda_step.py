@@ -115,7 +115,8 @@ class _RefEstimator:
 
 
 def run_ab(hs, B, iters, rounds=3):
-    from exploremultimodal_amd.heads import VQAHeadFn, VQAIsdaHeadFn, _VQAShadows
+    from exploremultimodal_amd.derived import Holder
+    from exploremultimodal_amd.heads import VQAHeadFn, VQAIsdaHeadFn
     torch.manual_seed(hs)
     h2 = 2 * hs
     cls = torch.nn.Sequential(torch.nn.Linear(hs, h2), torch.nn.LayerNorm(h2, eps=1e-12), torch.nn.GELU()).cuda()
@@ -126,7 +127,7 @@ def run_ab(hs, B, iters, rounds=3):
     count = torch.zeros(VS, device='cuda')
     mean = torch.zeros(VS, h2, device='cuda')
     cov = torch.rand(VS, h2, device='cuda')
-    sh1, sh2 = _VQAShadows(), _VQAShadows()
+    sh1, sh2 = Holder(), Holder()
     ref = _RefEstimator(h2)
     ratio = 0.25
 

@@ -71,9 +71,10 @@ def _head(hs):
 
 
 def run_ab(hs, B, iters, rounds=5):
-    from exploremultimodal_amd.heads import VQAHeadFn, _VQAShadows
+    from exploremultimodal_amd.derived import Holder
+    from exploremultimodal_amd.heads import VQAHeadFn
     head = _head(hs)
-    sh = _VQAShadows()
+    sh = Holder()
     x = torch.randn(B, hs, device='cuda', requires_grad=True)
     y = synth.synth_vqa_targets(B, VS).cuda()
     fc1, ln, _, fc2 = head
