@@ -11,48 +11,57 @@ namespace {
 
 constexpr int OPT_THREADS = 256;
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
+// Sum over the workgroup in double, for the gradient norm: the order of the tensors in the table and the load path a chunk
+// takes should not show in its value (see mt_sqnorm_kernel).
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) red[w] = v;
     __syncthreads();
-    float t = 0.f;
-    if (threadIdx.x < OPT_THREADS / 64) t = red[threadIdx.x];
-    if (w == 0) t = wave_sum(t);
-    return t;      // valid in wave 0
+    double t = 0.0;
+#pragma unroll
+    for (int i = 0; i < OPT_THREADS / 64; ++i) t += red[i];
+    return t;      // valid in every thread
 }
 
-// partial[c] = sum of g^2 over chunk c
+// partial[c] = sum of g^2 over chunk c.  Squares (exact in double) and sums are taken in double and the chunk's total is
+// rounded to fp32 once.  The double sum still depends on its order, at ~1e-16 relative per addition, so before the rounding
+// the value is the exact sum's to ~1e-13; two orders round to different fp32 values only when the exact sum lies that close
+// to the midpoint of two floats (1e-13 against a spacing of 6e-8: a few chunks in a million).  So the 16-byte path and the scalar one, and FusedAdam
+// (tensors in group order) and ZeroAdam at world size 1 (the same tensors in bucket order), give the same norm except for
+// such a tie: overwhelmingly likely, not guaranteed.
 __global__ __launch_bounds__(OPT_THREADS) void mt_sqnorm_kernel(const VlmoTensorList tl, float* __restrict__ partial) {
-    __shared__ float red[OPT_THREADS / 64];
+    __shared__ double red[OPT_THREADS / 64];
     const int c = blockIdx.x;
     const int t = tl.chunk_tensor[c];
     const int64_t off = tl.chunk_start[c];
     const int64_t n = min((int64_t)tl.chunk, tl.numel[t] - off);
     const float* g = (const float*)tl.g[t] + off;
-    float a = 0.f;
+    double a = 0.0;
+    auto sq = [&](float x) { a = fma((double)x, (double)x, a); };
     if ((((uintptr_t)g) & 15) == 0) {
         const int64_t n4 = n >> 2;
         for (int64_t i = threadIdx.x; i < n4; i += OPT_THREADS) {
             const f32x4 v = ((const f32x4*)g)[i];
-            a += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+            sq(v[0]), sq(v[1]), sq(v[2]), sq(v[3]);
         }
-        for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += OPT_THREADS) a += g[i] * g[i];
+        for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += OPT_THREADS) sq(g[i]);
     } else {
-        for (int64_t i = threadIdx.x; i < n; i += OPT_THREADS) a += g[i] * g[i];
+        for (int64_t i = threadIdx.x; i < n; i += OPT_THREADS) sq(g[i]);
     }
-    const float s = block_sum(a, red);
-    if (threadIdx.x == 0) partial[c] = s;
+    const double s = block_sum_d(a, red);
+    if (threadIdx.x == 0) partial[c] = (float)s;
 }
 
 // out[0] = ||g||_2, out[1] = clip coefficient min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0),
 // out[2] = 1 if the norm is not finite (the update is then skipped, as torch.cuda.amp.GradScaler.step does)
 __global__ __launch_bounds__(OPT_THREADS) void mt_norm_finish_kernel(const float* __restrict__ partial, int n, float inv_scale,
                                                                     float max_norm, float* __restrict__ out) {
-    __shared__ float red[OPT_THREADS / 64];
-    double a = 0.0;     // fixed summation order: deterministic
+    __shared__ double red[OPT_THREADS / 64];
+    double a = 0.0;     // double to the end: the order of the partials shows only below 1e-13 of the sum
     for (int i = threadIdx.x; i < n; i += OPT_THREADS) a += (double)partial[i];
-    const float s = block_sum((float)a, red);
+    const float s = (float)block_sum_d(a, red);
     if (threadIdx.x == 0) {
         const float norm = sqrtf(s) * inv_scale;
         const bool bad = !(norm == norm) || norm > 3.0e38f;

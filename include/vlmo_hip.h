@@ -348,7 +348,9 @@ typedef struct {
 
 /* out[0] = || inv_scale * g ||_2 over every tensor of the list, out[1] = the factor to apply to the raw
  * gradients = inv_scale * min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_; max_norm <= 0:
- * no clipping), out[2] = 1 if the norm is not finite.  partial: n_chunks floats of scratch.  Deterministic. */
+ * no clipping), out[2] = 1 if the norm is not finite.  partial: n_chunks floats of scratch.  Deterministic, and
+ * summed in double: another order of the same tensors, or another alignment, changes the sum below 1e-13 of it, so
+ * the fp32 result is the same but for a tie in the final roundings. */
 int vlmo_mt_grad_norm(const VlmoTensorList* tl, float inv_scale, float max_norm, float* partial, float* out,
                       hipStream_t stream);
 /* One Adam step on every tensor.  ctl = the 3 floats of vlmo_mt_grad_norm (gradients are multiplied by
