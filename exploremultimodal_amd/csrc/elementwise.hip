@@ -805,7 +805,7 @@ extern "C" int vlmo_embed_img_finish(const void* proj, const float* cls_tok, con
                                      const float* type_row, const uint8_t* masked_pos, float* x, int B, int npatch,
                                      int d, uint32_t drop_thresh, float inv_keep, uint64_t seed, hipStream_t stream) {
     VLMO_CHECK_ARG(proj && cls_tok && mask_tok && pos && type_row && x, "vlmo_embed_img_finish: null pointer");
-    VLMO_CHECK_ARG(B > 0 && npatch > 0 && d % 4 == 0 && d <= 4096, "vlmo_embed_img_finish: bad shape");
+    VLMO_CHECK_ARG(B > 0 && npatch > 0 && d > 0 && d % 4 == 0 && d <= 4096, "vlmo_embed_img_finish: bad shape");
     hipLaunchKernelGGL(embed_img_finish_kernel, dim3(npatch + 1, B), dim3(d / 4), 0, stream, (const bf16*)proj, cls_tok,
                        mask_tok, pos, type_row, masked_pos, x, npatch, d, drop_thresh, inv_keep, seed);
     VLMO_CHECK_LAUNCH("vlmo_embed_img_finish");
@@ -816,7 +816,7 @@ extern "C" int vlmo_embed_img_bwd(const float* dx, const uint8_t* masked_pos, vo
                                   float* dpos, float* dtype_row, int B, int npatch, int d, uint32_t drop_thresh,
                                   float inv_keep, uint64_t seed, hipStream_t stream) {
     VLMO_CHECK_ARG(dx && dproj, "vlmo_embed_img_bwd: null pointer");
-    VLMO_CHECK_ARG(B > 0 && npatch > 0 && d % 4 == 0 && d <= 4096, "vlmo_embed_img_bwd: bad shape");
+    VLMO_CHECK_ARG(B > 0 && npatch > 0 && d > 0 && d % 4 == 0 && d <= 4096, "vlmo_embed_img_bwd: bad shape");
     hipLaunchKernelGGL(embed_img_bwd_kernel, dim3(npatch + 1), dim3(d / 4), 0, stream, dx, masked_pos, (bf16*)dproj,
                        dcls, dmask, dpos, dtype_row, B, npatch, d, drop_thresh, inv_keep, seed);
     VLMO_CHECK_LAUNCH("vlmo_embed_img_bwd");
@@ -828,7 +828,7 @@ extern "C" int vlmo_embed_txt_fwd(const int64_t* ids, const float* word, const f
                                   float* rstd, int B, int T, int d, float eps, uint32_t drop_thresh, float inv_keep,
                                   uint64_t seed, hipStream_t stream) {
     VLMO_CHECK_ARG(ids && word && pos && btype0 && ln_w && ln_b && type0 && x, "vlmo_embed_txt_fwd: null pointer");
-    VLMO_CHECK_ARG(B > 0 && T > 0 && d % 4 == 0 && d <= 1024, "vlmo_embed_txt_fwd: bad shape");
+    VLMO_CHECK_ARG(B > 0 && T > 0 && d > 0 && d % 4 == 0 && d <= 1024, "vlmo_embed_txt_fwd: bad shape");
     const int ntok = B * T;
     const int grid = (ntok + 3) / 4 < 8192 ? (ntok + 3) / 4 : 8192;
     dispatch_vpl(d, [&](auto V) {
@@ -844,7 +844,7 @@ extern "C" int vlmo_embed_txt_bwd(const float* dx, const int64_t* ids, const flo
                                   float* dln_b, float* dtype0, int B, int T, int d, uint32_t drop_thresh,
                                   float inv_keep, uint64_t seed, hipStream_t stream) {
     VLMO_CHECK_ARG(dx && ids && xhat && rstd && ln_w, "vlmo_embed_txt_bwd: null pointer");
-    VLMO_CHECK_ARG(B > 0 && T > 0 && d % 4 == 0 && d <= 1024, "vlmo_embed_txt_bwd: bad shape");
+    VLMO_CHECK_ARG(B > 0 && T > 0 && d > 0 && d % 4 == 0 && d <= 1024, "vlmo_embed_txt_bwd: bad shape");
     const int ntok = B * T;
     const int rpb = B >= 64 ? 16 : (B >= 16 ? 8 : 4);         // sequences per workgroup (one position each)
     const int grid = T * ((B + rpb - 1) / rpb);

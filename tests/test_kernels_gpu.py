@@ -467,6 +467,7 @@ def test_attention_dropout_statistics():
 
 
 def test_colsum_cast_patchify():
+    """one shape; the widths, batch sizes and launch regimes of training are in tests/test_embedding_kernels_gpu.py"""
     M, N = 1000, 768
     x = _rand(M, N, seed=1)
     out = torch.zeros(N, device=DEV)
@@ -485,6 +486,7 @@ def test_colsum_cast_patchify():
 
 
 def test_embed_img_fwd_bwd():
+    """one shape; the widths, batch sizes and launch regimes of training are in tests/test_embedding_kernels_gpu.py"""
     B, npatch, d = 3, 16, 128
     proj = _rand(B * npatch, d, seed=1)
     cls_tok, mask_tok = [_rand(d, seed=s, dtype=torch.float32) for s in (2, 3)]
@@ -512,6 +514,7 @@ def test_embed_img_fwd_bwd():
 
 
 def test_embed_txt_fwd_bwd():
+    """one shape; the widths, batch sizes and launch regimes of training are in tests/test_embedding_kernels_gpu.py"""
     B, T, d, V = 3, 16, 128, 50
     ids = torch.randint(0, V, (B, T)).to(DEV)
     ids[0, 5:] = 0
