@@ -32,6 +32,9 @@ reference obtains with a hook and ``retain_grad()`` on the ``attn`` tensor.  kin
 'cam' (the default) P * max(G, 0).  The zero rules above hold for every kind, 'grad' included; ``head_mean`` is the mean
 over heads of the per-head output (of the products, not the product of the means).  Shapes, windows and memory are those
 of the maps.
+
+Relevance over the depth (Chefer et al.'s propagation, attention rollout; ``vlmo_relevance_step``): the head-mean maps of
+the layers multiplied into relevance rows from the top layer down -- defined where the relevance_* functions begin.
 """
 import torch
 
@@ -225,4 +228,160 @@ def gradcam_capture(block, store, key, queries=None, head_mean=False, kind='cam'
         maps = {name: attention_gradcam(qkv, dctx, seg, plan.B, n, block.num_heads, plan.keymask, block.attn.scale,
                                         queries, head_mean, kind) for name, seg, n in kinds}
         store[key] = maps[None] if len(kinds) == 1 else maps
+    return capture
+
+
+# ---- relevance over the depth: Chefer et al.'s propagation and attention rollout (vlmo_relevance_step) ------------------
+#
+# With Abar_l the [B, N, N] head-mean map of layer l in the token order of forward_features (text first) -- 'gradcam':
+# mean_h P_h * max(G_h, 0), (alpha, beta) = (1, 1); 'rollout': mean_h P_h, (alpha, beta) = (0.5, 0.5); below the fusion layer
+# of an image-text pass blockdiag(Abar_txt [T, T], Abar_img [P, P]) -- the relevance is
+#
+#     R = prod_{l = L-1 .. 0} (alpha I + beta Abar_l)          (top layer leftmost)
+#
+# which is R <- alpha R + beta Abar_l R from layer 0 upward, starting at I.  Only rows are wanted, so rows are carried from
+# the top layer downward: X = I[q0 : q0 + nq], then X <- alpha X + beta X @ Abar_l for l = L-1 .. 0 (relevance_step).  A
+# layer that is left out contributes the factor I.  Nothing is normalised; every quantity is >= 0.  Zero rules, from those of
+# the maps: a masked key is a zero column of every Abar_l, so its relevance column holds the identity part only (alpha^L on
+# its own row, 0 elsewhere); a query row whose keys are all masked propagates alpha X only.
+
+METHODS = {'gradcam': (1.0, 1.0), 'rollout': (0.5, 0.5)}
+
+
+def method_weights(method):
+    """(alpha, beta) of ``method``; ValueError for an unknown one."""
+    if method not in METHODS:
+        raise ValueError(f'method must be one of {tuple(METHODS)}, got {method!r}')
+    return METHODS[method]
+
+
+def resolve_rows(queries, N):
+    """queries=(q0, nq) over the N concatenated tokens (None: all of them) -> (q0, nq); ValueError outside [0, N]."""
+    q0, nq = (0, N) if queries is None else (int(queries[0]), int(queries[1]))
+    if q0 < 0 or nq < 1 or q0 + nq > N:
+        raise ValueError(f'queries=({q0}, {nq}) is not a window of the {N} tokens')
+    return q0, nq
+
+
+def check_layers(layers, L):
+    """The ``layers`` argument of the relevance entry points -> ascending list (None: all); ValueError for an index outside
+    [0, L) and for an unsorted or repeated list (the product has an order: a list that states another one is refused)."""
+    if layers is None:
+        return list(range(L))
+    layers = [int(i) for i in layers]
+    if any(i < 0 or i >= L for i in layers):
+        raise ValueError(f'layers must be block indices in [0, {L}), got {layers}')
+    if any(b <= a for a, b in zip(layers, layers[1:])):
+        raise ValueError(f'layers must be strictly ascending, got {layers}')
+    return layers
+
+
+def _square(m, what):
+    """A head-mean map [B, 1, n, n] or [B, n, n] -> [B, n, n]."""
+    if m.dim() == 4 and m.shape[1] == 1:
+        m = m[:, 0]
+    if m.dim() != 3 or m.shape[1] != m.shape[2]:
+        raise ValueError(f'{what} must be a head-mean map of every query row, [B, 1, n, n] or [B, n, n], got '
+                         f'{tuple(m.shape)}')
+    return m
+
+
+def _blocks(m, N, T):
+    """A layer's map or {'txt', 'img'} dict -> [(c0, Abar [B, n, n])], the diagonal blocks that tile the N columns."""
+    if isinstance(m, dict):
+        if set(m) != {'txt', 'img'}:
+            raise ValueError(f"a per-modality layer must be {{'txt': ..., 'img': ...}}, got keys {sorted(m)}")
+        txt, img = _square(m['txt'], "the 'txt' map"), _square(m['img'], "the 'img' map")
+        if txt.shape[1] + img.shape[1] != N or (T is not None and txt.shape[1] != T) or txt.shape[0] != img.shape[0]:
+            raise ValueError(f'per-modality maps of {txt.shape[1]} + {img.shape[1]} tokens do not tile N={N} (T={T})')
+        return [(0, txt), (txt.shape[1], img)]
+    m = _square(m, 'a map')
+    if m.shape[1] != N:
+        raise ValueError(f'a map of {m.shape[1]} tokens where N={N}')
+    return [(0, m)]
+
+
+def relevance_step(A, x, c0=0, alpha=1.0, beta=1.0):
+    """One step of the row form: a NEW tensor y [S, nq, width] with
+    y[s, r, c0 + j] = alpha x[s, r, c0 + j] + beta sum_{k < n} x[s, r, c0 + k] A[s, k, j] for A [S, n, n], and the columns
+    outside [c0, c0 + n) copied from x.  Device fp32 contiguous tensors take the HIP kernel (vlmo_relevance_step); CPU
+    tensors take this restatement in their own dtype."""
+    if A.dim() != 3 or A.shape[1] != A.shape[2] or x.dim() != 3 or x.shape[0] != A.shape[0]:
+        raise ValueError(f'need A [S, n, n] and x [S, nq, width], got {tuple(A.shape)} and {tuple(x.shape)}')
+    n, width = A.shape[1], x.shape[2]
+    c0 = int(c0)
+    if c0 < 0 or c0 + n > width:
+        raise ValueError(f'columns [{c0}, {c0 + n}) are not inside the width {width}')
+    if not x.is_cuda:
+        y = x.clone()
+        y[:, :, c0:c0 + n] = alpha * x[:, :, c0:c0 + n] + beta * (x[:, :, c0:c0 + n] @ A.to(x.dtype))
+        return y
+    if A.dtype != torch.float32 or x.dtype != torch.float32 or not A.is_contiguous() or not x.is_contiguous():
+        raise ValueError('device A and x must be contiguous fp32 tensors')
+    y = torch.empty_like(x) if n == width else x.clone()
+    hip.relevance_step(A, x, y, c0, alpha, beta)
+    return y
+
+
+def relevance_propagate(X, m, T, alpha, beta):
+    """X <- alpha X + beta X @ Abar for the map (or per-modality dict) ``m`` of one layer -> a new [B, nq, N] tensor.  A
+    per-modality layer is one kernel call per diagonal block into the same output: the two column ranges tile the width."""
+    blocks = _blocks(m, X.shape[2], T)
+    if not X.is_cuda:
+        for c0, A in blocks:
+            X = relevance_step(A, X, c0, alpha, beta)
+        return X
+    Y = torch.empty_like(X)
+    for c0, A in blocks:
+        hip.relevance_step(A.contiguous(), X, Y, c0, alpha, beta)
+    return Y
+
+
+def relevance_rows(B, N, q0, nq, device, dtype=torch.float32):
+    """I[q0 : q0 + nq, :] for every sample -> [B, nq, N]: where the row form starts."""
+    X = torch.zeros((B, nq, N), dtype=dtype, device=device)
+    X[:, torch.arange(nq, device=device), torch.arange(q0, q0 + nq, device=device)] = 1.0
+    return X
+
+
+def relevance_reference(maps, N, T=None, queries=None, method='gradcam', dtype=torch.float32):
+    """The definition above in plain torch (any device), computed in ``dtype`` (float32 or float64): ``maps`` is
+    {layer: map-or-dict} as attention_maps / attention_gradcam return it with head_mean=True and every query row; layers
+    that are not in it contribute the factor I.  R <- alpha R + beta Abar_l R over the whole [N, N] matrix from the lowest
+    layer upward, then rows [q0, q0 + nq) -> [B, nq, N].  T (the text length) is needed only to check per-modality maps."""
+    alpha, beta = method_weights(method)
+    q0, nq = resolve_rows(queries, N)
+    if not maps:
+        raise ValueError('maps is empty: pass at least one layer')
+    R = None
+    for i in sorted(maps):
+        blocks = _blocks(maps[i], N, T)
+        if R is None:
+            B, dev = blocks[0][1].shape[0], blocks[0][1].device
+            R = torch.eye(N, dtype=dtype, device=dev).expand(B, N, N).contiguous()
+        Abar = torch.zeros((B, N, N), dtype=dtype, device=dev)
+        for c0, A in blocks:
+            Abar[:, c0:c0 + A.shape[1], c0:c0 + A.shape[1]] = A.to(dtype)
+        R = alpha * R + beta * (Abar @ R)
+    return R[:, q0:q0 + nq].contiguous()
+
+
+def relevance_heatmaps(R, T, grid):
+    """Relevance rows R [B, nq, T + 1 + grid^2] of an image-text pass (text first, then the image CLS, then the patches row
+    by row; T = 0 for an image-only pass) -> (text [B, nq, T], image [B, nq, grid, grid]).  The image-CLS column T is left
+    out, as in text_to_image_heatmaps.  Nothing is normalised: display code min-max normalises."""
+    if R.dim() != 3 or T < 0 or grid < 1 or R.shape[2] != T + 1 + grid * grid:
+        raise ValueError(f'need relevance rows [B, nq, {T + 1 + grid * grid}] (T={T}, grid={grid}), got {tuple(R.shape)}')
+    return R[:, :, :T], R[:, :, T + 1:].reshape(R.shape[0], R.shape[1], grid, grid)
+
+
+def relevance_capture(block, state, T, alpha, beta):
+    """The engine.BlockMeta.capture callback of one block call for method 'gradcam': the head-mean 'cam' map of the block
+    (every query row) from the engine's buffers, multiplied into the rows state['X'] at once -- the backward reaches the
+    captured layers top-down, which is the order the row form needs, so one Abar is alive at a time."""
+    def capture(qkv, dctx, plan, fused):
+        kinds = plan_kinds(plan, fused)
+        maps = {name: attention_gradcam(qkv, dctx, seg, plan.B, n, block.num_heads, plan.keymask, block.attn.scale,
+                                        None, True, 'cam') for name, seg, n in kinds}
+        state['X'] = relevance_propagate(state['X'], maps[None] if len(kinds) == 1 else maps, T, alpha, beta)
     return capture

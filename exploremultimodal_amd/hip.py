@@ -177,10 +177,11 @@ _SIGS = {
     'vlmo_crop_resample': [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _f32, _vp,
                            _i64, _vp],
     'vlmo_randaug': [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _vp],
+    'vlmo_relevance_step': [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp],
 }
 
 _lib = None
-ABI_VERSION = 16    # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
+ABI_VERSION = 17    # vlmo_abi_version(): struct layouts of include/vlmo_hip.h mirrored above
 
 def lib():
     """Load (once) and return the C-ABI library; raise loudly if it is missing."""
@@ -765,6 +766,21 @@ def sim_topk(q, g, k, scale=1.0, splits=0):
     _check(lib().vlmo_sim_topk(_p(q), q.stride(0), _p(g), g.stride(0), Nq, Ng, D, k, float(scale), splits, _p(ws), nbytes,
                                _p(val), _p(idx), _stream()), 'vlmo_sim_topk')
     return val, idx
+
+
+def relevance_step(A, x_in, x_out, c0, alpha, beta):
+    """vlmo_relevance_step: x_out[s, r, c0 + j] = alpha x_in[s, r, c0 + j] + beta sum_k x_in[s, r, c0 + k] A[s, k, j] for
+    A fp32 [S, n, n], x_in and x_out fp32 [S, nq, width], all contiguous on one device; the other columns of x_out are
+    left as they are."""
+    for t, name in ((A, 'A'), (x_in, 'x_in'), (x_out, 'x_out')):
+        if t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous() or t.device != A.device:
+            raise ValueError(f'relevance_step: {name} must be a contiguous 3-D fp32 tensor on the device of A')
+    S, n, n2 = A.shape
+    if n != n2 or x_in.shape != x_out.shape or x_in.shape[0] != S:
+        raise ValueError(f'relevance_step: need A [S, n, n] and x_in, x_out [S, nq, width], got {tuple(A.shape)}, '
+                         f'{tuple(x_in.shape)}, {tuple(x_out.shape)}')
+    _check(lib().vlmo_relevance_step(_p(A), _p(x_in), _p(x_out), S, x_in.shape[1], x_in.shape[2], int(c0), n, float(alpha),
+                                     float(beta), _stream()), 'vlmo_relevance_step')
 
 
 FILTER_BICUBIC, FILTER_LANCZOS = 0, 1

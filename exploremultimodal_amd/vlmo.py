@@ -544,7 +544,17 @@ class VLMO(nn.Module):
         if kind not in attnmap.KINDS:
             raise ValueError(f'kind must be one of {attnmap.KINDS}, got {kind!r}')
         plan, mode, fl, layers = self._map_plan(img, txt, img_attn_masks, txt_attn_masks, layers, fusion_layer, queries)
-        L, maps = len(self.blocks), {}
+        maps = {}
+        captures = {i: attnmap.gradcam_capture(self.blocks[i], maps, i, queries, head_mean, kind) for i in layers}
+        self._captured_backward(score_fn, plan, mode, fl, layers, captures, img, txt, img_attn_masks, txt_attn_masks,
+                                img_token_type_idx)
+        return {i: maps[i] for i in layers}
+
+    def _captured_backward(self, score_fn, plan, mode, fl, layers, captures, img, txt, img_attn_masks, txt_attn_masks,
+                           img_token_type_idx):
+        """The forward and backward of attention_gradcam and attention_relevance: ``layers`` (ascending) run as one-block
+        stacks with captures[i] as their capture callback, which the backward therefore calls from the top layer down."""
+        L = len(self.blocks)
         with torch.no_grad():
             leaf = self._embed(plan, img, txt, None, img_token_type_idx, 0)
         leaf.requires_grad_(True)
@@ -552,8 +562,7 @@ class VLMO(nn.Module):
             x, done = leaf, 0
             for i in layers:
                 x = self._run_blocks(x, plan, mode, fl, range(done, i), 0)
-                cb = attnmap.gradcam_capture(self.blocks[i], maps, i, queries, head_mean, kind)
-                x = self._run_blocks(x, plan, mode, fl, [i], 0, capture={i: cb})
+                x = self._run_blocks(x, plan, mode, fl, [i], 0, capture={i: captures[i]})
                 done = i + 1
             x = self._run_blocks(x, plan, mode, fl, range(done, L), 0)
             out = engine.FinalNormFn.apply(x, self.norm.weight, self.norm.bias, plan,
@@ -566,7 +575,54 @@ class VLMO(nn.Module):
                 raise ValueError('score_fn must return a scalar tensor that depends on the features it is given')
             with engine.accumulate_into_grad(False):
                 torch.autograd.grad(score, leaf)
-        return {i: maps[i] for i in layers}
+
+    def attention_relevance(self, score_fn=None, img=None, txt=None, img_attn_masks=None, txt_attn_masks=None, layers=None,
+                            fusion_layer=None, img_token_type_idx=1, queries=None, method='gradcam'):
+        """Relevance of every token for the query tokens, aggregated over the depth -> fp32 [B, nq, N], no graph.
+
+        With Abar_l the [B, N, N] head-mean map of layer l in the token order of forward_features (N = T + P with the
+        text first; below the fusion layer of an image-text pass blockdiag(txt, img)), the result is rows
+        [q0, q0 + nq) of  prod_{l = L-1 .. 0} (alpha I + beta Abar_l)  (attnmap.py):
+          method='gradcam'  Chefer, Gur and Wolf's rule R <- R + mean_h max(grad A * A, 0) R: Abar_l is the kind='cam',
+                            head_mean=True map of attention_gradcam for score_fn, (alpha, beta) = (1, 1).  The single
+                            forward and backward of attention_gradcam, under its rules (eval mode, no attached reducer, no
+                            .grad / requires_grad changed); the rows are multiplied inside the backward, one map alive
+                            at a time.  score_fn is required.
+          method='rollout'  attention rollout R <- (0.5 I + 0.5 mean_h A) R: Abar_l is the head_mean=True map of
+                            attention_maps, (alpha, beta) = (0.5, 0.5).  Forward only; score_fn is ignored.
+        layers: ascending block indices (default all); the others contribute the factor I.  queries=(q0, nq) indexes the
+        N concatenated tokens and is accepted for every kind of pass (default all N rows); (0, 1) is the text [CLS].
+        Nothing is normalised; every value is >= 0.  A masked key's column holds only alpha^L on its own row.
+        ValueError: an unknown method, queries outside [0, N], unsorted or repeated layers, no score_fn for 'gradcam'."""
+        alpha, beta = attnmap.method_weights(method)
+        if self.training:
+            raise RuntimeError('attention_relevance needs eval mode: the maps are pre-dropout and are computed from the '
+                               'activations of a deterministic pass (call model.eval() first)')
+        if method == 'gradcam':
+            if engine.GRAD_SINK is not None:
+                raise RuntimeError('attention_relevance(method=\'gradcam\') cannot run while a gradient reducer is '
+                                   'attached: its backward pass would feed the reducer\'s buckets')
+            if score_fn is None:
+                raise ValueError("method='gradcam' needs a score_fn (the decision whose relevance is wanted)")
+        layers = attnmap.check_layers(layers, len(self.blocks))
+        plan, mode, fl, layers = self._map_plan(img, txt, img_attn_masks, txt_attn_masks, layers, fusion_layer, None)
+        N = plan.T + plan.P
+        q0, nq = attnmap.resolve_rows(queries, N)
+        X = attnmap.relevance_rows(plan.B, N, q0, nq, plan.device)
+        if not layers:
+            return X
+        if method == 'rollout':
+            maps = self.attention_maps(img=img, txt=txt, img_attn_masks=img_attn_masks, txt_attn_masks=txt_attn_masks,
+                                       layers=layers, fusion_layer=fusion_layer, img_token_type_idx=img_token_type_idx,
+                                       head_mean=True)
+            for i in reversed(layers):
+                X = attnmap.relevance_propagate(X, maps.pop(i), plan.T, alpha, beta)
+            return X
+        state = {'X': X}
+        captures = {i: attnmap.relevance_capture(self.blocks[i], state, plan.T, alpha, beta) for i in layers}
+        self._captured_backward(score_fn, plan, mode, fl, layers, captures, img, txt, img_attn_masks, txt_attn_masks,
+                                img_token_type_idx)
+        return state['X']
 
     def forward(self, img=None, txt=None, img_attn_masks=None, txt_attn_masks=None, fusion_layer=None,
                 img_token_type_idx=1):

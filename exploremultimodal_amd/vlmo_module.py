@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import objectives
+from . import attnmap, objectives
 from .heads import ISDAHead, ITCHead, ITMHead, MIMHead, MLMHead
 from .vlmo import VLMO, LayerNorm
 
@@ -256,14 +256,22 @@ class VlmoModule(nn.Module):
         itm_head(cls_feats)[:, 1], summed over the batch -- in eval mode nothing couples the samples, so every sample
         gets the gradient of its own logit; needs 'itm' among the losses.  A callable target gets the dict infer returns
         and gives a scalar tensor.  Masks and inputs are picked exactly as infer picks them."""
+        kw, score_fn = self._gradcam_inputs('attention_gradcam', batch, infer_mode, target)
+        return self.transformer.attention_gradcam(score_fn, layers=layers, queries=queries, head_mean=head_mean, kind=kind,
+                                                  **kw)
+
+    def _gradcam_inputs(self, what, batch, infer_mode, target, need_score=True):
+        """What attention_gradcam and attention_relevance share: the inputs and masks infer picks, as keyword arguments
+        of the transformer's entry point, and the score function of ``target`` (need_score=False: target is not looked
+        at and the score function is None)."""
         assert infer_mode in ['img_only', 'txt_only', 'img-txt']
         if self.training:
-            raise RuntimeError('attention_gradcam needs eval mode: the maps are pre-dropout and are computed from the '
+            raise RuntimeError(f'{what} needs eval mode: the maps are pre-dropout and are computed from the '
                                'activations of a deterministic pass (call model.eval() first)')
-        if target == 'itm':
+        if need_score and target == 'itm':
             if 'itm' not in self.loss_names:
                 raise ValueError("target='itm' needs the ITM head: build the model with 'itm' in train.loss_names")
-        elif not callable(target):
+        elif need_score and not callable(target):
             raise ValueError(f"target must be 'itm' or a callable on the dict infer returns, got {target!r}")
         transformer = self.transformer
         img, img_attn_masks, txt_ids, txt_attn_masks = None, None, None, None
@@ -282,9 +290,17 @@ class VlmoModule(nn.Module):
                    'txt_labels': None, 'txt_ids': txt_ids, 'txt_masks': txt_attn_masks}
             return self.itm_head(out['cls_feats'])[:, 1].sum() if target == 'itm' else target(out)
 
-        return transformer.attention_gradcam(score_fn, img=img, txt=txt_ids, img_attn_masks=img_attn_masks,
-                                             txt_attn_masks=txt_attn_masks, layers=layers, queries=queries,
-                                             head_mean=head_mean, kind=kind)
+        kw = dict(img=img, txt=txt_ids, img_attn_masks=img_attn_masks, txt_attn_masks=txt_attn_masks)
+        return kw, (score_fn if need_score else None)
+
+    def attention_relevance(self, batch, infer_mode='img-txt', layers=None, target='itm', queries=None, method='gradcam'):
+        """Relevance of every token for the query tokens, aggregated over the depth, of the backbone pass
+        ``infer(batch, infer_mode)`` runs -> fp32 [B, nq, N] (VLMO.attention_relevance: methods, ``layers``, ``queries``
+        over the concatenated tokens, eval mode only).  method='gradcam' takes ``target`` as attention_gradcam does;
+        method='rollout' runs forward only and ignores it.  Masks and inputs are picked exactly as infer picks them."""
+        attnmap.method_weights(method)
+        kw, score_fn = self._gradcam_inputs('attention_relevance', batch, infer_mode, target, method == 'gradcam')
+        return self.transformer.attention_relevance(score_fn, layers=layers, queries=queries, method=method, **kw)
 
     # ------------------------------------------------- merged backbone passes
     @staticmethod

@@ -82,7 +82,7 @@ typedef struct VlmoEpilogue {
 const char* vlmo_last_error(void);
 /* Version of the struct layouts and signatures below; raised whenever one of them changes
  * (exploremultimodal_amd/hip.py mirrors it as ABI_VERSION and refuses any other). */
-#define VLMO_ABI_VERSION 16
+#define VLMO_ABI_VERSION 17
 int vlmo_abi_version(void);     /* = VLMO_ABI_VERSION of the header the library was built from */
 
 /* C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue.  tile: -1 = pick by shape, 0 = 128x128x64
@@ -238,6 +238,19 @@ int vlmo_attn_probs(const void* qkv, const int32_t* seg, int num_seq, const int3
 int vlmo_attn_gradcam(const void* qkv, const void* dctx, const int32_t* seg, int num_seq, const int32_t* keymask,
                       float* out, int heads, int d, int seq_len, int q0, int nq, int kind, int head_mean, float scale,
                       hipStream_t stream);
+
+/* One step of the relevance propagation over the depth (Chefer et al.'s rule R <- R + Abar R and attention rollout
+ * R <- (0.5 I + 0.5 Abar) R, carried as rows from the top layer downward); csrc/relevance.hip.  For every sequence s:
+ *   x_out[s, r, c0 + j] = alpha * x_in[s, r, c0 + j] + beta * sum_{k < n} x_in[s, r, c0 + k] * A[s, k, j]
+ * A fp32 contiguous [num_seq, n, n] (a head-mean map of the two entry points above); x_in, x_out fp32 contiguous
+ * [num_seq, nq, width]; columns outside [c0, c0 + n) of x_out are NOT written: a block-diagonal layer (text and image
+ * attended separately) is two calls that tile the width.  fp32 operands and fp32 accumulation on the fp32 MFMA; an
+ * element is one chain over k in ascending groups of 16 whatever the grid, with no atomics and no workspace: two runs are
+ * bitwise equal.  Every access is guarded: nq, n, width and c0 need not be multiples of anything.
+ * Refused (negative status, nothing written): a null pointer; x_out overlapping x_in or A; num_seq < 1; nq < 1; n < 1;
+ * n > 1024; width > 1024; c0 < 0; c0 + n > width; non-finite alpha or beta. */
+int vlmo_relevance_step(const float* A, const float* x_in, float* x_out, int num_seq, int nq, int width, int c0, int n,
+                        float alpha, float beta, hipStream_t stream);
 
 /* Residual-branch backward (vlmo.py:194-196): dz = dx * gamma * row_scale * dropmask/(1-p);
  * dgamma += sum_m dx * row_scale * zd;  dbias += sum_m dz. */
